@@ -11,11 +11,18 @@ the reference), N = M = 256 superpoints, C = 432, warp active (max_condition_num
 inputs resident in HBM, launched as one HIP-graph replay.  Pairs shard across ranks with no
 data-path collective (weak scaling); RCCL is used only for the barrier / max-time / checksum gather.
 
-Prints ONE JSON line (rank 0) with the contract fields plus
+A plain run sets up, warms up, times the K steps and prints ONE JSON line (rank 0) with the contract
+fields (metric, value, unit, higher_is_better, dtype, ms_per_step = milliseconds of one timed step, ...).
+--dump-outputs DIR also writes what the last timed step computed to DIR/<name>.npy (see dump_outputs).
+--full adds everything else the benchmark measures or checks (each block can still be switched off by its
+--no-* option):
+  metric_gather IR / FMR / RR of the last pass through the device harness, gathered over the ranks
   roofline      dominant kernel family (by GPU time, HIP events on the launch stream) vs its peak,
                 and the batched Sinkhorn micro-benchmark vs the 8 TB/s HBM peak (north_star)
+  single_pair   latency of one pair (the literal "batch=1")
+  other_configs the short cfg3 / cfg5 / real-size B = 1 / training-step runs
   cpu_baseline  the oracle (PyTorch CPU restatement, "port") timed on this box's host cores on a
-                bounded sample of the same workload (rank 0, N = 1 only)
+                bounded sample of the same workload (rank 0, N = 1 only), with the IR / FMR parity sample
 """
 import argparse
 import json
@@ -536,6 +543,43 @@ def bench_b1_real_size(dev):
 
 MAX_LINE_BYTES = 6144               # the printed line must stay under this (asserted in main(); tests/test_bench_line.py)
 DETAILS_NAME = "bench_details.json"
+DUMP_MAX_BYTES = 64 << 20           # --dump-outputs writes at most this much
+DUMP_SAMPLE_PAIRS = 32              # pairs whose whole N x M matrices --dump-outputs writes (a fixed, seeded sample)
+DUMP_SEED = 0
+
+
+def dump_outputs(outs, d):
+    """--dump-outputs DIR: what the last timed step returned to its caller (rank 0's pairs, in pair order), as DIR/<name>.npy.
+    Every pair: R_final [P,3,3] / t_final [P,3,1] (float32), match_count [P] and match_pred [P,N+M,3] (the padded match list as
+    float32, entries past match_count set to -1).  A fixed sample of pairs (sorted, drawn with DUMP_SEED; at most DUMP_SAMPLE_PAIRS,
+    fewer where the files would pass DUMP_MAX_BYTES): their whole conf_matrix_pred and x_final ([n,N,M] float64, sample_pairs = the
+    pair indices).  The inputs are a fixed function of the arguments, so two builds run with the same arguments compare file by file."""
+    os.makedirs(d, exist_ok=True)
+    cat = lambda k: torch.cat([o[k] for o in outs]).cpu()
+    arrays = {"R_final": cat("R_final").float().numpy(), "t_final": cat("t_final").float().numpy()}
+    cnt = cat("match_count").numpy()
+    m = cat("matches_padded").numpy().astype(np.float32)
+    m[np.arange(m.shape[1])[None, :] >= cnt[:, None]] = -1.0
+    arrays.update(match_count=cnt.astype(np.float32), match_pred=m)
+    sizes = [int(o["conf_matrix_pred"].shape[0]) for o in outs]
+    P, (N, M) = sum(sizes), outs[0]["conf_matrix_pred"].shape[1:]
+    room = DUMP_MAX_BYTES - sum(a.nbytes for a in arrays.values()) - (1 << 20)
+    n = max(0, min(P, DUMP_SAMPLE_PAIRS, room // (2 * N * M * 8)))
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(P, size=n, replace=False))
+    starts = np.cumsum([0] + sizes)
+
+    def rows(k):
+        """the sampled pairs' [N, M] matrices of output k, gathered over the concurrent batches"""
+        parts = []
+        for g, o in enumerate(outs):
+            local = [int(i - starts[g]) for i in idx if starts[g] <= i < starts[g + 1]]
+            if local:
+                parts.append(o[k][local].cpu())
+        return torch.cat(parts).double().numpy() if parts else np.zeros((0, N, M))
+    arrays.update(sample_pairs=idx.astype(np.float64), conf_matrix_pred=rows("conf_matrix_pred"), x_final=rows("x_final"))
+    assert sum(a.nbytes for a in arrays.values()) <= DUMP_MAX_BYTES
+    for k, a in arrays.items():
+        np.save(os.path.join(d, k + ".npy"), np.ascontiguousarray(a))
 
 
 def _r(x, sig=6):
@@ -625,9 +669,10 @@ def compact_line(result, details_path):
             p["stress_head"] = {"error": sh["error"][:160]} if "error" in sh else _pick(sh, ("pairs", "head_gain", "pairs_within_1e4", "max_abs_ir_diff", "fmr_hip", "fmr_oracle"))
         line["ir_fmr_parity"] = p
     line["parity_ok"] = result.get("parity_ok")
-    mg = result["metric_gather"]
-    line["metric_gather"] = _pick(mg, ("backend", "n_pairs", "per_rank_pairs", "per_rank_pairs_per_s", "mean_inlier_ratio", "fmr", "registration_recall") + tuple(
-        k for k in mg if k.startswith("sum_")))
+    if "metric_gather" in result:
+        mg = result["metric_gather"]
+        line["metric_gather"] = _pick(mg, ("backend", "n_pairs", "per_rank_pairs", "per_rank_pairs_per_s", "mean_inlier_ratio", "fmr", "registration_recall") + tuple(
+            k for k in mg if k.startswith("sum_")))
     line["conf_checksum"] = result["conf_checksum"]
     line["details"] = details_path
     # (the contract's own top-level numbers keep full precision -- value x ms_per_step must stay consistent; the nested summaries are rounded)
@@ -758,6 +803,12 @@ def main():
                          "(tests/test_rccl_gpu.py); not a scaling measurement")
     ap.add_argument("--breakdown-only", action="store_true",
                     help="run only the eager, event-timed passes of one batch (the command profiled with rocprofv3 for profiles/)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run every secondary measurement and check (metric gather, roofline and kernel "
+                         "breakdown, Sinkhorn micro-benchmark, single-pair latency, other configurations, CPU baseline + parity "
+                         "sample); without it a run only sets up, warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed to DIR/<name>.npy (float32 / float64, < 64 MB in all)")
     args = ap.parse_args()
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -837,10 +888,15 @@ def main():
         args.no_single_pair = args.no_cpu_baseline = args.no_other_configs = True
     if stub:
         args.no_single_pair = args.no_cpu_baseline = args.no_breakdown = args.no_other_configs = True
+    # a plain run does what the headline needs and nothing else: every secondary measurement or check is behind --full
+    # (--breakdown-only asks for its own block by name)
+    full = args.full or args.breakdown_only
+    if not full:
+        args.no_single_pair = args.no_cpu_baseline = args.no_breakdown = args.no_other_configs = True
     # the Sinkhorn roofline micro-benchmark (batched tiles, HBM-bound) runs first: behind the MFMA-heavy loop the
     # same launch is 8 % slower (the chip is then at its power limit), which would measure the loop's heat, not the kernel
     sk_roof = None
-    if rank == 0 and world == 1 and not args.breakdown_only and not stub:
+    if rank == 0 and world == 1 and args.full and not args.breakdown_only and not stub:
         sk_roof = sinkhorn_microbench(dev)
         sk_roof["measured"] = "before the timed loop (HIP events, 20 launches after 0.3 s of warm-up launches)"
     for _ in range(max(args.warmup, 1)):
@@ -860,15 +916,18 @@ def main():
     sync()
     elapsed = time.perf_counter() - t0
     elapsed = shard.max_over_ranks(elapsed, dev)                       # max over ranks
-    # the run's ONE collective on results (RCCL over xGMI when N > 1; SURVEY 8e, vision3d/utils/distributed.py:57-64):
-    # all_reduce(SUM) of [sum IR, sum FMR, sum RR, n_pairs, sum t] of the last pass, evaluated on the device harness
-    ir, fmr, rr = evaluate(outs)
-    gathered = shard.reduce_metrics(shard.metric_vector(ir, fmr, rr, t_rank).to(dev))
-    per_rank_s = shard.gather_per_rank(t_rank, dev)
+    if args.dump_outputs and rank == 0 and not stub:
+        dump_outputs(outs, args.dump_outputs)
     per_rank_pairs = shard.gather_per_rank(P, dev)
+    if full:
+        # the run's ONE collective on results (RCCL over xGMI when N > 1; SURVEY 8e, vision3d/utils/distributed.py:57-64):
+        # all_reduce(SUM) of [sum IR, sum FMR, sum RR, n_pairs, sum t] of the last pass, evaluated on the device harness
+        ir, fmr, rr = evaluate(outs)
+        gathered = shard.reduce_metrics(shard.metric_vector(ir, fmr, rr, t_rank).to(dev))
+        per_rank_s = shard.gather_per_rank(t_rank, dev)
     checksum = torch.zeros(1, dtype=torch.float64) if stub else outs[0]["conf_matrix_pred"].sum().reshape(1).double()
     checksum = shard.gather_metrics(checksum, dev)
-    total_pairs = int(gathered["n_pairs"]) * args.steps
+    total_pairs = int(sum(per_rank_pairs)) * args.steps
     value = total_pairs / elapsed
     out = outs[0]
 
@@ -882,11 +941,12 @@ def main():
                    "state": "fp64 (quirk Q2), Sinkhorn arithmetic " + ("fp64 (DR_LOOP_STRICT_F64)" if args.strict_f64 else "fp32"), "gemm_path": "plane images (csrc/pgemm.hip), weights packed once per engine",
                    "gemm_arithmetic": "fp32 in / fp32 out; each product as %s, fp32 accumulate (error vs fp64 = that of an fp32 GEMM)" % SPLIT_TEXT, "parallelism": "pairs sharded over %d GPU(s)" % world},
         "conf_checksum": float(checksum.item()),
-        "metric_gather": dict(gathered, collective="all_reduce(SUM) of [sum IR, sum FMR, sum RR, n_pairs, sum t] (float64)",
-                              backend="gloo" if stub else ("nccl (RCCL)" if use_dist else "none (1 rank)"),
-                              per_rank_pairs=[int(p) for p in per_rank_pairs],
-                              per_rank_pairs_per_s=[p * args.steps / t for p, t in zip(per_rank_pairs, per_rank_s)]),
     }
+    if full:
+        result["metric_gather"] = dict(gathered, collective="all_reduce(SUM) of [sum IR, sum FMR, sum RR, n_pairs, sum t] (float64)",
+                                       backend="gloo" if stub else ("nccl (RCCL)" if use_dist else "none (1 rank)"),
+                                       per_rank_pairs=[int(p) for p in per_rank_pairs],
+                                       per_rank_pairs_per_s=[p * args.steps / t for p, t in zip(per_rank_pairs, per_rank_s)])
 
     if rank == 0:
         # (N > 1: rank 0 still measures the roofline of its own GPU after the timed region; single-pair latency, the

@@ -20,6 +20,9 @@ def test_cpu_stub_line_is_short_and_complete(tmp_path):
     assert len(lines[0]) < bench.MAX_LINE_BYTES
     d = json.loads(lines[0])
     assert all(k in d for k in CONTRACT) and isinstance(d["config"]["workload"], str) and "model" not in d["config"]
+    # a plain run: exactly the asked-for timed steps, and none of the blocks --full adds
+    assert d["steps"] == 2 and d["warmup"] == 1 and d["ms_per_step"] > 0
+    assert not any(k in d for k in ("metric_gather", "roofline", "sinkhorn_roofline", "single_pair", "other_configs", "cpu_baseline", "ir_fmr_parity"))
     assert d["details"] and os.path.exists(os.path.join(ROOT, d["details"]))
     full = json.load(open(os.path.join(ROOT, d["details"])))
     assert full["value"] == d["value"] or abs(full["value"] - d["value"]) <= 1e-5 * abs(full["value"])

@@ -1,12 +1,13 @@
 """GPU parity of the collate-time ops through the C ABI: dr_grid_subsample_f32, dr_radius_neighbors_f32 against
-oracle/collate_oracle.py and against the reference's own C++ (oracle/_ref, when built), and the device level loop against the
-index arrays the KPFCN backbone is tested with."""
+oracle/collate_oracle.py and against the reference's own C++ (its outputs or their digests stored in tests/golden/collate_ref.npz; the library in
+oracle/_ref as well, when built), and the device level loop against the index arrays the KPFCN backbone is tested with."""
 import numpy as np
 import pytest
 import torch
 
 from diffreg_hip import synth
 from oracle import collate_oracle as co
+from oracle import make_golden_collate as mk
 from tests.test_collate_oracle import scene, rows_equal_up_to_ties
 
 pytestmark = pytest.mark.gpu
@@ -15,13 +16,16 @@ T = lambda a: torch.from_numpy(np.ascontiguousarray(a)).cuda()
 
 @pytest.mark.parametrize("n_src,n_tgt,seed,dl", [(1400, 1200, 0, 0.05), (3000, 2500, 1, 0.05), (3000, 2500, 1, 0.1), (700, 900, 2, 0.2),
                                                  (20000, 17000, 4, 0.03), (5, 3, 5, 0.05)])
-def test_grid_subsample_bit_exact(n_src, n_tgt, seed, dl):
+def test_grid_subsample_bit_exact(golden, n_src, n_tgt, seed, dl):
     from diffreg_hip.collate import batch_grid_subsampling_kpconv
     P, L = scene(n_src, n_tgt, seed)
     sp, sl = batch_grid_subsampling_kpconv(T(P), T(L), sampleDl=dl)
     op, ol = co.grid_subsample_batch(P, L, dl)
     assert sl.dtype == torch.int32 and np.array_equal(sl.cpu().numpy(), ol)
     assert np.array_equal(sp.cpu().numpy(), op)               # same points, same order, same float32 bits
+    g, k = golden("collate_ref"), mk.sub_key(n_src, n_tgt, seed, dl)
+    if k + "_points" in g:                                    # the reference's own output, in the canonical voxel order
+        assert np.array_equal(g[k + "_lengths"], sl.cpu().numpy()) and np.array_equal(g[k + "_points"], sp.cpu().numpy())
     if co.ref_lib() is not None and n_src <= 3000:
         rp, rl = co.ref_subsample_batch(P, L, dl)
         assert np.array_equal(rp[co.canonical_order(rp, rl, P, L, dl)], sp.cpu().numpy())
@@ -43,15 +47,19 @@ def test_grid_subsample_four_clouds_and_empty():
 
 
 @pytest.mark.parametrize("n_src,n_tgt,seed,dl,limit", [(1400, 1200, 0, 0.05, 40), (3000, 2500, 1, 0.1, 35), (20000, 17000, 4, 0.03, 38)])
-def test_radius_neighbors_vs_oracle_and_reference(n_src, n_tgt, seed, dl, limit):
+def test_radius_neighbors_vs_oracle_and_reference(golden, n_src, n_tgt, seed, dl, limit):
     from diffreg_hip.collate import batch_neighbors_kpconv
     P, L = scene(n_src, n_tgt, seed)
-    sp, sl = co.grid_subsample_batch(P, L, dl)
-    for (Q, ql, S, sl_, r) in ((P, L, P, L, 1.25 * dl), (sp, sl, P, L, 1.25 * dl), (P, L, sp, sl, 2.5 * dl)):
+    g = golden("collate_ref")
+    for j, (Q, ql, S, sl_, r) in enumerate(mk.queries(P, L, dl)):
         got = batch_neighbors_kpconv(T(Q), T(S), T(ql), T(sl_), r, limit).cpu().numpy()
         if len(Q) <= 6000:
             want = co.radius_neighbors_batch(Q, S, ql, sl_, r)[:, :limit]
             assert got.dtype == np.int64 and np.array_equal(got, want)          # the oracle breaks ties like the kernel
+        key = mk.nb_key(n_src, n_tgt, seed, dl, j)
+        key = key + "_first%d" % limit if key + "_first%d" % limit in g else key
+        if key in g:                                                            # the reference's own kd-tree search, stored as row digests
+            assert mk.LIMITS[(n_src, n_tgt, seed, dl)] == limit and mk.rows_match_reference(g[key], got, Q, S)
         if co.ref_lib() is not None:
             ref = co.ref_batch_query(Q, S, ql, sl_, r)[:, :limit]                # the reference's own kd-tree search
             assert rows_equal_up_to_ties(ref.astype(np.int64), got, Q, S)
@@ -176,18 +184,16 @@ def test_radius_neighbors_more_than_cap_points_in_the_ball():
         assert np.array_equal(out.cpu().numpy(), want[:, :limit])
 
 
-def test_grid_subsample_large_cloud_and_negative_coordinates():
+def test_grid_subsample_large_cloud_and_negative_coordinates(golden):
     """131 072-pair sort (six global bitonic levels), coordinates on both sides of the origin, a cell size that does not divide
-    the extent; against the reference's own C++ when it is built, else the oracle"""
+    the extent; against the reference's own C++ (a digest of its output stored in tests/golden/collate_ref.npz; the library too when it is built)"""
     from diffreg_hip.collate import batch_grid_subsampling_kpconv
-    u = synth.hash_uniform(11, 3, (90000, 3), -1.0, 1.0)
-    P = np.stack([3.1 * u[:, 0], 2.3 * u[:, 1], 0.4 * np.sin(2 * u[:, 0]) + 0.05 * u[:, 2]], 1).astype(np.float32)
-    L = np.array([50000, 40000], np.int32)
-    sp, sl = batch_grid_subsampling_kpconv(T(P), T(L), sampleDl=0.037)
+    P, L = mk.large_cloud()
+    sp, sl = batch_grid_subsampling_kpconv(T(P), T(L), sampleDl=mk.LARGE_DL)
+    g = golden("collate_ref")
+    assert np.array_equal(g["sub_large_lengths"], sl.cpu().numpy())
+    assert mk.digest(sp.cpu().numpy()) == int(g["sub_large_points_digest"][0])
     if co.ref_lib() is not None:
-        rp, rl = co.ref_subsample_batch(P, L, 0.037)
+        rp, rl = co.ref_subsample_batch(P, L, mk.LARGE_DL)
         assert np.array_equal(rl, sl.cpu().numpy())
-        assert np.array_equal(rp[co.canonical_order(rp, rl, P, L, 0.037)], sp.cpu().numpy())
-    else:
-        op, ol = co.grid_subsample_batch(P, L, 0.037)
-        assert np.array_equal(op, sp.cpu().numpy())
+        assert np.array_equal(rp[co.canonical_order(rp, rl, P, L, mk.LARGE_DL)], sp.cpu().numpy())

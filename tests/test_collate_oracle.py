@@ -1,13 +1,12 @@
-"""CPU: the collate oracle (oracle/collate_oracle.py) against the reference's own C++ compiled from the sources where they lie
-(oracle/Makefile -> oracle/_ref/libref_collate.so; built by __graft_entry__.build() where /root/reference exists, shipped to the
-GPU box with the snapshot)."""
+"""CPU: the collate oracle (oracle/collate_oracle.py) against the reference's own C++: its outputs on these scenes are stored in
+tests/golden/collate_ref.npz (oracle/make_golden_collate.py: subsampled points, row digests of the neighbour matrices), and where oracle/_ref/libref_collate.so is built (oracle/Makefile,
+run by __graft_entry__.build() where the reference sources exist) the library itself is asked as well."""
 import numpy as np
 import pytest
 
 from diffreg_hip import synth
 from oracle import collate_oracle as co
-
-needs_ref = pytest.mark.skipif(co.ref_lib() is None, reason="oracle/_ref not built (python __graft_entry__.py build with /root/reference)")
+from oracle import make_golden_collate as mk
 
 
 def scene(n_src, n_tgt, seed, jitter=0.004):
@@ -31,26 +30,29 @@ def rows_equal_up_to_ties(a, b, Q, S):
     return True
 
 
-@needs_ref
 @pytest.mark.parametrize("n_src,n_tgt,seed,dl", [(1400, 1200, 0, 0.05), (3000, 2500, 1, 0.05), (3000, 2500, 1, 0.1), (700, 900, 2, 0.2)])
-def test_grid_subsample_oracle_vs_reference_cpp(n_src, n_tgt, seed, dl):
+def test_grid_subsample_oracle_vs_reference_cpp(golden, n_src, n_tgt, seed, dl):
     P, L = scene(n_src, n_tgt, seed)
-    rp, rl = co.ref_subsample_batch(P, L, dl)
     op, ol = co.grid_subsample_batch(P, L, dl)
-    assert np.array_equal(rl, ol)
-    perm = co.canonical_order(rp, rl, P, L, dl)
-    assert np.array_equal(rp[perm], op)                       # bit-exact barycentres, up to the unordered_map's order
+    g, k = golden("collate_ref"), mk.sub_key(n_src, n_tgt, seed, dl)
+    assert np.array_equal(g[k + "_lengths"], ol)
+    assert np.array_equal(g[k + "_points"], op)               # bit-exact barycentres (stored in the oracle's canonical voxel order)
+    if co.ref_lib() is not None:
+        rp, rl = co.ref_subsample_batch(P, L, dl)
+        assert np.array_equal(rl, ol)
+        perm = co.canonical_order(rp, rl, P, L, dl)
+        assert np.array_equal(rp[perm], op)                   # bit-exact barycentres, up to the unordered_map's order
 
 
-@needs_ref
 @pytest.mark.parametrize("n_src,n_tgt,seed,dl", [(1400, 1200, 0, 0.05), (3000, 2500, 1, 0.1)])
-def test_radius_neighbors_oracle_vs_reference_cpp(n_src, n_tgt, seed, dl):
+def test_radius_neighbors_oracle_vs_reference_cpp(golden, n_src, n_tgt, seed, dl):
     P, L = scene(n_src, n_tgt, seed)
-    sp, sl = co.grid_subsample_batch(P, L, dl)
-    for (Q, ql, S, sl_, r) in ((P, L, P, L, 1.25 * dl), (sp, sl, P, L, 1.25 * dl), (P, L, sp, sl, 2.5 * dl)):
-        rn = co.ref_batch_query(Q, S, ql, sl_, r)
+    g = golden("collate_ref")
+    for j, (Q, ql, S, sl_, r) in enumerate(mk.queries(P, L, dl)):
         on = co.radius_neighbors_batch(Q, S, ql, sl_, r)
-        assert rows_equal_up_to_ties(rn, on, Q, S)
+        assert mk.rows_match_reference(g[mk.nb_key(n_src, n_tgt, seed, dl, j)], on, Q, S)
+        if co.ref_lib() is not None:
+            assert rows_equal_up_to_ties(co.ref_batch_query(Q, S, ql, sl_, r), on, Q, S)
 
 
 def test_subsample_properties():

@@ -59,7 +59,7 @@ def test_bench_rank_path_with_the_nccl_branch_forced(capsys, monkeypatch):
     monkeypatch.setenv("WORLD_SIZE", "1"); monkeypatch.setenv("RANK", "0"); monkeypatch.setenv("LOCAL_RANK", "0")
     monkeypatch.setenv("MASTER_ADDR", "127.0.0.1"); monkeypatch.setenv("MASTER_PORT", str(29950 + os.getpid() % 40))
     monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "8", "--streams", "1",
-                                      "--dist-single-rank", "--no-cpu-baseline", "--no-other-configs", "--no-single-pair", "--no-breakdown"])
+                                      "--dist-single-rank", "--full", "--no-cpu-baseline", "--no-other-configs", "--no-single-pair", "--no-breakdown"])
     bench.main()
     assert not dist.is_initialized()                     # main() tore the group down
     line = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")][-1]
@@ -73,12 +73,12 @@ def test_bench_rank_path_with_the_nccl_branch_forced(capsys, monkeypatch):
 
 
 def test_bench_default_shape_line_is_short_and_carries_roofline_and_cpu_baseline(capsys, monkeypatch):
-    """a small run with EVERY block of the default run switched on except the other configurations (32 pairs, 2 timed passes): the printed line
+    """a small run with EVERY block of the --full run switched on except the other configurations (32 pairs, 2 timed passes): the printed line
     stays under the limit and carries `roofline` (HIP-event-timed, with PMC traffic from profiles/) and `cpu_baseline`"""
     sys.path.insert(0, ROOT)
     import bench
     monkeypatch.setenv("WORLD_SIZE", "1"); monkeypatch.setenv("RANK", "0"); monkeypatch.setenv("LOCAL_RANK", "0")
-    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "32", "--no-other-configs"])
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--gpus", "1", "--steps", "2", "--warmup", "1", "--pairs", "32", "--full", "--no-other-configs"])
     monkeypatch.setattr(bench, "cpu_baseline", lambda *a, **k: bench.__dict__["_cpu_baseline_orig"](*a, budget_s=4.0, **k))
     bench.main()
     line = [l for l in capsys.readouterr().out.splitlines() if l.startswith("{")][-1]

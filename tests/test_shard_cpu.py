@@ -47,14 +47,14 @@ def test_two_ranks_shard_and_gather():
 
 
 def _run_bench_stub(nproc, extra, gpus=None, expect_fail=False):
-    """bench.py's own multi-rank control path (torchrun environment, barrier, max time over ranks, metric-vector all_reduce)
+    """bench.py's own multi-rank control path (torchrun environment, barrier, max time over ranks, metric-vector all_reduce: --full)
     under gloo with the CPU stand-in engine (--cpu-stub)"""
     import json
     import subprocess
     port = 29600 + (os.getpid() % 300)
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(nproc), "--master-addr", "127.0.0.1",
            "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", str(nproc if gpus is None else gpus), "--steps", "3",
-           "--warmup", "1", "--cpu-stub"] + extra
+           "--warmup", "1", "--cpu-stub", "--full"] + extra
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=ROOT)
     if expect_fail:
         return r
@@ -116,18 +116,35 @@ def test_single_process_gather_is_identity():
     assert shard.gather_metrics([1.0, 2.0]).tolist() == [1.0, 2.0]
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference/Diff-Reg-3dmatch"), reason="reference tree only exists in the build container")
-def test_models_overlay_resolves_the_rest_in_reference_tree():
+def _stand_in_reference_tree(root):
+    """a checkout with the reference's package layout (3D/models, 3D/models/transformer, 3D/kernels): the modules the overlay shadows
+    are decoys that fail on import, the ones it leaves to the checkout are one-liners that record where they were found"""
+    files = {"models/__init__.py": "", "models/transformer/__init__.py": "", "kernels/__init__.py": "",
+             "kernels/kernel_points.py": "HOME = 'tree'\n",
+             "models/blocks.py": "from kernels.kernel_points import HOME\n",
+             "models/transformer/geoattention.py": "HOME = 'tree'\n",
+             "models/transformer/geotransformer.py": "from models.transformer.geoattention import HOME\n"}
+    for name in ("pipeline", "backbone", "matching", "procrustes", "transformero", "position_encoding", "loss"):
+        files["models/%s.py" % name] = "raise ImportError('the checkout shadowed the overlay: models.%s')\n" % name
+    for rel, text in files.items():
+        path = os.path.join(root, rel)
+        os.makedirs(os.path.dirname(path), exist_ok=True)
+        with open(path, "w") as f:
+            f.write(text)
+    return str(root)
+
+
+def test_models_overlay_resolves_the_rest_in_reference_tree(tmp_path):
     """our models.* shadow the hot-path modules (and the backbone, row f1); everything else (models.blocks, models.loss,
-    models.transformer.geotransformer, ...) still comes from the reference checkout."""
+    models.transformer.geotransformer, ...) still comes from the reference checkout -- here a stand-in with its package layout."""
     import subprocess
-    code = ("import sys; from unittest.mock import MagicMock; sys.modules['open3d']=MagicMock();"
-            "sys.path.insert(0,'/root/reference/Diff-Reg-3dmatch'); sys.path.insert(0,%r);"
+    tree = _stand_in_reference_tree(tmp_path / "Diff-Reg-3dmatch")
+    code = ("import sys; sys.path.insert(0,%r); sys.path.insert(0,%r);"
             "import models.pipeline as p, models.backbone as b, models.blocks as k, models.transformer.geotransformer as g;"
             "from models.transformer import RepositioningTransformer as R;"
-            "assert p.__file__.startswith(%r) and b.__file__.startswith(%r) and k.__file__.startswith('/root/reference') "
-            "and R.__module__=='models.transformero';"
-            "print('ok')") % (os.path.join(ROOT, "diff-reg_amd"), ROOT, ROOT)
+            "assert p.__file__.startswith(%r) and b.__file__.startswith(%r) and k.__file__.startswith(%r) and g.__file__.startswith(%r) "
+            "and k.HOME == g.HOME == 'tree' and R.__module__=='models.transformero';"
+            "print('ok')") % (tree, os.path.join(ROOT, "diff-reg_amd"), ROOT, ROOT, tree, tree)
     out = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
     assert out.returncode == 0 and "ok" in out.stdout, out.stderr[-2000:]
 
