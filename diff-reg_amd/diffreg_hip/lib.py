@@ -63,6 +63,11 @@ class FusionWeights(ctypes.Structure):
                                         "bin_score", "prepacked")]
 
 
+class CircleLossParams(ctypes.Structure):
+    """dr_circle_loss_params (include/diffreg_hip.h)"""
+    _fields_ = [(n, c_float) for n in ("pos_margin", "neg_margin", "pos_optimal", "neg_optimal", "log_scale", "pos_overlap", "neg_overlap")]
+
+
 class PlanesLinear(ctypes.Structure):
     """dr_planes_linear (include/diffreg_hip.h)"""
     _fields_ = [("rows", c_int), ("C", c_int), ("nblk", c_int),
@@ -217,7 +222,19 @@ SIGNATURES.update({
     "dr_mutual_topk_select_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, c_float, c_int] + [c_void_p] * 4 +
                                   [ctypes.c_longlong, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dr_denoiser_match_f32": (c_int, [_P(LoopConfig), _P(LoopWeights), c_int, c_int, c_int] + [c_void_p] * 9 +
-                              [c_void_p, c_size_t, c_void_p]),
+                              [c_void_p, c_size_t, c_void_p]),    # ABI 0.3.0: the 2D-3D training branch (dr_fusion_layer_grads has the layout of dr_fusion_layer_weights: FusionLayerWeights binds both)
+    "dr_fusion_layer_train_saved_bytes": (c_size_t, [c_int, c_int, c_int, c_int]),
+    "dr_fusion_layer_train_forward_f32": (c_int, [_P(FusionLayerWeights), c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "dr_fusion_layer_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int, c_int, c_int]),
+    "dr_fusion_layer_backward_f32": (c_int, [_P(FusionLayerWeights), c_int, c_int, c_int, c_int, c_int] + [c_void_p] * 7 +
+                                     [_P(FusionLayerWeights), c_void_p, c_size_t, c_void_p]),
+    "dr_l2_normalize_f32": (c_int, [c_int, c_int, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "dr_l2_normalize_backward_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "dr_circle_loss_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dr_circle_loss_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [_P(CircleLossParams), c_void_p, c_void_p,
+                                                                                                       c_size_t, c_void_p]),
+    "dr_circle_loss_backward_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 4 +
+                                    [_P(CircleLossParams)] + [c_void_p] * 5 + [c_size_t, c_void_p]),
 })
 
 
@@ -231,7 +248,7 @@ def _bind(table):
 _bind(SIGNATURES)
 _INIT_DONE = False
 
-ABI_VERSION = 202          # DR_ABI_VERSION of the include/diffreg_hip.h these signatures were written against
+ABI_VERSION = 300          # DR_ABI_VERSION of the include/diffreg_hip.h these signatures were written against
 if _lib.dr_version() // 100 != ABI_VERSION // 100:
     raise ImportError("libdiffreg_hip.so is ABI %d, this binding is written against %d: rebuild (make -C diff-reg_amd/csrc)"
                       % (_lib.dr_version(), ABI_VERSION))
@@ -925,6 +942,112 @@ def attention_layer_backward(tensors, C, H, x, y, cos_x, sin_x, cos_y, sin_y, x_
                                                ptr(xm), ptr(ym), ptr(saved), ptr(grad_out), ptr(gx), ptr(gy), ctypes.byref(gw), ptr(ws), wsb,
                                                stream_of(x)))
     return gx, gy, grads
+
+
+# vision3d TransformerLayer parameters (vision3d/layers/transformer.py:58-301) in the order of dr_fusion_layer_weights' fields
+FUSION_LAYER_KEYS = ("attention.attention.q_token_layer.weight", "attention.attention.q_token_layer.bias",
+                     "attention.attention.k_token_layer.weight", "attention.attention.k_token_layer.bias",
+                     "attention.attention.v_token_layer.weight", "attention.attention.v_token_layer.bias",
+                     "attention.linear.weight", "attention.linear.bias", "attention.norm.weight", "attention.norm.bias",
+                     "output.expand.weight", "output.expand.bias", "output.squeeze.weight", "output.squeeze.bias",
+                     "output.norm.weight", "output.norm.bias")
+
+
+def fusion_layer_weights(tensors):
+    """tensors: the 16 tensors of one vision3d TransformerLayer in FUSION_LAYER_KEYS order (kept alive by the caller)."""
+    lw = FusionLayerWeights()
+    for (name, _), tns in zip(FusionLayerWeights._fields_, tensors):
+        assert tns.is_cuda and tns.is_contiguous() and tns.dtype == torch.float32
+        setattr(lw, name, tns.data_ptr())
+    return lw
+
+
+def fusion_layer_train_forward(tensors, C, H, x, y, y_mask=None):
+    """TransformerLayer.forward(x, y, y) keeping what the backward needs: x [B,L,C], y [B,S,C] float32 contiguous, y_mask [B,S] (True = a valid
+    key) or None -> (out [B,L,C], saved: an opaque uint8 tensor)"""
+    ensure_init()
+    B, L, _ = x.shape
+    S = y.shape[1]
+    lw = fusion_layer_weights(tensors)
+    out = torch.empty(B, L, C, device=x.device)
+    nb = _lib.dr_fusion_layer_train_saved_bytes(B, L, S, C)
+    saved = torch.empty(nb, dtype=torch.uint8, device=x.device)
+    check(_lib.dr_fusion_layer_train_forward_f32(ctypes.byref(lw), C, H, B, L, S, ptr(x), ptr(y), ptr(mask_u8(y_mask)), ptr(out), ptr(saved), nb,
+                                                 stream_of(x)))
+    return out, saved
+
+
+def fusion_layer_backward(tensors, C, H, x, y, y_mask, saved, grad_out):
+    """-> grad_x [B,L,C], grad_y [B,S,C], the 16 parameter gradients in FUSION_LAYER_KEYS order"""
+    ensure_init()
+    B, L, _ = x.shape
+    S = y.shape[1]
+    lw = fusion_layer_weights(tensors)
+    grads = [torch.empty_like(t_) for t_ in tensors]
+    gw = fusion_layer_weights(grads)
+    gx, gy = torch.empty(B, L, C, device=x.device), torch.empty(B, S, C, device=x.device)
+    wsb = _lib.dr_fusion_layer_backward_workspace_bytes(B, H, L, S, C)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=x.device)
+    check(_lib.dr_fusion_layer_backward_f32(ctypes.byref(lw), C, H, B, L, S, ptr(x), ptr(y), ptr(mask_u8(y_mask)), ptr(saved), ptr(grad_out.contiguous()),
+                                            ptr(gx), ptr(gy), ctypes.byref(gw), ptr(ws), wsb, stream_of(x)))
+    return gx, gy, grads
+
+
+def l2_normalize(x, eps=1e-12):
+    """F.normalize(x, p=2, dim=1, eps) of rows x [R,C] -> (y, norms [R])"""
+    ensure_init()
+    x = x.contiguous().float()
+    y = torch.empty_like(x)
+    n = torch.empty(x.shape[0], device=x.device)
+    check(_lib.dr_l2_normalize_f32(x.shape[0], x.shape[1], ptr(x), float(eps), ptr(y), ptr(n), stream_of(x)))
+    return y, n
+
+
+def l2_normalize_backward(y, norms, grad_y, eps=1e-12):
+    ensure_init()
+    gx = torch.empty_like(y)
+    check(_lib.dr_l2_normalize_backward_f32(y.shape[0], y.shape[1], ptr(y), ptr(norms), float(eps), ptr(grad_y.contiguous().float()), ptr(gx),
+                                            stream_of(y)))
+    return gx
+
+
+def circle_params(pos_margin, neg_margin, pos_optimal, neg_optimal, log_scale, pos_overlap, neg_overlap):
+    return CircleLossParams(float(pos_margin), float(neg_margin), float(pos_optimal), float(neg_optimal), float(log_scale), float(pos_overlap),
+                            float(neg_overlap))
+
+
+def _circle_inputs(img, pcd, img_idx, pcd_idx, min_ov, max_ov):
+    f = lambda t_: t_.detach().contiguous().float()
+    i = lambda t_: t_.detach().contiguous().to(torch.int64)
+    return f(img), f(pcd), i(img_idx), i(pcd_idx), f(min_ov), f(max_ov)
+
+
+def circle_loss(img, pcd, img_idx, pcd_idx, min_ov, max_ov, params):
+    """weighted circle loss of feat_dists(img [M,C], pcd [N,C]) (dr_circle_loss_f32) -> 0-dim device tensor"""
+    ensure_init()
+    img, pcd, ii, jj, mn, mx = _circle_inputs(img, pcd, img_idx, pcd_idx, min_ov, max_ov)
+    (M, C), N = img.shape, pcd.shape[0]
+    loss = torch.empty((), device=img.device)
+    wsb = _lib.dr_circle_loss_workspace_bytes(M, N, C)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=img.device)
+    check(_lib.dr_circle_loss_f32(M, N, C, ptr(img), ptr(pcd), ii.numel(), ptr(ii), ptr(jj), ptr(mn), ptr(mx), ctypes.byref(params), ptr(loss), ptr(ws),
+                                  wsb, stream_of(img)))
+    return loss
+
+
+def circle_loss_backward(img, pcd, img_idx, pcd_idx, min_ov, max_ov, params, grad_loss=None):
+    """-> (loss, d loss / d img [M,C], d loss / d pcd [N,C]) scaled by grad_loss (0-dim device tensor or None = 1)"""
+    ensure_init()
+    img, pcd, ii, jj, mn, mx = _circle_inputs(img, pcd, img_idx, pcd_idx, min_ov, max_ov)
+    (M, C), N = img.shape, pcd.shape[0]
+    loss = torch.empty((), device=img.device)
+    gi, gp = torch.empty_like(img), torch.empty_like(pcd)
+    gl = None if grad_loss is None else grad_loss.detach().reshape(()).float().contiguous()
+    wsb = _lib.dr_circle_loss_workspace_bytes(M, N, C)
+    ws = torch.empty(wsb, dtype=torch.uint8, device=img.device)
+    check(_lib.dr_circle_loss_backward_f32(M, N, C, ptr(img), ptr(pcd), ii.numel(), ptr(ii), ptr(jj), ptr(mn), ptr(mx), ctypes.byref(params), ptr(gl),
+                                           ptr(loss), ptr(gi), ptr(gp), ptr(ws), wsb, stream_of(img)))
+    return loss, gi, gp
 
 
 def dual_softmax(sim, temperature, src_mask=None, tgt_mask=None):

@@ -16,18 +16,28 @@ those x_start, so `conf_matrix_pred` and everything behind it are the reference'
     from diffreg_hip.overlay2d3d import accelerate
     model = create_model(cfg).cuda().eval();  accelerate(model)          # EXP/eval.py, after loading the checkpoint
 
-Under model.train() the three calls fall through to the original code.
+Under model.train() the three calls fall through to the original code -- unless the overlay is installed with `training=True`: then the
+four modules of the differentiable training branch (EXP/model.py:386-392, 548, 615-623) -- `transformer`, `denoising_transformer`,
+`coarse_matching`, `denoising_coarse_matching` -- run on the device under model.train() (diffreg_hip/autograd2d3d.py: forward and backward in
+libdiffreg_hip, gradients into the modules' own parameters and back to the backbone features), and eval forwards keep the loop overlay:
+
+    accelerate(model, training=True);  accelerate_loss(loss_fn)          # EXP/trainval.py, after create_model / OverallLoss(cfg)
+
+accelerate_loss re-binds CoarseMatchingLoss.forward (EXP/loss.py:30-75; an OverallLoss instance: its c_loss) to the device circle + focal loss.
+The GT search, q_sample, the warp, the backbones and the fine loss stay the reference's code.
 """
 import types
 
 import torch
 
+from . import autograd2d3d
 from .engine import DenoiseEngine2D3D
 
 
 class LoopOverlay2D3D:
-    def __init__(self, model, n_head=4, engine_kwargs=None):
+    def __init__(self, model, n_head=4, engine_kwargs=None, training=False):
         self.model = model
+        self.training = bool(training)
         self.n_head = n_head
         self.engine_kwargs = dict(engine_kwargs or {})
         self.engine = None
@@ -39,12 +49,19 @@ class LoopOverlay2D3D:
         model.get_warped_from_noising_matching3D3D = self._warp
         t.forward = self._transformer
         m.forward = self._matching
+        if self.training:
+            self._orig.update(coarse_transformer=model.transformer.forward, coarse_matching=model.coarse_matching.forward)
+            model.transformer.forward = self._coarse_transformer
+            model.coarse_matching.forward = self._coarse_matching
         model._dr_overlay = self
 
     def remove(self):
         """restore the three call sites"""
         m = self.model
-        for obj, name in ((m, "get_warped_from_noising_matching3D3D"), (m.denoising_transformer, "forward"), (m.denoising_coarse_matching, "forward")):
+        sites = [(m, "get_warped_from_noising_matching3D3D"), (m.denoising_transformer, "forward"), (m.denoising_coarse_matching, "forward")]
+        if self.training:
+            sites += [(m.transformer, "forward"), (m.coarse_matching, "forward")]
+        for obj, name in sites:
             if name in obj.__dict__:
                 del obj.__dict__[name]
         m.__dict__.pop("_dr_overlay", None)
@@ -88,6 +105,8 @@ class LoopOverlay2D3D:
 
     def _transformer(self, img_feats, img_dino, img_pixels, pcd_feats, pcd_points):
         if self.model.training:
+            if self.training:
+                return autograd2d3d.fusion_module(self.model.denoising_transformer, img_feats, img_dino, img_pixels, pcd_feats, pcd_points)
             return self._orig["transformer"](img_feats, img_dino, img_pixels, pcd_feats, pcd_points)
         if self._k == 0:
             self._rec.update(img_feats=img_feats, img_dino=img_dino, img_pixels=img_pixels, pcd_feats=pcd_feats)
@@ -97,6 +116,8 @@ class LoopOverlay2D3D:
 
     def _matching(self, src_feats, tgt_feats, src_mask, tgt_mask, *args, **kwargs):
         if self.model.training:
+            if self.training:
+                return autograd2d3d.matching_head_2d3d(self.model.denoising_coarse_matching, src_feats, tgt_feats, src_mask, tgt_mask, *args, **kwargs)
             return self._orig["matching"](src_feats, tgt_feats, src_mask, tgt_mask, *args, **kwargs)
         if self._k == 0:
             r = self._rec
@@ -115,6 +136,27 @@ class LoopOverlay2D3D:
         return x_start, None, None, None
 
 
-def accelerate(model, n_head=4, **engine_kwargs):
-    """install the overlay on a MATR2D3D instance (see the module docstring); returns the LoopOverlay2D3D (`.remove()` undoes it)"""
-    return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs)
+    # ---- the training branch's coarse modules (training=True): the device path in train mode, the original code in eval mode ---------------
+    def _coarse_transformer(self, img_feats, img_dino, img_pixels, pcd_feats, pcd_points, *args, **kwargs):
+        if self.model.training and not args and not kwargs:
+            return autograd2d3d.fusion_module(self.model.transformer, img_feats, img_dino, img_pixels, pcd_feats, pcd_points)
+        return self._orig["coarse_transformer"](img_feats, img_dino, img_pixels, pcd_feats, pcd_points, *args, **kwargs)
+
+    def _coarse_matching(self, src_feats, tgt_feats, src_mask, tgt_mask, *args, **kwargs):
+        if self.model.training:
+            return autograd2d3d.matching_head_2d3d(self.model.coarse_matching, src_feats, tgt_feats, src_mask, tgt_mask, *args, **kwargs)
+        return self._orig["coarse_matching"](src_feats, tgt_feats, src_mask, tgt_mask, *args, **kwargs)
+
+
+def accelerate(model, n_head=4, training=False, **engine_kwargs):
+    """install the overlay on a MATR2D3D instance (see the module docstring); returns the LoopOverlay2D3D (`.remove()` undoes it).
+    training=True: the training branch's four coarse modules run on the device under model.train() as well."""
+    return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs, training=training)
+
+
+def accelerate_loss(loss_module):
+    """re-bind CoarseMatchingLoss.forward of `loss_module` (or of its `c_loss`: an OverallLoss) to autograd2d3d.coarse_matching_loss, on the
+    instance; returns a function that restores it"""
+    target = loss_module.c_loss if hasattr(loss_module, "c_loss") else loss_module
+    target.forward = lambda output_dict: autograd2d3d.coarse_matching_loss(target, output_dict)
+    return lambda: target.__dict__.pop("forward", None)

@@ -35,8 +35,11 @@ extern "C" {
  * minor (the Python mirror does, diffreg_hip/lib.py).  History of breaks:
  *   0.2.0  dr_loop_trace grew the teacher-forcing fields (a 0.1.0 caller's struct is too short); dr_procrustes_f32 and
  *          dr_top1_union_f32 / _f64 take (workspace, workspace_bytes) in front of `stream` since the last 0.1.0 builds -- a caller
- *          compiled against the header without them passes its stream in the workspace slot. */
-#define DR_ABI_VERSION 202
+ *          compiled against the header without them passes its stream in the workspace slot.
+ *   0.3.0  training of the 2D-3D model: the vision3d TransformerLayer's training forward / backward (dr_fusion_layer_*, the new struct
+ *          dr_fusion_layer_grads), the row L2 normalisation and the weighted circle loss with their backwards (dr_l2_normalize_*,
+ *          dr_circle_loss_*, the new struct dr_circle_loss_params). */
+#define DR_ABI_VERSION 300
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
 const char* dr_last_hip_error(void);  /* text of the last failing HIP call on this thread */
@@ -689,6 +692,57 @@ int dr_denoise_loop_2d3d(const dr_loop2d3d_config* cfg, const dr_fusion_weights*
                          const uint8_t* tgt_mask, const uint8_t* tgt_mask_da, const float* x_T, double* conf,
                          double* x_final, int64_t* matches, int32_t* match_count, float* img_out, float* pcd_out,
                          const dr_loop_trace* trace, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The same vision3d TransformerLayer for TRAINING (the 2D-3D training branch, EXP/model.py:386-392 and :615-621; the layer is
+ * vision3d/layers/transformer.py:58-301: biased q / k / v, attention, linear, LayerNorm(x + .), expand, ReLU, squeeze, LayerNorm(z + .)): the forward
+ * that keeps what its backward needs, and the whole backward, one call each, as dr_attention_layer_train_forward_f32 / dr_attention_layer_backward_f32
+ * do for the 3D layer.  x [B*L, C] (queries), y [B*S, C] (keys / values; y == x for a self-attention call) contiguous; y_mask uint8 [B*S] or NULL:
+ * 1 = a valid key (the reference's k_masks is the complement: True = ignored).  C % H == 0, (C / H) % 4 == 0, C / H <= 160, C <= 1024.
+ *   forward : out [B*L, C]; `saved` = caller memory of dr_fusion_layer_train_saved_bytes(B, L, S, C): q | k | v | heads' output | LN1 input | z |
+ *             ReLU activation | LN2 input | (mean, rstd) of both LayerNorms -- opaque, handed to the backward
+ *   backward: grad_out [B*L, C] -> grad_x [B*L, C], grad_y [B*S, C] (separate buffers also when x == y: the caller adds them) and the 16 parameter
+ *             gradients (dr_fusion_layer_grads: the layout of dr_fusion_layer_weights; overwritten, not accumulated).  Every sum in a fixed order
+ *             (bias / LayerNorm gradients: column partials per block of 16 rows, added in block order; no atomics): bit-reproducible between
+ *             launches.  workspace: dr_fusion_layer_backward_workspace_bytes(B, H, L, S, C). */
+typedef struct {
+    float *q_w, *q_b, *k_w, *k_b, *v_w, *v_b;
+    float *lin_w, *lin_b, *norm1_w, *norm1_b;
+    float *expand_w, *expand_b, *squeeze_w, *squeeze_b, *norm2_w, *norm2_b;
+} dr_fusion_layer_grads;
+size_t dr_fusion_layer_train_saved_bytes(int B, int L, int S, int C);
+int dr_fusion_layer_train_forward_f32(const dr_fusion_layer_weights* w, int C, int H, int B, int L, int S, const float* x, const float* y,
+                                      const uint8_t* y_mask, float* out, void* saved, size_t saved_bytes, void* stream);
+size_t dr_fusion_layer_backward_workspace_bytes(int B, int H, int L, int S, int C);
+int dr_fusion_layer_backward_f32(const dr_fusion_layer_weights* w, int C, int H, int B, int L, int S, const float* x, const float* y,
+                                 const uint8_t* y_mask, const void* saved, const float* grad_out, float* grad_x, float* grad_y,
+                                 const dr_fusion_layer_grads* grads, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The coarse loss of the 2D-3D training branch (EXP/loss.py:30-75, CoarseMatchingLoss; its circle terms):
+ * dr_l2_normalize_f32: F.normalize(x, p = 2, dim = 1, eps) on rows [rows, C] (EXP/model.py:552-553, 630-631); norms [rows] = |x| per row, kept for
+ *   dr_l2_normalize_backward_f32 (grad_x = (g - y (g . y)) / |x| where |x| >= eps, g / eps below).
+ * dr_circle_loss_f32: the weighted circle loss (vision3d/loss/circle_loss.py:11-52) of feat_dists = sqrt(clamp(2 - 2 img pcd^T, 0) + 1e-8)
+ *   (vision3d/ops/pairwise_distance.py:38-56): img [M, C] (rows) and pcd [N, C] (columns), both already normalised; the node correspondences as
+ *   K duplicate-free entries (img_idx, pcd_idx int64, min_overlaps, max_overlaps float; entries outside the matrix are skipped -- the reference
+ *   raises); positives where the min overlap > pos_overlap with scale sqrt(min overlap), negatives where the max overlap < neg_overlap (0 off the
+ *   list).  CoarseMatchingLoss reads its max overlaps from the MIN list (EXP/loss.py:36): its caller passes that list twice.  *loss (device
+ *   float): an empty anchor set gives NaN, as the reference's mean of an empty selection.  Row / column log-sum-exps and the means in double,
+ *   each in one fixed order.  workspace: dr_circle_loss_workspace_bytes(M, N, C).
+ * dr_circle_loss_backward_f32: grad_img [M, C], grad_pcd [N, C] = d loss / d features, scaled by *grad_loss (device float; NULL = 1); the weights
+ *   are constants (the reference detaches them); zero where the clamp is active (2 - 2 x y < 0); an empty anchor set contributes no gradient, as
+ *   torch's.  It recomputes the forward (loss: optional device float). */
+typedef struct {
+    float pos_margin, neg_margin, pos_optimal, neg_optimal, log_scale;   /* cfg.loss.coarse_loss.* */
+    float pos_overlap, neg_overlap;                                      /* positive_overlap, negative_overlap */
+} dr_circle_loss_params;
+int dr_l2_normalize_f32(int rows, int C, const float* x, float eps, float* y, float* norms, void* stream);
+int dr_l2_normalize_backward_f32(int rows, int C, const float* y, const float* norms, float eps, const float* grad_y, float* grad_x, void* stream);
+size_t dr_circle_loss_workspace_bytes(int M, int N, int C);
+int dr_circle_loss_f32(int M, int N, int C, const float* img, const float* pcd, int K, const int64_t* img_idx, const int64_t* pcd_idx,
+                       const float* min_overlaps, const float* max_overlaps, const dr_circle_loss_params* params, float* loss, void* workspace,
+                       size_t workspace_bytes, void* stream);
+int dr_circle_loss_backward_f32(int M, int N, int C, const float* img, const float* pcd, int K, const int64_t* img_idx, const int64_t* pcd_idx,
+                                const float* min_overlaps, const float* max_overlaps, const dr_circle_loss_params* params, const float* grad_loss,
+                                float* loss, float* grad_img, float* grad_pcd, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Forward half of the training branch: the pieces of Pipeline.forward's
