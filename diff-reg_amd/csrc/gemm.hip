@@ -374,19 +374,15 @@ static int launch_direct(const GemmBatch& g, hipStream_t st) {
 
 //                 TM TN WM WN WK BKC
 #define CFG_SMALL  1, 1, 1, 1, 4, 128    /*  32 x  32 tile, k split over the 4 waves, deep chunks (latency-bound sizes) */
-#define CFG_MEDIUM 1, 1, 2, 2, 1, 64     /*  64 x  64 tile                                                            */
-#define CFG_LARGE  2, 1, 2, 2, 1, 32     /* 128 x  64 tile, 64 x 32 per wave                                          */
 #define CFG_M1B    1, 1, 2, 2, 1, 32, 1  /*  64 x  64 tile, single LDS buffer: 18 KB -> 8 workgroups per CU            */
 
 int gemm_configure() {
     int rc = configure_cfg<CFG_SMALL>();
-    if (rc == DR_OK) rc = configure_cfg<CFG_MEDIUM>();
-    if (rc == DR_OK) rc = configure_cfg<CFG_LARGE>();
     if (rc == DR_OK) rc = configure_cfg<CFG_M1B>();
     return rc;
 }
 
-static int g_force_cfg = -1;   // tools / tests: force a configuration (0, 1, 2, 9: LDS-staged f32-MFMA tiles; 11, 12: latency form)
+static int g_force_cfg = -1;   // tools / tests: force a configuration (0, 9: LDS-staged f32-MFMA tiles; 11, 12: latency form)
 void gemm_force_config(int c) { g_force_cfg = c; }
 
 int launch_gemm(const GemmBatch& g, hipStream_t st) {
@@ -423,11 +419,10 @@ int launch_gemm(const GemmBatch& g, hipStream_t st) {
     const int env_cfg = env_knob("DR_GEMM_CFG", -1);   // tools/: tile experiments
     if (env_cfg >= 0 && cfg == 9) cfg = env_cfg;
     if (g_force_cfg >= 0) cfg = g_force_cfg;
-    if (cfg == 11) return launch_direct<8, 7>(g, st);
-    if (cfg == 12) return launch_direct<16, 7>(g, st);
+    // a forced latency form holds only 8 NW MAXG k of a row in registers: beyond that it would drop terms, so it is refused
+    if (cfg == 11) return maxK <= 8 * 8 * 7 ? launch_direct<8, 7>(g, st) : DR_ENOSUP;
+    if (cfg == 12) return maxK <= 16 * 8 * 7 ? launch_direct<16, 7>(g, st) : DR_ENOSUP;
     if (cfg == 9) return launch_cfg<CFG_M1B>(g, st);
-    if (cfg == 2) return launch_cfg<CFG_LARGE>(g, st);
-    if (cfg == 1) return launch_cfg<CFG_MEDIUM>(g, st);
     if (cfg == 0) return launch_cfg<CFG_SMALL>(g, st);
     return DR_EINVAL;
 }

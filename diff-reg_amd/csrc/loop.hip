@@ -691,9 +691,31 @@ int dr_init(void) {
     return rc;
 }
 
-/* diagnostics for tools/: force the GEMM tile configuration (-1 auto, 0 small, 1 medium, 2 large) */
+/* diagnostics for tools/ and tests: force the GEMM tile configuration (-1 auto, 0, 9, 11, 12), run the internal problem form */
 void dr_debug_enable_env(int on) { enable_env_knobs(on != 0); }
 void dr_debug_gemm_config(int c) { gemm_force_config(c); }
+
+int dr_debug_gemm_f32(const dr_debug_gemm_problem* problems, int n, void* stream) {
+    if (!problems || n < 1 || n > 4) return DR_EINVAL;
+    GemmBatch g;
+    memset(&g, 0, sizeof(g));
+    for (int i = 0; i < n; ++i) {
+        const dr_debug_gemm_problem& q = problems[i];
+        const int K1 = q.A2 ? q.K1 : q.K;
+        if (q.rows < 0 || q.ncols <= 0 || q.K <= 0 || !q.A || !q.W || !q.out || q.nbatch < 0) return DR_EINVAL;
+        if (q.lda < K1 || q.ldo < q.ncols || (q.A2 && (K1 <= 0 || K1 >= q.K || q.lda2 < q.K - K1))) return DR_EINVAL;
+        if ((q.epilogue & ~(EPI_RELU | EPI_ROTARY)) ||
+            ((q.epilogue & EPI_ROTARY) && (!q.cos_t || !q.sin_t || q.rot_C <= 0 || (q.rot_C & 1))))
+            return DR_EINVAL;
+        GemmProblem& p = g.p[i];
+        p.A = q.A; p.A2 = q.A2; p.W = q.W; p.out = q.out; p.cosT = q.cos_t; p.sinT = q.sin_t; p.bias = q.bias; p.addend = q.addend;
+        p.rows = q.rows; p.ncols = q.ncols; p.K = q.K; p.K1 = K1; p.lda = q.lda; p.lda2 = q.A2 ? q.lda2 : 0; p.ldo = q.ldo;
+        p.epi = q.epilogue; p.rot_C = q.rot_C; p.scale = q.scale;
+        p.nbatch = q.nbatch; p.sA = q.stride_a; p.sW = q.stride_w; p.sO = q.stride_o;
+    }
+    g.n = n;
+    return launch_gemm(g, (hipStream_t)stream);
+}
 void dr_debug_attention_config(int flash_min_workgroups) { attention_force_flash_min(flash_min_workgroups); }
 void dr_debug_attention_split(int on) { attention_force_split(on); }
 

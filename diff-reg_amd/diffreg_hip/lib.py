@@ -96,6 +96,13 @@ class LoopTrace(ctypes.Structure):
                 ("topk_idx", c_void_p), ("wconf", c_void_p)]
 
 
+class DebugGemmProblem(ctypes.Structure):
+    """dr_debug_gemm_problem (include/diffreg_hip_debug.h): one problem of the f32-input GEMM in its internal form"""
+    _fields_ = [(n, c_void_p) for n in ("A", "A2", "W", "out", "cos_t", "sin_t", "bias", "addend")] + \
+               [(n, c_int) for n in ("rows", "ncols", "K", "K1", "lda", "lda2", "ldo", "epilogue", "rot_C")] + \
+               [("scale", c_float), ("nbatch", c_int)] + [(n, ctypes.c_longlong) for n in ("stride_a", "stride_w", "stride_o")]
+
+
 _P = ctypes.POINTER
 SIGNATURES.update({
     "dr_init": (c_int, []),
@@ -160,6 +167,7 @@ SIGNATURES.update({
     "dr_debug_enable_env": (None, [c_int]),
     "dr_debug_launch_chain": (c_int, [c_int, c_int, c_int, c_void_p]),
     "dr_debug_gemm_config": (None, [c_int]),
+    "dr_debug_gemm_f32": (c_int, [_P(DebugGemmProblem), c_int, c_void_p]),
     "dr_debug_attention_config": (None, [c_int]),
     "dr_debug_attention_split": (None, [c_int]),
     "dr_pnp_ransac_workspace_bytes": (c_size_t, [c_int, c_int]),
@@ -789,6 +797,31 @@ def linear_ex(x, W, bias=None, epilogue=0, scale=1.0, K=None):
     check(_lib.dr_linear_ex_f32(x.shape[0], W.shape[0], K, ptr(x), x.stride(0), ptr(W), ptr(bias), ptr(out), out.stride(0), epilogue,
                                 float(scale), stream_of(x)))
     return out
+
+
+def gemm_problem(A, W, out, rows, ncols, K, lda, ldo, A2=None, K1=0, lda2=0, bias=None, addend=None, epilogue=0, cos=None, sin=None,
+                 rot_C=0, scale=1.0, nbatch=0, stride_a=0, stride_w=0, stride_o=0):
+    """-> DebugGemmProblem for debug_gemm.  Tensors are passed by their data pointer, so views with an offset (a column offset of `out`, a
+    row window of A) address exactly what they show; the caller keeps every tensor alive and sizes it for rows / lda / ldo / strides."""
+    def dp(t):
+        if t is None:
+            return None
+        if not t.is_cuda:
+            raise RuntimeError("libdiffreg_hip ops need tensors on a ROCm device (got %s); there is no CPU path" % t.device)
+        return t.data_ptr()
+    return DebugGemmProblem(dp(A), dp(A2), dp(W), dp(out), dp(cos), dp(sin), dp(bias), dp(addend), rows, ncols, K, K1, lda, lda2, ldo,
+                            epilogue, rot_C, float(scale), nbatch, stride_a, stride_w, stride_o)
+
+
+def debug_gemm(problems, stream_tensor, checked=True):
+    """one grouped launch of 1..4 problems (gemm_problem) through dr_debug_gemm_f32 on the current stream of stream_tensor's device;
+    checked=False returns the status code instead of raising"""
+    ensure_init()
+    arr = (DebugGemmProblem * len(problems))(*problems)
+    rc = _lib.dr_debug_gemm_f32(arr, len(problems), stream_of(stream_tensor))
+    if checked:
+        check(rc)
+    return rc
 
 
 KP_INFLUENCE = {"constant": 0, "linear": 1, "gaussian": 2}

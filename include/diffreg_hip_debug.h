@@ -16,9 +16,36 @@ extern "C" {
 #endif
 
 void dr_debug_enable_env(int on);
-/* force the f32-input GEMM configuration: -1 auto, 0 / 1 / 2 / 9 LDS-staged 32 x 32 / 64 x 64 / 128 x 64 / 64 x 64 single-buffer
- * tiles, 11 / 12 the latency form with 8 / 16 waves */
+/* force the f32-input GEMM configuration: -1 auto, 0 / 9 LDS-staged 32 x 32 / 64 x 64 single-buffer tiles, 11 / 12 the latency
+ * form with 8 / 16 waves (K <= 448 / 896: a launch beyond that returns DR_ENOSUP); any other value makes every launch DR_EINVAL */
 void dr_debug_gemm_config(int c);
+/* one grouped launch of the f32-input GEMM in its internal problem form (what the ABI's dr_linear_f32 / dr_linear_ex_f32 /
+ * dr_gemm_nt_batched_f32 cannot express: a two-segment A, an addend, bias with rotary, a column offset of `out`, 2..4 different problems in one
+ * grid), for the per-geometry tests.  Problem i:
+ *   acc[r][c] = sum_{k < K1} A[r lda + k] W[c K + k] + sum_{K1 <= k < K} A2[r lda2 + k - K1] W[c K + k]    (A2 == NULL: K1 is ignored)
+ *   out[r ldo + c] = scale * relu(rot(acc)[r][c] + bias[c]) + addend[r ldo + c]    for r < rows, c < ncols
+ * rot (epilogue & 2): with h = c % rot_C / 2, rot(acc)[r][2j] = acc[r][2j] cos_t[r rot_C/2 + h] - acc[r][2j+1] sin_t[..], rot(acc)[r][2j+1] =
+ * acc[r][2j+1] cos_t[..] + acc[r][2j] sin_t[..]; relu (epilogue & 1); bias / addend NULL: none.  nbatch > 1: instance z reads A + z stride_a,
+ * W + z stride_w and writes out + z stride_o (floats); A2, bias, addend and the rotary tables are shared by all instances.
+ * K, K1, lda, lda2 multiples of 4 and A, A2, W 16-byte aligned (else DR_ENOSUP, as inside the library).  The geometry is the automatic one
+ * or the one dr_debug_gemm_config forced; n outside 1..4 or a malformed problem -> DR_EINVAL. */
+typedef struct dr_debug_gemm_problem {
+    const float* A;
+    const float* A2;
+    const float* W;
+    float* out;
+    const float* cos_t;
+    const float* sin_t;
+    const float* bias;
+    const float* addend;
+    int rows, ncols, K, K1, lda, lda2, ldo;
+    int epilogue;
+    int rot_C;
+    float scale;
+    int nbatch;
+    long long stride_a, stride_w, stride_o;
+} dr_debug_gemm_problem;
+int dr_debug_gemm_f32(const dr_debug_gemm_problem* problems, int n, void* stream);
 /* attention: use the 128-query (flash) kernel from this many workgroups on; -1 = default rule (256) */
 void dr_debug_attention_config(int flash_min_workgroups);
 /* flash attention arithmetic: 1 = split-operand bf16 MFMA products (default), 0 = f32-input MFMA, -1 = default */
