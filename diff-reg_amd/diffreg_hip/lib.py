@@ -177,6 +177,17 @@ SIGNATURES.update({
     "dr_unique_pairs_workspace_bytes": (c_size_t, [c_int]),
     "dr_unique_pairs_i64": (c_int, [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
     "dr_corr_gather_f32": (c_int, [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_int] + [c_void_p] * 14),
+    # ABI 0.4.0: patch partition and ground-truth overlaps of the 2D-3D model (csrc/partition2d3d.hip; wrappers in diffreg_hip/partition2d3d.py)
+    "dr_point_to_node_partition_workspace_bytes": (c_size_t, [c_int]),
+    "dr_point_to_node_partition_f32": (c_int, [c_int, c_int, c_int] + [c_void_p] * 9 + [c_size_t, c_void_p]),
+    "dr_patchify_f32": (c_int, [c_int] * 5 + [c_void_p] * 14),
+    "dr_node_correspondences_2d3d_workspace_bytes": (c_size_t, [c_int, c_int, c_int, ctypes.c_longlong]),
+    "dr_node_correspondences_2d3d_f32": (c_int, [c_int] * 4 + [c_void_p] * 11 + [c_float, c_float, ctypes.c_longlong] + [c_void_p] * 9 + [c_size_t, c_void_p]),
+    "dr_mutual_nn_radius_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dr_mutual_nn_radius_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dr_radius_pairs_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dr_radius_pairs_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
+                                    c_void_p]),
     "dr_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dr_match_matrix_f32": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dr_gt_noising_f64": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p]),
@@ -256,7 +267,7 @@ def _bind(table):
 _bind(SIGNATURES)
 _INIT_DONE = False
 
-ABI_VERSION = 300          # DR_ABI_VERSION of the include/diffreg_hip.h these signatures were written against
+ABI_VERSION = 400          # DR_ABI_VERSION of the include/diffreg_hip.h these signatures were written against
 if _lib.dr_version() // 100 != ABI_VERSION // 100:
     raise ImportError("libdiffreg_hip.so is ABI %d, this binding is written against %d: rebuild (make -C diff-reg_amd/csrc)"
                       % (_lib.dr_version(), ABI_VERSION))

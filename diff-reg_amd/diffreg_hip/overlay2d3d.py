@@ -24,8 +24,17 @@ libdiffreg_hip, gradients into the modules' own parameters and back to the backb
     accelerate(model, training=True);  accelerate_loss(loss_fn)          # EXP/trainval.py, after create_model / OverallLoss(cfg)
 
 accelerate_loss re-binds CoarseMatchingLoss.forward (EXP/loss.py:30-75; an OverallLoss instance: its c_loss) to the device circle + focal loss.
-The GT search, q_sample, the warp, the backbones and the fine loss stay the reference's code.
+The GT search, q_sample, the warp, the backbones and the fine loss stay the reference's code -- unless the overlay is installed with
+`partition=True`: then the patch partition and the ground-truth patch overlaps between the backbones and the coarse matching
+(EXP/model.py:395-540: point_to_node_partition, patchify, get_2d3d_node_correspondences) run on the device (diffreg_hip/partition2d3d.py), and
+with `training=True` also the GT search of the training branch (model.py:569: get_correspondences; to_o3d_pcd becomes the identity).  These are
+module-level names that forward() calls inline, so they are re-bound in the globals of the module that defines the model's class; `remove()`
+restores them.  Without the flag no global is touched.
+
+    accelerate(model, partition=True)                                   # eval
+    accelerate(model, training=True, partition=True)                    # training
 """
+import sys
 import types
 
 import torch
@@ -35,9 +44,11 @@ from .engine import DenoiseEngine2D3D
 
 
 class LoopOverlay2D3D:
-    def __init__(self, model, n_head=4, engine_kwargs=None, training=False):
+    def __init__(self, model, n_head=4, engine_kwargs=None, training=False, partition=False):
         self.model = model
         self.training = bool(training)
+        self.partition = bool(partition)
+        self._globals_saved = {}
         self.n_head = n_head
         self.engine_kwargs = dict(engine_kwargs or {})
         self.engine = None
@@ -53,7 +64,22 @@ class LoopOverlay2D3D:
             self._orig.update(coarse_transformer=model.transformer.forward, coarse_matching=model.coarse_matching.forward)
             model.transformer.forward = self._coarse_transformer
             model.coarse_matching.forward = self._coarse_matching
+        if self.partition:
+            self._bind_partition()
         model._dr_overlay = self
+
+    _MISSING = object()
+
+    def _bind_partition(self):
+        """re-bind the module-level functions of EXP/model.py:395-540 (and, with training, :569) in the globals of the model's defining module"""
+        from . import partition2d3d as p
+        names = ["point_to_node_partition", "patchify", "get_2d3d_node_correspondences"]
+        if self.training:
+            names += ["get_correspondences", "to_o3d_pcd"]
+        g = vars(sys.modules[type(self.model).__module__])
+        for name in names:
+            self._globals_saved[name] = g.get(name, self._MISSING)
+            g[name] = getattr(p, name)
 
     def remove(self):
         """restore the three call sites"""
@@ -64,6 +90,14 @@ class LoopOverlay2D3D:
         for obj, name in sites:
             if name in obj.__dict__:
                 del obj.__dict__[name]
+        if self._globals_saved:
+            g = vars(sys.modules[type(m).__module__])
+            for name, old in self._globals_saved.items():
+                if old is self._MISSING:
+                    g.pop(name, None)
+                else:
+                    g[name] = old
+            self._globals_saved = {}
         m.__dict__.pop("_dr_overlay", None)
 
     def refresh(self):
@@ -148,10 +182,11 @@ class LoopOverlay2D3D:
         return self._orig["coarse_matching"](src_feats, tgt_feats, src_mask, tgt_mask, *args, **kwargs)
 
 
-def accelerate(model, n_head=4, training=False, **engine_kwargs):
+def accelerate(model, n_head=4, training=False, partition=False, **engine_kwargs):
     """install the overlay on a MATR2D3D instance (see the module docstring); returns the LoopOverlay2D3D (`.remove()` undoes it).
-    training=True: the training branch's four coarse modules run on the device under model.train() as well."""
-    return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs, training=training)
+    training=True: the training branch's four coarse modules run on the device under model.train() as well.
+    partition=True: the patch partition and GT patch overlaps (and, with training, the GT search) run on the device as well."""
+    return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs, training=training, partition=partition)
 
 
 def accelerate_loss(loss_module):

@@ -38,8 +38,10 @@ extern "C" {
  *          compiled against the header without them passes its stream in the workspace slot.
  *   0.3.0  training of the 2D-3D model: the vision3d TransformerLayer's training forward / backward (dr_fusion_layer_*, the new struct
  *          dr_fusion_layer_grads), the row L2 normalisation and the weighted circle loss with their backwards (dr_l2_normalize_*,
- *          dr_circle_loss_*, the new struct dr_circle_loss_params). */
-#define DR_ABI_VERSION 300
+ *          dr_circle_loss_*, the new struct dr_circle_loss_params).
+ *   0.4.0  the 2D-3D patch partition and ground-truth overlaps: dr_point_to_node_partition_f32, dr_patchify_f32,
+ *          dr_node_correspondences_2d3d_f32, dr_mutual_nn_radius_f32, dr_radius_pairs_f32 (new entries only; nothing older changed). */
+#define DR_ABI_VERSION 400
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
 const char* dr_last_hip_error(void);  /* text of the last failing HIP call on this thread */
@@ -618,6 +620,62 @@ int dr_corr_gather_f32(int capacity, const int32_t* count, const int64_t* unique
                        const float* img_pixels_f, const float* pcd_points_f, const float* pcd_pixels_f, const float* img_feats_f, const float* pcd_feats_f,
                        int64_t* img_corr_indices, int64_t* pcd_corr_indices, float* img_corr_points, float* img_corr_pixels, float* pcd_corr_points,
                        float* pcd_corr_pixels, float* corr_scores, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 0.4.0: the patch partition and the ground-truth patch overlaps of the 2D-3D model (EXP/model.py:395-540, between the backbones and the
+ * coarse matching, every pair in eval and in training) and the training-only ground-truth search (model.py:565-600).  csrc/partition2d3d.hip.
+ * Nothing synchronises.  Bool tensors are uint8 (0 / 1).  Every list is written in the reference's order by a sort or a count / scan / write
+ * compaction; distances are sums of squared differences in float32 (the reference's x^2 + y^2 - 2xy form differs from it in the last bits:
+ * the tests compare wherever a float64 restatement decides the comparison).
+ *
+ * dr_point_to_node_partition_f32: point_to_node_partition(points, nodes, point_limit, return_count=True, gather_points=True)
+ *   (vision3d/ops/point_cloud_partition.py:41-104).  points [Nf,3], nodes [Nc,3]; point_to_node [Nf]: the nearest node (equal distances: the
+ *   lower index); node_sizes [Nc]; node_masks [Nc] = size > 0; node_knn_indices [Nc, point_limit]: the node's own points nearest first (equal
+ *   distances: lower index first), padded with Nf, node_knn_masks = not padding.  max_points_per_node (device int32) = the largest node size:
+ *   the reference's output is min(that, point_limit) columns wide, the caller slices.  point_limit <= 128 (DR_ENOSUP beyond).  The (Nc x Nf)
+ *   distance matrix is never formed: nearest-node pass, one (node, distance, index) sort, one wave per node.
+ *   workspace: dr_point_to_node_partition_workspace_bytes(Nf).
+ * dr_patchify_f32: patchify (EXP/utils.py:28-56) for an (H_f x W_f) image cut into (H_c x W_c) blocks, every stride-th row / column of a
+ *   block: Ki = ceil(H_f / H_c / stride) * ceil(W_f / W_c / stride).  img_points, img_points_da [H_f W_f, 3], img_pixels [H_f W_f, 2],
+ *   img_masks, img_masks_da [H_f W_f] -> knn_points, knn_points_da [M, Ki, 3], knn_pixels [M, Ki, 2], knn_indices int64 [M, Ki], knn_masks,
+ *   knn_masks_da [M, Ki], node_masks, node_masks_da [M] = any over the block (M = H_c W_c).  One launch.
+ * dr_node_correspondences_2d3d_f32: get_2d3d_node_correspondences (EXP/utils.py:59-175) without its mutual-NN list (the next entry): the point
+ *   patches moved by transform (16 floats, device, row-major 4 x 4; apply_transform, vision3d/ops/se3.py:46-53), the three masked means (eps
+ *   1e-6, vision3d/ops/masked_ops.py:23-41) -> pcd_centers [N,3], img_centers, img_centers_da [M,3]; enclosing radii and the candidate test
+ *   over (M x N) (:107-117), candidates compacted in row-major order; per candidate both nearest-neighbour passes over the whole other patch
+ *   (k = 1; vision3d/ops/knn.py:10-27), the 3D radius, the 2D radius and the mask tests, the two overlap ratios (:130-163); the pairs with both
+ *   ratios > 0 in candidate order (:165-171) -> img_corr_indices, pcd_corr_indices int64, img_corr_overlaps, pcd_corr_overlaps, each of
+ *   `capacity` rows.  counts int32 [3]: [0] = pairs written, [1] = candidates kept, [2] = candidates found: [2] > capacity means that the
+ *   candidate list was cut at `capacity` and the result must not be used (never a silent truncation: the caller reads counts).
+ *   Ki <= 256, Kc <= 128 (DR_ENOSUP beyond).  workspace: dr_node_correspondences_2d3d_workspace_bytes(M, N, Kc, capacity).
+ * dr_mutual_nn_radius_f32: multual_nn_correspondence(src, tgt, search_radius, knn = 1) (EXP/utils.py:234-252): the sources whose nearest
+ *   target has them as its nearest source and lies closer than radius, ascending: out_src, out_tgt int64 [ns], count (device int32).
+ *   workspace: dr_mutual_nn_radius_workspace_bytes(ns, nt).
+ * dr_radius_pairs_f32: all (i, j) with |T src_i - tgt_j| < radius in ascending (i, j) order: what get_correspondences / KDTree_corr compute
+ *   (EXP/utils.py:426-446; there per query in KD-tree order, which nothing downstream reads: model.py:574-577, 603-604 scatter ones).
+ *   transform: 16 floats on the device or NULL (identity).  counts int32 [2]: [0] = pairs written, [1] = pairs found (> capacity: cut).
+ *   PARITY UNPINNED against Open3D (not part of the reference tree), pinned against the definition in float64.
+ *   workspace: dr_radius_pairs_workspace_bytes(ns, nt). */
+size_t dr_point_to_node_partition_workspace_bytes(int Nf);
+int dr_point_to_node_partition_f32(int Nf, int Nc, int point_limit, const float* points, const float* nodes, int64_t* point_to_node, int64_t* node_sizes,
+                                   uint8_t* node_masks, int64_t* node_knn_indices, uint8_t* node_knn_masks, int32_t* max_points_per_node, void* workspace,
+                                   size_t workspace_bytes, void* stream);
+int dr_patchify_f32(int H_f, int W_f, int H_c, int W_c, int stride, const float* img_points, const float* img_points_da, const float* img_pixels,
+                    const uint8_t* img_masks, const uint8_t* img_masks_da, float* knn_points, float* knn_points_da, float* knn_pixels, int64_t* knn_indices,
+                    uint8_t* knn_masks, uint8_t* knn_masks_da, uint8_t* node_masks, uint8_t* node_masks_da, void* stream);
+size_t dr_node_correspondences_2d3d_workspace_bytes(int M, int N, int Kc, long long capacity);
+int dr_node_correspondences_2d3d_f32(int M, int Ki, int N, int Kc, const uint8_t* img_masks, const float* img_knn_points, const float* img_knn_points_da,
+                                     const float* img_knn_pixels, const uint8_t* img_knn_masks, const uint8_t* img_knn_masks_da, const uint8_t* pcd_masks,
+                                     const float* pcd_knn_points, const float* pcd_knn_pixels, const uint8_t* pcd_knn_masks, const float* transform,
+                                     float pos_radius_2d, float pos_radius_3d, long long capacity, int64_t* img_corr_indices, int64_t* pcd_corr_indices,
+                                     float* img_corr_overlaps, float* pcd_corr_overlaps, int32_t* counts, float* pcd_centers, float* img_centers,
+                                     float* img_centers_da, void* workspace, size_t workspace_bytes, void* stream);
+size_t dr_mutual_nn_radius_workspace_bytes(int ns, int nt);
+int dr_mutual_nn_radius_f32(int ns, int nt, const float* src, const float* tgt, float radius, int64_t* out_src, int64_t* out_tgt, int32_t* count,
+                            void* workspace, size_t workspace_bytes, void* stream);
+size_t dr_radius_pairs_workspace_bytes(int ns, int nt);
+int dr_radius_pairs_f32(int ns, int nt, const float* src, const float* tgt, const float* transform, float radius, long long capacity, int64_t* out_src,
+                        int64_t* out_tgt, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
 
 /* PnP-RANSAC registration of the fine correspondences (EXP/eval.py:174-182 -> vision3d/utils/opencv.py:10-63 = cv2.solvePnPRansac with
  * iterationsCount = 50000, reprojectionError = 8.0, flags = SOLVEPNP_P3P).  OpenCV is not part of the reference tree: the published algorithm of
