@@ -188,6 +188,18 @@ SIGNATURES.update({
     "dr_radius_pairs_workspace_bytes": (c_size_t, [c_int, c_int]),
     "dr_radius_pairs_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p, c_float, ctypes.c_longlong, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                     c_void_p]),
+    # ABI 0.5.0: the 2D-3D point backbone's GroupNorm, kNN interpolation and KPConv neighbour count (csrc/backbone2d3d.hip; diffreg_hip/pcd_backbone2d3d.py)
+    "dr_group_norm_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dr_group_norm_stats_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_float, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dr_group_norm_apply_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_int] + [c_void_p] * 4 + [c_void_p, c_int] + [c_void_p] * 4 +
+                                [c_float, c_int, c_void_p, c_int, c_void_p]),
+    "dr_group_norm_backward_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dr_group_norm_backward_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int] + [c_void_p] * 3 +
+                                   [c_void_p, c_int] + [c_void_p] * 3 + [c_float, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int,
+                                                                          c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dr_knn_interpolate_f32": (c_int, [c_int] * 4 + [c_void_p] * 5 + [c_int, c_void_p]),
+    "dr_knn_interpolate_backward_f32": (c_int, [c_int] * 4 + [c_void_p] * 4 + [c_int, c_void_p, c_void_p]),
+    "dr_kpconv_neighbor_count_f32": (c_int, [c_int] * 4 + [c_void_p] * 4),
     "dr_train_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dr_match_matrix_f32": (c_int, [c_int, c_int, c_int, c_int, c_void_p, c_void_p, c_void_p]),
     "dr_gt_noising_f64": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_double, c_double, c_void_p, c_void_p, c_void_p]),
@@ -267,7 +279,7 @@ def _bind(table):
 _bind(SIGNATURES)
 _INIT_DONE = False
 
-ABI_VERSION = 400          # DR_ABI_VERSION of the include/diffreg_hip.h these signatures were written against
+ABI_VERSION = 500          # DR_ABI_VERSION of the include/diffreg_hip.h these signatures were written against
 if _lib.dr_version() // 100 != ABI_VERSION // 100:
     raise ImportError("libdiffreg_hip.so is ABI %d, this binding is written against %d: rebuild (make -C diff-reg_amd/csrc)"
                       % (_lib.dr_version(), ABI_VERSION))
@@ -922,6 +934,91 @@ def gather_pool_backward(x, inds, grad_out, first_only=False):
     check(_lib.dr_gather_pool_backward_f32(n2, H, H, x.shape[1], ptr(x.contiguous()), x.shape[0], ptr(inds.contiguous()), 1 if first_only else 0,
                                            ptr(grad_out.contiguous()), ptr(gx), stream_of(x)))
     return gx
+
+
+def _at_col(t, col):
+    """device pointer of column `col` of a contiguous row-major [rows, width] tensor (a column slice addressed through its leading dimension)"""
+    if not t.is_cuda or not t.is_contiguous():
+        raise RuntimeError("libdiffreg_hip ops need contiguous ROCm tensors")
+    return c_void_p(t.data_ptr() + col * t.element_size())
+
+
+def group_norm_stats(x, G, eps=1e-5):
+    """(mean, rstd) [G] of nn.GroupNorm(G, C) over the rows of x [N, C] (dr_group_norm_stats_f32)"""
+    ensure_init()
+    N, C = x.shape
+    mean, rstd = torch.empty(G, device=x.device), torch.empty(G, device=x.device)
+    wsb = _lib.dr_group_norm_workspace_bytes(N, C)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=x.device)
+    check(_lib.dr_group_norm_stats_f32(N, C, G, ptr(x), x.stride(0), float(eps), ptr(mean), ptr(rstd), ptr(ws), wsb, stream_of(x)))
+    return mean, rstd
+
+
+def group_norm_apply(a, stats_a, gamma_a, beta_a, b=None, stats_b=None, gamma_b=None, beta_b=None, slope=None):
+    """act( GN(a) + [GN(b) | b | 0] ), act = LeakyReLU(slope) or none when slope is None (dr_group_norm_apply_f32)"""
+    ensure_init()
+    N, C = a.shape
+    G = stats_a[0].shape[0]
+    out = torch.empty(N, C, device=a.device)
+    mb, rb = stats_b if stats_b is not None else (None, None)
+    check(_lib.dr_group_norm_apply_f32(N, C, G, ptr(a), a.stride(0), ptr(stats_a[0]), ptr(stats_a[1]), ptr(gamma_a), ptr(beta_a), ptr(b),
+                                       b.stride(0) if b is not None else 0, ptr(mb), ptr(rb), ptr(gamma_b if mb is not None else None),
+                                       ptr(beta_b if mb is not None else None), float(slope or 0.0), 0 if slope is None else 1, ptr(out), C,
+                                       stream_of(a)))
+    return out
+
+
+def group_norm_backward(grad_out, out, a, stats_a, gamma_a, b=None, stats_b=None, gamma_b=None, slope=None):
+    """backward of group_norm_apply -> (grad_a, grad_b or None, d gamma_a, d beta_a, d gamma_b or None, d beta_b or None)"""
+    ensure_init()
+    N, C = a.shape
+    G = stats_a[0].shape[0]
+    g = grad_out.contiguous()
+    dev = a.device
+    ga = torch.empty(N, C, device=dev)
+    gb = torch.empty(N, C, device=dev) if b is not None else None
+    dga, dba = torch.empty(C, device=dev), torch.empty(C, device=dev)
+    mb, rb = stats_b if stats_b is not None else (None, None)
+    dgb, dbb = (torch.empty(C, device=dev), torch.empty(C, device=dev)) if mb is not None else (None, None)
+    wsb = _lib.dr_group_norm_backward_workspace_bytes(N, C, G)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    check(_lib.dr_group_norm_backward_f32(N, C, G, ptr(g), C, ptr(out), out.stride(0), ptr(a), a.stride(0), ptr(stats_a[0]), ptr(stats_a[1]), ptr(gamma_a),
+                                          ptr(b), b.stride(0) if b is not None else 0, ptr(mb), ptr(rb), ptr(gamma_b if mb is not None else None),
+                                          float(slope or 0.0), 0 if slope is None else 1, ptr(ga), C, ptr(dga), ptr(dba), ptr(gb), C, ptr(dgb), ptr(dbb),
+                                          ptr(ws), wsb, stream_of(a)))
+    return ga, gb, dga, dba, dgb, dbb
+
+
+def knn_interpolate(q_pts, s_pts, neighb_inds, x, out=None, col=0):
+    """knn_interpolate_pack_mode(q, s, x, inds) -> [Nq, C], or written into columns col .. col + C - 1 of `out` [Nq, width] (returned)"""
+    ensure_init()
+    Nq, H = neighb_inds.shape
+    C = x.shape[1]
+    if out is None:
+        out, col = torch.empty(Nq, C, device=x.device), 0
+    check(_lib.dr_knn_interpolate_f32(Nq, s_pts.shape[0], H, C, ptr(q_pts.contiguous()), ptr(s_pts.contiguous()), ptr(neighb_inds.contiguous()),
+                                      ptr(x.contiguous()), _at_col(out, col), out.shape[1], stream_of(x)))
+    return out
+
+
+def knn_interpolate_backward(q_pts, s_pts, neighb_inds, grad_out, C, col=0):
+    """d loss / d x [Ns, C] of knn_interpolate from columns col .. col + C - 1 of grad_out [Nq, width]"""
+    ensure_init()
+    Nq, H = neighb_inds.shape
+    g = grad_out.contiguous()
+    gx = torch.empty(s_pts.shape[0], C, device=g.device)
+    check(_lib.dr_knn_interpolate_backward_f32(Nq, s_pts.shape[0], H, C, ptr(q_pts.contiguous()), ptr(s_pts.contiguous()), ptr(neighb_inds.contiguous()),
+                                               _at_col(g, col), g.shape[1], ptr(gx), stream_of(g)))
+    return gx
+
+
+def kpconv_neighbor_count(neighb_inds, x, Ns):
+    """int32 [Nq]: KPConv's neighbours with a positive feature sum, as dr_kpconv_gather_f32 counts them"""
+    ensure_init()
+    Nq, H = neighb_inds.shape
+    counts = torch.empty(Nq, dtype=torch.int32, device=x.device)
+    check(_lib.dr_kpconv_neighbor_count_f32(Nq, Ns, H, x.shape[1], ptr(neighb_inds.contiguous()), ptr(x.contiguous()), ptr(counts), stream_of(x)))
+    return counts
 
 
 _LAYER_KEYS = ("q_proj.weight", "k_proj.weight", "v_proj.weight", "merge.weight", "mlp.0.weight", "mlp.2.weight",

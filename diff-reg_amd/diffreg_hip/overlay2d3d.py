@@ -33,21 +33,29 @@ restores them.  Without the flag no global is touched.
 
     accelerate(model, partition=True)                                   # eval
     accelerate(model, training=True, partition=True)                    # training
+
+With `backbone=True` the point backbone in front of all of it (`self.pcd_backbone(pcd_feats, data_dict)`, EXP/model.py:366-368) runs on the device
+too, in eval and in train mode (diffreg_hip/pcd_backbone2d3d.py: forward and backward in libdiffreg_hip, gradients into the module's own parameters):
+`pcd_backbone.forward` is re-bound on the instance and `remove()` restores it.  With training=True the gradients of the device fusion path flow into
+the device backbone.  The image backbone stays the reference's code.
+
+    accelerate(model, training=True, partition=True, backbone=True)
 """
 import sys
 import types
 
 import torch
 
-from . import autograd2d3d
+from . import autograd2d3d, pcd_backbone2d3d
 from .engine import DenoiseEngine2D3D
 
 
 class LoopOverlay2D3D:
-    def __init__(self, model, n_head=4, engine_kwargs=None, training=False, partition=False):
+    def __init__(self, model, n_head=4, engine_kwargs=None, training=False, partition=False, backbone=False):
         self.model = model
         self.training = bool(training)
         self.partition = bool(partition)
+        self.backbone = bool(backbone)
         self._globals_saved = {}
         self.n_head = n_head
         self.engine_kwargs = dict(engine_kwargs or {})
@@ -66,6 +74,9 @@ class LoopOverlay2D3D:
             model.coarse_matching.forward = self._coarse_matching
         if self.partition:
             self._bind_partition()
+        if self.backbone:
+            pb = model.pcd_backbone
+            pb.forward = lambda feats, data_dict: pcd_backbone2d3d.point_backbone(pb, feats, data_dict)
         model._dr_overlay = self
 
     _MISSING = object()
@@ -87,6 +98,8 @@ class LoopOverlay2D3D:
         sites = [(m, "get_warped_from_noising_matching3D3D"), (m.denoising_transformer, "forward"), (m.denoising_coarse_matching, "forward")]
         if self.training:
             sites += [(m.transformer, "forward"), (m.coarse_matching, "forward")]
+        if self.backbone:
+            sites += [(m.pcd_backbone, "forward")]
         for obj, name in sites:
             if name in obj.__dict__:
                 del obj.__dict__[name]
@@ -182,11 +195,12 @@ class LoopOverlay2D3D:
         return self._orig["coarse_matching"](src_feats, tgt_feats, src_mask, tgt_mask, *args, **kwargs)
 
 
-def accelerate(model, n_head=4, training=False, partition=False, **engine_kwargs):
+def accelerate(model, n_head=4, training=False, partition=False, backbone=False, **engine_kwargs):
     """install the overlay on a MATR2D3D instance (see the module docstring); returns the LoopOverlay2D3D (`.remove()` undoes it).
     training=True: the training branch's four coarse modules run on the device under model.train() as well.
-    partition=True: the patch partition and GT patch overlaps (and, with training, the GT search) run on the device as well."""
-    return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs, training=training, partition=partition)
+    partition=True: the patch partition and GT patch overlaps (and, with training, the GT search) run on the device as well.
+    backbone=True: the point backbone (model.pcd_backbone) runs on the device, in eval and train mode."""
+    return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs, training=training, partition=partition, backbone=backbone)
 
 
 def accelerate_loss(loss_module):

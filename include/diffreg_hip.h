@@ -40,8 +40,10 @@ extern "C" {
  *          dr_fusion_layer_grads), the row L2 normalisation and the weighted circle loss with their backwards (dr_l2_normalize_*,
  *          dr_circle_loss_*, the new struct dr_circle_loss_params).
  *   0.4.0  the 2D-3D patch partition and ground-truth overlaps: dr_point_to_node_partition_f32, dr_patchify_f32,
- *          dr_node_correspondences_2d3d_f32, dr_mutual_nn_radius_f32, dr_radius_pairs_f32 (new entries only; nothing older changed). */
-#define DR_ABI_VERSION 400
+ *          dr_node_correspondences_2d3d_f32, dr_mutual_nn_radius_f32, dr_radius_pairs_f32 (new entries only; nothing older changed).
+ *   0.5.0  the 2D-3D point backbone: dr_group_norm_stats_f32, dr_group_norm_apply_f32, dr_group_norm_backward_f32, dr_knn_interpolate_f32,
+ *          dr_knn_interpolate_backward_f32, dr_kpconv_neighbor_count_f32 and their workspace sizes (new entries only; nothing older changed). */
+#define DR_ABI_VERSION 500
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
 const char* dr_last_hip_error(void);  /* text of the last failing HIP call on this thread */
@@ -676,6 +678,45 @@ int dr_mutual_nn_radius_f32(int ns, int nt, const float* src, const float* tgt, 
 size_t dr_radius_pairs_workspace_bytes(int ns, int nt);
 int dr_radius_pairs_f32(int ns, int nt, const float* src, const float* tgt, const float* transform, float radius, long long capacity, int64_t* out_src,
                         int64_t* out_tgt, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 0.5.0: the 2D-3D model's point backbone (PointBackbone, EXP/point_backbone.py:8-95, called at EXP/model.py:366-368; vision3d's KPConv FPN).
+ * csrc/backbone2d3d.hip.  KPConv's gather half is dr_kpconv_gather_f32 / its backward, its product dr_linear_ex_f32 with the bias in the epilogue,
+ * the strided max-pool dr_gather_pool_f32 / its backward; these entries add what the KPFCN backbone does not have.  Nothing synchronises, nothing
+ * allocates.  Rows are [N, C] float32 with leading dimensions.
+ *
+ * dr_group_norm_stats_f32: GroupNormPackMode = nn.GroupNorm(G, C, eps, affine) over the transposed [1, C, N] rows (vision3d/layers/basic_layers/
+ *   norm.py:53-65): mean / rstd [G] over all N rows x C/G channels, biased variance, float64 partials over a fixed grid of row slabs (no atomics).
+ *   C % G == 0.  workspace: dr_group_norm_workspace_bytes(N, C).
+ * dr_group_norm_apply_f32: out = act( gamma_a xhat_a + beta_a + [ gamma_b xhat_b + beta_b  |  b  |  0 ] ), act = LeakyReLU(leaky_slope) or none:
+ *   UnaryBlockPackMode's Linear -> GroupNorm -> LeakyReLU (vision3d/layers/unary_block.py:26-30), KPConvBlock's (kpconv.py:203-207) and the tail of
+ *   KPResidualBlock (kpconv.py:266-280: the shortcut through its own Linear + GroupNorm when mean_b is given, the identity shortcut added raw when only
+ *   b is).  Both operands share C and G.
+ * dr_group_norm_backward_f32: the apply step backwards with `out` its result (the LeakyReLU's derivative is read off its sign) -> grad_a, d gamma_a,
+ *   d beta_a and, when b took part, grad_b (and, when b was normalised, d gamma_b, d beta_b).  Any output may be NULL.  Float64 column reductions
+ *   over a fixed grid.  workspace: dr_group_norm_backward_workspace_bytes(N, C, G).
+ * dr_knn_interpolate_f32: knn_interpolate_pack_mode(q, s, x, neighb_inds, k = None) (vision3d/ops/knn_interpolate.py:43-77): out[q] = sum_h w_h x[i_h]
+ *   with w = mask / (d^2 + 1e-8) / (sum + 1e-8), the shadow index Ns masked (an all-shadow row gives zeros).  neighb_inds [Nq, H] int64; out has
+ *   leading dimension ldo, so it may be a column slice of the decoder's concatenation buffer (EXP/point_backbone.py:81-88).  H <= 64 (DR_ENOSUP beyond).
+ * dr_knn_interpolate_backward_f32: grad_x [Ns, C] (zeroed here, then fp32 atomics) from grad_out [Nq, ldg].  H <= 64.
+ * dr_kpconv_neighbor_count_f32: the neighbour count of KPConv's normalisation (vision3d/layers/kpconv.py:137-139: neighbours whose feature sum is
+ *   > 0) exactly as dr_kpconv_gather_f32 sums it -> counts int32 [Nq] (before the floor at 1).  For tests: the count is a discrete decision. */
+size_t dr_group_norm_workspace_bytes(int N, int C);
+int dr_group_norm_stats_f32(int N, int C, int G, const float* x, int ldx, float eps, float* mean, float* rstd, void* workspace, size_t workspace_bytes,
+                            void* stream);
+int dr_group_norm_apply_f32(int N, int C, int G, const float* a, int lda, const float* mean_a, const float* rstd_a, const float* gamma_a, const float* beta_a,
+                            const float* b, int ldb, const float* mean_b, const float* rstd_b, const float* gamma_b, const float* beta_b, float leaky_slope,
+                            int activate, float* out, int ldo, void* stream);
+size_t dr_group_norm_backward_workspace_bytes(int N, int C, int G);
+int dr_group_norm_backward_f32(int N, int C, int G, const float* grad_out, int ldg, const float* out, int ldo, const float* a, int lda, const float* mean_a,
+                               const float* rstd_a, const float* gamma_a, const float* b, int ldb, const float* mean_b, const float* rstd_b,
+                               const float* gamma_b, float leaky_slope, int activate, float* grad_a, int ldga, float* grad_gamma_a, float* grad_beta_a,
+                               float* grad_b, int ldgb, float* grad_gamma_b, float* grad_beta_b, void* workspace, size_t workspace_bytes, void* stream);
+int dr_knn_interpolate_f32(int Nq, int Ns, int H, int C, const float* q_pts, const float* s_pts, const int64_t* neighb_inds, const float* x, float* out,
+                           int ldo, void* stream);
+int dr_knn_interpolate_backward_f32(int Nq, int Ns, int H, int C, const float* q_pts, const float* s_pts, const int64_t* neighb_inds, const float* grad_out,
+                                    int ldg, float* grad_x, void* stream);
+int dr_kpconv_neighbor_count_f32(int Nq, int Ns, int H, int Cin, const int64_t* neighb_inds, const float* x, int32_t* counts, void* stream);
 
 /* PnP-RANSAC registration of the fine correspondences (EXP/eval.py:174-182 -> vision3d/utils/opencv.py:10-63 = cv2.solvePnPRansac with
  * iterationsCount = 50000, reprojectionError = 8.0, flags = SOLVEPNP_P3P).  OpenCV is not part of the reference tree: the published algorithm of
