@@ -7,14 +7,21 @@ dr_focal_loss_*).  Every function reads the reference module's own parameters, s
     conf, src_idx, tgt_idx, w = matching_head_2d3d(model.coarse_matching, pcd, img, src_mask, tgt_mask)    # EXP/model.py:548
     losses = coarse_matching_loss(loss_fn.c_loss, output_dict)                                              # EXP/loss.py:30-75
 
-The Fourier embeddings of the pixel / point positions are constants of the graph (the reference's own FourierEmbedding module computes them);
-the GT search, q_sample, the warp, the backbones and the fine loss stay the reference's code: gradients reach the backbones through the
+    loss, recall = fine_matching_loss(loss_fn.f_loss, data_dict, output_dict)                                # EXP/loss.py:157-215
+    warped, tgt, R_forwd, t_forwd = noising_warp(model, s_pcd, t_pcd_da, src_mask, tgt_mask_da, x)          # EXP/model.py:830-846
+
+The Fourier embeddings of the pixel / point positions are constants of the graph by default (the reference's own FourierEmbedding module
+computes them); `fusion_module(..., embed_grad=True)` computes the point embedding with gradients enabled, so that the gradient of the warped
+points (noising_warp: Sinkhorn -> top-K Procrustes -> R, t) reaches denoising_coarse_matching.bin_score as in the reference.  The image
+backbone (with DINOv2 / Depth-Anything) and the inline GT retry ladder stay the reference's code: gradients reach the backbones through the
 returned input gradients.
 """
+import sys
+
 import torch
 
 from . import lib
-from .autograd import _MatchingHeadG, focal_loss, _mm
+from .autograd import _MatchingHeadG, _Procrustes, _SinkhornConf, focal_loss, _mm
 
 
 def _det(t):
@@ -101,17 +108,21 @@ def fusion_layer(layer, x, y, y_mask=None, n_head=None):
     return _FusionLayer.apply(x, y, y_mask, H, *_fusion_layer_params(layer))
 
 
-def fusion_module(module, img_feats, img_dino, img_pixels, pcd_feats, pcd_points):
+def fusion_module(module, img_feats, img_dino, img_pixels, pcd_feats, pcd_points, embed_grad=False):
     """CrossModalFusionModule.forward (EXP/fusion_module.py:61-107) from the module's own parameters, no masks (the path passes none,
     EXP/model.py:386-392, 615-621) -> (img [B,M,C], pcd [B,N,C]).  Gradients: every parameter, and whichever of img_feats / img_dino / pcd_feats
-    requires grad; the positions are constants."""
+    requires grad; the positions are constants -- unless embed_grad: then the point embedding (vision3d's FourierEmbedding is differentiable in
+    its input) is computed with gradients enabled and pcd_points receives its gradient through pcd_emb_proj."""
     img = torch.cat([linear(img_feats, module.img_in_proj, relu=True), linear(img_dino, module.img_in_proj_dino, relu=True)], dim=-1)  # relu(cat)
     img = linear(img, module.img_in_proj_all)
     pcd = linear(pcd_feats, module.pcd_in_proj)
     if module.use_embedding:
         with torch.no_grad():
             e_img = module.embedding(img_pixels.float())
-            e_pcd = module.embedding((pcd_points - pcd_points.mean(dim=1)).float())    # fusion_module.py:55-59
+            if not embed_grad:
+                e_pcd = module.embedding((pcd_points - pcd_points.mean(dim=1)).float())    # fusion_module.py:55-59
+        if embed_grad:
+            e_pcd = module.embedding((pcd_points - pcd_points.mean(dim=1)).float())
         img = img + linear(e_img, module.img_emb_proj)
         pcd = pcd + linear(e_pcd, module.pcd_emb_proj)
     for i, block in enumerate(module.blocks):
@@ -217,3 +228,95 @@ def coarse_matching_loss(loss_module, output_dict):
     loss_focal = focal_loss(output_dict["conf_matrix_pred"], conf_gt, *hp)
     loss_gt_hat = focal_loss(output_dict["conf_matrix_gt_hat"], conf_gt, *hp)
     return loss_circle, loss_circle_dn, loss_focal, loss_gt_hat
+
+
+class _FineLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, img_feats, pcd_feats, img_points, pcd_points, pcd_pixels, transform, sel_pixels, sel_indices, image_w, params):
+        loss, recall, saved = lib.fine_loss(img_points, img_feats, pcd_points, pcd_pixels, pcd_feats, transform, sel_pixels, sel_indices, image_w, params)
+        ctx.save_for_backward(_det(img_feats), _det(pcd_feats), img_points, pcd_points, pcd_pixels, transform, sel_pixels, sel_indices, saved)
+        ctx.image_w, ctx.params, ctx.dtypes = image_w, params, (img_feats.dtype, pcd_feats.dtype)
+        ctx.mark_non_differentiable(recall)
+        return loss, recall
+
+    @staticmethod
+    def backward(ctx, g, _g_recall):
+        fi, fp, ip, pp, px, T, sp, si, saved = ctx.saved_tensors
+        gi, gp = lib.fine_loss_backward(ip, fi, pp, px, fp, T, sp, si, ctx.image_w, ctx.params, saved, g)
+        return gi.to(ctx.dtypes[0]), gp.to(ctx.dtypes[1]), None, None, None, None, None, None, None, None     # (the kernels are float32)
+
+
+def _fine_params(loss_module):
+    c = loss_module.circle_loss
+    return lib.fine_params(loss_module.pos_radius_3d, loss_module.neg_radius_3d, loss_module.pos_radius_2d, loss_module.neg_radius_2d,
+                           c.pos_margin, c.neg_margin, c.pos_optimal, c.neg_optimal, c.log_scale)
+
+
+def fine_loss(img_feats, pcd_feats, img_points, pcd_points, pcd_pixels, transform, img_sel_pixels, pcd_sel_indices, image_w, params):
+    """the fine loss on given selections (lib.fine_params) -> (loss, recall); differentiable in img_feats [HW,C] and pcd_feats [N,C]"""
+    return _FineLoss.apply(img_feats, pcd_feats, img_points, pcd_points, pcd_pixels, transform, img_sel_pixels, pcd_sel_indices, int(image_w), params)
+
+
+def fine_matching_loss(loss_module, data_dict, output_dict):
+    """FineMatchingLoss.forward (EXP/loss.py:157-215) -> (loss, recall).  The sub-sampling above max_correspondences is the reference's own
+    random_choice (vision3d.ops, numpy's global RNG), looked up in the module that defines the loss class: the random stream is the reference's."""
+    assert data_dict["batch_size"] == 1, "Only support the batch_size of 1."
+    sel_pixels, sel_indices = data_dict["img_corr_pixels"], data_dict["pcd_corr_indices"]
+    if sel_indices.shape[0] > loss_module.max_correspondences:
+        random_choice = vars(sys.modules[type(loss_module).__module__])["random_choice"]
+        sel = random_choice(sel_indices.shape[0], size=loss_module.max_correspondences, replace=False)
+        sel_pixels, sel_indices = sel_pixels[sel], sel_indices[sel]
+    return fine_loss(output_dict["img_feats_f"], output_dict["pcd_feats_f"], output_dict["img_points_f"], output_dict["pcd_points_f"],
+                     output_dict["pcd_pixels_f"], data_dict["transform"], sel_pixels, sel_indices, data_dict["image_w"], _fine_params(loss_module))
+
+
+def soft_procrustes(layer, conf, src_pcd, tgt_pcd, src_mask, tgt_mask):
+    """SoftProcrustesLayer.forward of the 2D-3D model (EXP/procrustes.py:48-93: K from the mask sums) on dr_procrustes_f32 ->
+    (R, t, R_forwd, t_forwd, condition, solution_mask); differentiable in conf (dr_procrustes_backward_f32) where it requires grad.  On a 0 / 1
+    matrix with more than K ones the reference's torch.sort leaves the choice among the equal entries unspecified; the device takes the lowest
+    flat indices (parity-unpinned)."""
+    return _Procrustes.apply(conf.float(), src_pcd.float().contiguous(), tgt_pcd.float().contiguous(), src_mask, tgt_mask, float(layer.sample_rate),
+                             float(layer.max_condition_num), True)
+
+
+def noising_warp(model, s_pcd, t_pcd, src_mask, tgt_mask, matrix):
+    """MATR2D3D.get_warped_from_noising_matching3D3D (EXP/model.py:830-846): masked fill (IN PLACE, as the reference) -> Sinkhorn with
+    denoising_coarse_matching.bin_score -> top-K Procrustes -> R_forwd s + t_forwd, as one autograd chain (dr_sinkhorn_f32, dr_procrustes_f32;
+    backward dr_procrustes_backward_f32 -> dr_sinkhorn_backward_f32) -> (warped [B,N,3], t_pcd float32, R_forwd, t_forwd).  Where the condition
+    gate fails R_forwd, t_forwd are the identity and no gradient flows."""
+    head = model.denoising_coarse_matching
+    if src_mask is not None:
+        matrix.masked_fill_(~(src_mask[..., None] * tgt_mask[:, None]).bool(), float("-inf"))
+    conf = _SinkhornConf.apply(matrix.float(), head.bin_score, int(head.skh_iters), src_mask, tgt_mask)
+    _, _, Rf, tf, _, _ = soft_procrustes(model.denoising_soft_procrustes, conf, s_pcd, t_pcd, src_mask, tgt_mask)
+    warped = (torch.matmul(Rf, s_pcd.float().transpose(1, 2)) + tf).transpose(1, 2)
+    return warped, t_pcd.type(torch.float32), Rf, tf
+
+
+_SCHEDULES = {}     # (timesteps, device) -> (sqrt(alphas_cumprod), sqrt(1 - alphas_cumprod)), float64, on the device
+
+
+def _schedule(timesteps, device):
+    key = (int(timesteps), str(device))
+    hit = _SCHEDULES.get(key)
+    if hit is None:
+        import math
+        with torch.no_grad():                                                # cosine_beta_schedule (EXP/model.py:109-121) and q_sample's tables (:128-134)
+            x = torch.linspace(0, timesteps, timesteps + 1, dtype=torch.float64)
+            ac = torch.cos(((x / timesteps) + 0.008) / (1 + 0.008) * math.pi * 0.5) ** 2
+            ac = ac / ac[0]
+            betas = torch.clip(1 - (ac[1:] / ac[:-1]), 0, 0.999).to(device)
+            alphas_cumprod = torch.cumprod(1. - betas, dim=0)
+            hit = _SCHEDULES[key] = (torch.sqrt(alphas_cumprod), torch.sqrt(1. - alphas_cumprod))
+    return hit
+
+
+@torch.no_grad()
+def q_sample(x_start, t, noise=None, timesteps=1000):
+    """q_sample (EXP/model.py:123-139) with the 1 000-step schedule tables built once per (timesteps, device): the same float64 torch ops in the
+    same order, so the result is bit-equal; the two coefficients are gathered by `t` on the device (no host read)."""
+    if noise is None:
+        noise = torch.randn_like(x_start)
+    sa, so = _schedule(timesteps, x_start.device)
+    shape = (t.shape[0],) + (1,) * (len(x_start.shape) - 1)
+    return sa.gather(-1, t).reshape(shape) * x_start + so.gather(-1, t).reshape(shape) * noise

@@ -68,6 +68,12 @@ class CircleLossParams(ctypes.Structure):
     _fields_ = [(n, c_float) for n in ("pos_margin", "neg_margin", "pos_optimal", "neg_optimal", "log_scale", "pos_overlap", "neg_overlap")]
 
 
+class FineLossParams(ctypes.Structure):
+    """dr_fine_loss_params (include/diffreg_hip.h)"""
+    _fields_ = [(n, c_float) for n in ("pos_radius_3d", "neg_radius_3d", "pos_radius_2d", "neg_radius_2d", "pos_margin", "neg_margin", "pos_optimal",
+                                       "neg_optimal", "log_scale")]
+
+
 class PlanesLinear(ctypes.Structure):
     """dr_planes_linear (include/diffreg_hip.h)"""
     _fields_ = [("rows", c_int), ("C", c_int), ("nblk", c_int),
@@ -266,6 +272,12 @@ SIGNATURES.update({
                                                                                                        c_size_t, c_void_p]),
     "dr_circle_loss_backward_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 4 +
                                     [_P(CircleLossParams)] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    # ABI 0.6.0: the 2D-3D fine loss
+    "dr_fine_loss_saved_bytes": (c_size_t, [c_int]),
+    "dr_fine_loss_f32": (c_int, [c_int] * 4 + [c_void_p] * 8 + [c_int, _P(FineLossParams), c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dr_fine_loss_backward_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dr_fine_loss_backward_f32": (c_int, [c_int] * 4 + [c_void_p] * 8 + [c_int, _P(FineLossParams), c_void_p, c_size_t] + [c_void_p] * 4 +
+                                  [c_size_t, c_void_p]),
 })
 
 
@@ -279,7 +291,7 @@ def _bind(table):
 _bind(SIGNATURES)
 _INIT_DONE = False
 
-ABI_VERSION = 500          # DR_ABI_VERSION of the include/diffreg_hip.h these signatures were written against
+ABI_VERSION = 600          # DR_ABI_VERSION of the include/diffreg_hip.h these signatures were written against
 if _lib.dr_version() // 100 != ABI_VERSION // 100:
     raise ImportError("libdiffreg_hip.so is ABI %d, this binding is written against %d: rebuild (make -C diff-reg_amd/csrc)"
                       % (_lib.dr_version(), ABI_VERSION))
@@ -1189,6 +1201,52 @@ def circle_loss_backward(img, pcd, img_idx, pcd_idx, min_ov, max_ov, params, gra
     check(_lib.dr_circle_loss_backward_f32(M, N, C, ptr(img), ptr(pcd), ii.numel(), ptr(ii), ptr(jj), ptr(mn), ptr(mx), ctypes.byref(params), ptr(gl),
                                            ptr(loss), ptr(gi), ptr(gp), ptr(ws), wsb, stream_of(img)))
     return loss, gi, gp
+
+
+def fine_params(pos_radius_3d, neg_radius_3d, pos_radius_2d, neg_radius_2d, pos_margin, neg_margin, pos_optimal, neg_optimal, log_scale):
+    return FineLossParams(*(float(v) for v in (pos_radius_3d, neg_radius_3d, pos_radius_2d, neg_radius_2d, pos_margin, neg_margin, pos_optimal,
+                                               neg_optimal, log_scale)))
+
+
+def _fine_inputs(img_points, img_feats, pcd_points, pcd_pixels, pcd_feats, transform, img_sel_pixels, pcd_sel_indices):
+    f = lambda t_: t_.detach().contiguous().float()
+    i = lambda t_: t_.detach().contiguous().to(torch.int64)
+    ip, fi, pp, px, fp, T = f(img_points), f(img_feats), f(pcd_points), f(pcd_pixels), f(pcd_feats), f(transform)
+    sp, si = i(img_sel_pixels), i(pcd_sel_indices)
+    (HW, C), N, M = fi.shape, fp.shape[0], si.shape[0]
+    if ip.shape != (HW, 3) or pp.shape != (N, 3) or px.shape != (N, 2) or fp.shape != (N, C) or T.shape != (4, 4) or sp.shape != (M, 2):
+        raise RuntimeError("fine_loss: shapes img_points %s img_feats %s pcd_points %s pcd_pixels %s pcd_feats %s transform %s img_sel_pixels %s "
+                           "pcd_sel_indices %s" % tuple(tuple(t_.shape) for t_ in (ip, fi, pp, px, fp, T, sp, si)))
+    return (ip, fi, pp, px, fp, T, sp, si), (HW, N, M, C)
+
+
+def fine_loss(img_points, img_feats, pcd_points, pcd_pixels, pcd_feats, transform, img_sel_pixels, pcd_sel_indices, image_w, params):
+    """FineMatchingLoss.forward behind its random_choice (dr_fine_loss_f32): img_points [HW,3], img_feats [HW,C], pcd_points [N,3], pcd_pixels
+    [N,2], pcd_feats [N,C], transform [4,4], img_sel_pixels [M,2] (v, u), pcd_sel_indices [M] -> (loss, recall, saved): two 0-dim views of one
+    device tensor, and the opaque statistics fine_loss_backward wants.  M <= 1024, C <= 256 (raises beyond)."""
+    ensure_init()
+    ts, (HW, N, M, C) = _fine_inputs(img_points, img_feats, pcd_points, pcd_pixels, pcd_feats, transform, img_sel_pixels, pcd_sel_indices)
+    dev = ts[1].device
+    out = torch.empty(2, device=dev)
+    nb = _lib.dr_fine_loss_saved_bytes(M)
+    saved = torch.empty(max(nb, 1), dtype=torch.uint8, device=dev)
+    check(_lib.dr_fine_loss_f32(HW, N, M, C, *(ptr(t_) for t_ in ts), int(image_w), ctypes.byref(params), ptr(out), ptr(saved), nb, stream_of(ts[1])))
+    return out[0], out[1], saved
+
+
+def fine_loss_backward(img_points, img_feats, pcd_points, pcd_pixels, pcd_feats, transform, img_sel_pixels, pcd_sel_indices, image_w, params, saved,
+                       grad_loss=None):
+    """-> (d loss / d img_feats [HW,C], d loss / d pcd_feats [N,C]), dense, scaled by grad_loss (0-dim device tensor or None = 1)"""
+    ensure_init()
+    ts, (HW, N, M, C) = _fine_inputs(img_points, img_feats, pcd_points, pcd_pixels, pcd_feats, transform, img_sel_pixels, pcd_sel_indices)
+    dev = ts[1].device
+    gi, gp = torch.empty(HW, C, device=dev), torch.empty(N, C, device=dev)
+    gl = None if grad_loss is None else grad_loss.detach().reshape(()).float().contiguous()
+    wsb = _lib.dr_fine_loss_backward_workspace_bytes(M, C)
+    ws = torch.empty(max(wsb, 1), dtype=torch.uint8, device=dev)
+    check(_lib.dr_fine_loss_backward_f32(HW, N, M, C, *(ptr(t_) for t_ in ts), int(image_w), ctypes.byref(params), ptr(saved), saved.numel(), ptr(gl),
+                                         ptr(gi), ptr(gp), ptr(ws), wsb, stream_of(ts[1])))
+    return gi, gp
 
 
 def dual_softmax(sim, temperature, src_mask=None, tgt_mask=None):

@@ -23,9 +23,10 @@ libdiffreg_hip, gradients into the modules' own parameters and back to the backb
 
     accelerate(model, training=True);  accelerate_loss(loss_fn)          # EXP/trainval.py, after create_model / OverallLoss(cfg)
 
-accelerate_loss re-binds CoarseMatchingLoss.forward (EXP/loss.py:30-75; an OverallLoss instance: its c_loss) to the device circle + focal loss.
-The GT search, q_sample, the warp, the backbones and the fine loss stay the reference's code -- unless the overlay is installed with
-`partition=True`: then the patch partition and the ground-truth patch overlaps between the backbones and the coarse matching
+accelerate_loss re-binds CoarseMatchingLoss.forward (EXP/loss.py:30-75; an OverallLoss instance: its c_loss) to the device circle + focal loss;
+with `fine=True` also FineMatchingLoss.forward (EXP/loss.py:157-215; its f_loss) to the device fine loss (dr_fine_loss_*; the sub-sampling stays
+the reference's random_choice).  The GT search, q_sample, the warp and the backbones stay the reference's code -- unless the overlay is
+installed with `partition=True`: then the patch partition and the ground-truth patch overlaps between the backbones and the coarse matching
 (EXP/model.py:395-540: point_to_node_partition, patchify, get_2d3d_node_correspondences) run on the device (diffreg_hip/partition2d3d.py), and
 with `training=True` also the GT search of the training branch (model.py:569: get_correspondences; to_o3d_pcd becomes the identity).  These are
 module-level names that forward() calls inline, so they are re-bound in the globals of the module that defines the model's class; `remove()`
@@ -37,9 +38,22 @@ restores them.  Without the flag no global is touched.
 With `backbone=True` the point backbone in front of all of it (`self.pcd_backbone(pcd_feats, data_dict)`, EXP/model.py:366-368) runs on the device
 too, in eval and in train mode (diffreg_hip/pcd_backbone2d3d.py: forward and backward in libdiffreg_hip, gradients into the module's own parameters):
 `pcd_backbone.forward` is re-bound on the instance and `remove()` restores it.  With training=True the gradients of the device fusion path flow into
-the device backbone.  The image backbone stays the reference's code.
+the device backbone.
 
     accelerate(model, training=True, partition=True, backbone=True)
+
+With `training=True, noising=True` the noising front end of the training branch (EXP/model.py:568-611) runs on the device as well:
+`denoising_soft_procrustes.forward` is re-bound on the instance to the device fit under model.train() (the GT retry ladder's calls, :583; on its
+0 / 1 matrices with more than K ones the reference's sort leaves the choice among equal entries unspecified and the device takes the lowest flat
+indices -- parity-unpinned); the warp under model.train() is masked fill -> Sinkhorn -> top-K Procrustes -> R_forwd s + t_forwd as one autograd
+chain, and the denoising transformer computes its point embedding with gradients enabled, so d loss / d denoising_coarse_matching.bin_score
+carries the term through the warp that the reference has (without the flag the device path treats the warped points as constants); `q_sample`
+is re-bound in the globals of the model's defining module to a version with cached schedule tables (bit-equal).  `remove()` restores every site.
+
+    accelerate(model, training=True, partition=True, backbone=True, noising=True);  accelerate_loss(loss_fn, fine=True)
+
+What then stays the reference's code in a training step: the image backbone (with DINOv2 / Depth-Anything), the inline GT retry ladder and the
+other inline glue of MATR2D3D.forward.
 """
 import sys
 import types
@@ -51,11 +65,14 @@ from .engine import DenoiseEngine2D3D
 
 
 class LoopOverlay2D3D:
-    def __init__(self, model, n_head=4, engine_kwargs=None, training=False, partition=False, backbone=False):
+    def __init__(self, model, n_head=4, engine_kwargs=None, training=False, partition=False, backbone=False, noising=False):
         self.model = model
         self.training = bool(training)
         self.partition = bool(partition)
         self.backbone = bool(backbone)
+        self.noising = bool(noising)
+        if self.noising and not self.training:
+            raise ValueError("noising=True is the training branch's front end: it needs training=True")
         self._globals_saved = {}
         self.n_head = n_head
         self.engine_kwargs = dict(engine_kwargs or {})
@@ -77,6 +94,10 @@ class LoopOverlay2D3D:
         if self.backbone:
             pb = model.pcd_backbone
             pb.forward = lambda feats, data_dict: pcd_backbone2d3d.point_backbone(pb, feats, data_dict)
+        if self.noising:
+            self._orig.update(procrustes=model.denoising_soft_procrustes.forward)
+            model.denoising_soft_procrustes.forward = self._procrustes
+            self._bind_globals({"q_sample": autograd2d3d.q_sample})
         model._dr_overlay = self
 
     _MISSING = object()
@@ -87,19 +108,24 @@ class LoopOverlay2D3D:
         names = ["point_to_node_partition", "patchify", "get_2d3d_node_correspondences"]
         if self.training:
             names += ["get_correspondences", "to_o3d_pcd"]
+        self._bind_globals({name: getattr(p, name) for name in names})
+
+    def _bind_globals(self, table):
         g = vars(sys.modules[type(self.model).__module__])
-        for name in names:
+        for name, fn in table.items():
             self._globals_saved[name] = g.get(name, self._MISSING)
-            g[name] = getattr(p, name)
+            g[name] = fn
 
     def remove(self):
-        """restore the three call sites"""
+        """restore every site this overlay bound: the instance attributes and the globals of the model's defining module"""
         m = self.model
         sites = [(m, "get_warped_from_noising_matching3D3D"), (m.denoising_transformer, "forward"), (m.denoising_coarse_matching, "forward")]
         if self.training:
             sites += [(m.transformer, "forward"), (m.coarse_matching, "forward")]
         if self.backbone:
             sites += [(m.pcd_backbone, "forward")]
+        if self.noising:
+            sites += [(m.denoising_soft_procrustes, "forward")]
         for obj, name in sites:
             if name in obj.__dict__:
                 del obj.__dict__[name]
@@ -137,6 +163,8 @@ class LoopOverlay2D3D:
     # ---- the three call sites ------------------------------------------------------------------------------------------------
     def _warp(self, s_pcd, t_pcd, src_mask, tgt_mask, matrix):
         if self.model.training:
+            if self.noising and src_mask is not None:      # (without masks the reference's own code raises: conf is never assigned, :832-841)
+                return autograd2d3d.noising_warp(self.model, s_pcd, t_pcd, src_mask, tgt_mask, matrix)
             return self._orig["warp"](s_pcd, t_pcd, src_mask, tgt_mask, matrix)
         if self._k == 0:
             self._rec = dict(s_pcd=s_pcd, t_pcd_da=t_pcd, src_mask=src_mask, tgt_mask_da=tgt_mask, x_T=matrix.detach().clone())
@@ -153,7 +181,8 @@ class LoopOverlay2D3D:
     def _transformer(self, img_feats, img_dino, img_pixels, pcd_feats, pcd_points):
         if self.model.training:
             if self.training:
-                return autograd2d3d.fusion_module(self.model.denoising_transformer, img_feats, img_dino, img_pixels, pcd_feats, pcd_points)
+                return autograd2d3d.fusion_module(self.model.denoising_transformer, img_feats, img_dino, img_pixels, pcd_feats, pcd_points,
+                                                  embed_grad=self.noising)
             return self._orig["transformer"](img_feats, img_dino, img_pixels, pcd_feats, pcd_points)
         if self._k == 0:
             self._rec.update(img_feats=img_feats, img_dino=img_dino, img_pixels=img_pixels, pcd_feats=pcd_feats)
@@ -183,6 +212,11 @@ class LoopOverlay2D3D:
         return x_start, None, None, None
 
 
+    def _procrustes(self, conf_matrix, src_pcd, tgt_pcd, src_mask, tgt_mask):
+        if self.model.training:
+            return autograd2d3d.soft_procrustes(self.model.denoising_soft_procrustes, conf_matrix, src_pcd, tgt_pcd, src_mask, tgt_mask)
+        return self._orig["procrustes"](conf_matrix, src_pcd, tgt_pcd, src_mask, tgt_mask)
+
     # ---- the training branch's coarse modules (training=True): the device path in train mode, the original code in eval mode ---------------
     def _coarse_transformer(self, img_feats, img_dino, img_pixels, pcd_feats, pcd_points, *args, **kwargs):
         if self.model.training and not args and not kwargs:
@@ -195,17 +229,32 @@ class LoopOverlay2D3D:
         return self._orig["coarse_matching"](src_feats, tgt_feats, src_mask, tgt_mask, *args, **kwargs)
 
 
-def accelerate(model, n_head=4, training=False, partition=False, backbone=False, **engine_kwargs):
+def accelerate(model, n_head=4, training=False, partition=False, backbone=False, noising=False, **engine_kwargs):
     """install the overlay on a MATR2D3D instance (see the module docstring); returns the LoopOverlay2D3D (`.remove()` undoes it).
     training=True: the training branch's four coarse modules run on the device under model.train() as well.
     partition=True: the patch partition and GT patch overlaps (and, with training, the GT search) run on the device as well.
-    backbone=True: the point backbone (model.pcd_backbone) runs on the device, in eval and train mode."""
-    return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs, training=training, partition=partition, backbone=backbone)
+    backbone=True: the point backbone (model.pcd_backbone) runs on the device, in eval and train mode.
+    noising=True (with training=True): the GT ladder's Procrustes fits, q_sample and the warp run on the device under model.train(), and the
+    warp's gradient reaches denoising_coarse_matching.bin_score."""
+    return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs, training=training, partition=partition, backbone=backbone,
+                           noising=noising)
 
 
-def accelerate_loss(loss_module):
+def accelerate_loss(loss_module, fine=False):
     """re-bind CoarseMatchingLoss.forward of `loss_module` (or of its `c_loss`: an OverallLoss) to autograd2d3d.coarse_matching_loss, on the
-    instance; returns a function that restores it"""
+    instance; fine=True: also FineMatchingLoss.forward of its `f_loss` to autograd2d3d.fine_matching_loss.  Returns a function that restores
+    every site it bound."""
+    if fine and not hasattr(loss_module, "f_loss"):          # (before anything is bound)
+        raise ValueError("accelerate_loss(fine=True) needs an OverallLoss (a module with c_loss and f_loss)")
     target = loss_module.c_loss if hasattr(loss_module, "c_loss") else loss_module
     target.forward = lambda output_dict: autograd2d3d.coarse_matching_loss(target, output_dict)
-    return lambda: target.__dict__.pop("forward", None)
+    bound = [target]
+    if fine:
+        f = loss_module.f_loss
+        f.forward = lambda data_dict, output_dict: autograd2d3d.fine_matching_loss(f, data_dict, output_dict)
+        bound.append(f)
+
+    def restore():
+        for mod in bound:
+            mod.__dict__.pop("forward", None)
+    return restore

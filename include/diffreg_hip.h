@@ -42,8 +42,10 @@ extern "C" {
  *   0.4.0  the 2D-3D patch partition and ground-truth overlaps: dr_point_to_node_partition_f32, dr_patchify_f32,
  *          dr_node_correspondences_2d3d_f32, dr_mutual_nn_radius_f32, dr_radius_pairs_f32 (new entries only; nothing older changed).
  *   0.5.0  the 2D-3D point backbone: dr_group_norm_stats_f32, dr_group_norm_apply_f32, dr_group_norm_backward_f32, dr_knn_interpolate_f32,
- *          dr_knn_interpolate_backward_f32, dr_kpconv_neighbor_count_f32 and their workspace sizes (new entries only; nothing older changed). */
-#define DR_ABI_VERSION 500
+ *          dr_knn_interpolate_backward_f32, dr_kpconv_neighbor_count_f32 and their workspace sizes (new entries only; nothing older changed).
+ *   0.6.0  the 2D-3D fine loss: dr_fine_loss_f32, dr_fine_loss_backward_f32, their two size queries and the new struct dr_fine_loss_params
+ *          (new entries only; nothing older changed). */
+#define DR_ABI_VERSION 600
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
 const char* dr_last_hip_error(void);  /* text of the last failing HIP call on this thread */
@@ -842,6 +844,37 @@ int dr_circle_loss_f32(int M, int N, int C, const float* img, const float* pcd, 
 int dr_circle_loss_backward_f32(int M, int N, int C, const float* img, const float* pcd, int K, const int64_t* img_idx, const int64_t* pcd_idx,
                                 const float* min_overlaps, const float* max_overlaps, const dr_circle_loss_params* params, const float* grad_loss,
                                 float* loss, float* grad_img, float* grad_pcd, void* workspace, size_t workspace_bytes, void* stream);
+
+/* The fine loss of the 2D-3D training step (EXP/loss.py:157-215, FineMatchingLoss.forward behind its random_choice; ABI 0.6.0):
+ * dr_fine_loss_f32 replaces loss.py:175, 186-213 and get_recall (:146-155): img_points [HW,3], img_feats [HW,C], pcd_points [N,3], pcd_pixels [N,2],
+ *   pcd_feats [N,C], transform [4,4] (row-major; applied to the M selected points only), img_sel_pixels [M,2] int64 (v, u: the dense row is
+ *   v * image_w + u), pcd_sel_indices [M] int64.  dist3d / dist2d are float32 norms of differences (pairwise_distance(strict=True)), positives lie
+ *   under both positive radii, negatives above either negative radius, fdist = clamp(x^2 - 2 x y + y^2, 0) (squared, normalized=False), the
+ *   circle loss is the unweighted one of vision3d/loss/circle_loss.py:11-52 (an entry outside a mask keeps the logit 0 and counts in the
+ *   log-sum-exp).  loss_recall (2 device floats): [0] the loss (NaN for an empty anchor set on either side, torch's mean of an empty selection),
+ *   [1] the recall (rows whose arg-min of fdist -- first minimum -- is a positive / (rows holding a positive + 1e-12)).  `saved`: caller memory
+ *   of dr_fine_loss_saved_bytes(M), opaque (row / column log-sum-exps, anchor flags, gradient coefficients), handed to the backward.  Dot
+ *   products, logits, log-sum-exps and means in double, every sum in one fixed order -- on purpose NOT dr_circle_loss_f32's choice of float32
+ *   logits: the float32 rounding of fdist times log_scale is the size of the bar the gradients are held to (csrc/fine_loss.hip).  A selection outside its tensor (v or u negative, u >= image_w, row >= HW; index outside [0, N)) reads a zero row and
+ *   receives no gradient (the reference raises).  M <= 1024, C <= 256: DR_ENOSUP beyond.
+ * dr_fine_loss_backward_f32: the same inputs and `saved` -> grad_img_feats [HW,C], grad_pcd_feats [N,C] = d loss / d features * *grad_loss
+ *   (device float; NULL = 1), DENSE: zero-filled, then the <= M touched rows; selections of one pixel / point accumulate (in selection order), as
+ *   torch's index backward; zero where the clamp is active; all zero for an empty anchor set.  No atomics: two runs are bit-identical.
+ *   workspace: dr_fine_loss_backward_workspace_bytes(M, C). */
+typedef struct {
+    float pos_radius_3d, neg_radius_3d, pos_radius_2d, neg_radius_2d;    /* cfg.loss.fine_loss.*_radius_* */
+    float pos_margin, neg_margin, pos_optimal, neg_optimal, log_scale;   /* cfg.loss.fine_loss.* */
+} dr_fine_loss_params;
+size_t dr_fine_loss_saved_bytes(int M);
+int dr_fine_loss_f32(int HW, int N, int M, int C, const float* img_points, const float* img_feats, const float* pcd_points, const float* pcd_pixels,
+                     const float* pcd_feats, const float* transform, const int64_t* img_sel_pixels, const int64_t* pcd_sel_indices, int image_w,
+                     const dr_fine_loss_params* params, float* loss_recall, void* saved, size_t saved_bytes, void* stream);
+size_t dr_fine_loss_backward_workspace_bytes(int M, int C);
+int dr_fine_loss_backward_f32(int HW, int N, int M, int C, const float* img_points, const float* img_feats, const float* pcd_points,
+                              const float* pcd_pixels, const float* pcd_feats, const float* transform, const int64_t* img_sel_pixels,
+                              const int64_t* pcd_sel_indices, int image_w, const dr_fine_loss_params* params, const void* saved, size_t saved_bytes,
+                              const float* grad_loss, float* grad_img_feats, float* grad_pcd_feats, void* workspace, size_t workspace_bytes,
+                              void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Forward half of the training branch: the pieces of Pipeline.forward's
