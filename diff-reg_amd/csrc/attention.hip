@@ -1171,6 +1171,10 @@ int attention_configure() {
     int rc = configure_attn<8, 2>();
     if (rc == DR_OK) rc = configure_attn<14, 4>();
     if (rc == DR_OK) rc = configure_attn<17, 5>();
+    // 136 < d <= 160 (the training primitives' documented range): the 32-query kernel alone
+    if (rc == DR_OK)
+        DR_HIP_CHECK(hipFuncSetAttribute((const void*)attention_kernel<20, 5>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                         (int)(AttnGeom<20, 5>::SMEM_FLOATS * sizeof(float))));
     return rc;
 }
 
@@ -1258,6 +1262,14 @@ int launch_attention(const AttnArgs& a, hipStream_t st) {
     if (a.d <= 64) return launch_attn<8, 2>(a, st);       // 2D-3D: d = 64
     if (a.d <= 112) return launch_attn<14, 4>(a, st);     // 3DMatch: d = 108
     if (a.d <= 136) return launch_attn<17, 5>(a, st);     // 4DMatch: d = 132
+    if (a.d <= 160 && !a.qimg[0] && !a.pimg[0]) {         // no model uses it: the 32-query, 4-wave kernel on float32 operands only
+        using G = AttnGeom<20, 5>;
+        static_assert(G::SMEM_FLOATS * sizeof(float) <= 160 * 1024, "LDS of the d <= 160 geometry");
+        const int maxLq = a.nseg2 > 0 && a.Lqb > a.Lq ? a.Lqb : a.Lq;
+        hipLaunchKernelGGL((attention_kernel<20, 5>), dim3((maxLq + 31) / 32, a.H, a.nseg + a.nseg2), dim3(256), G::SMEM_FLOATS * sizeof(float), st, a);
+        DR_LAUNCH_CHECK();
+        return DR_OK;
+    }
     return DR_ENOSUP;
 }
 

@@ -237,10 +237,12 @@ static size_t bwd_lds(int d) {
     return (tiles + (sums > wave_area ? sums - wave_area : 0) + NW * 64 + 64) * sizeof(float);
 }
 
+constexpr size_t BWD_LDS_MAX = 160 * 1024;
+
 template <int DT, int NW>
 static int launch_bwd(const AttnBwdArgs& a, hipStream_t st) {
     const size_t lds = bwd_lds<DT, NW>(a.d);
-    if (lds > 160 * 1024) return DR_ENOSUP;
+    if (lds > BWD_LDS_MAX) return DR_ENOSUP;
     // raise the dynamic-LDS limit whenever this launch needs more than the largest size set so far for this instantiation (a later call with a
     // larger head dim inside the same DT bucket needs more than the first one did; as in sinkhorn.hip the attribute follows the need)
     static size_t lds_set = 0;
@@ -258,6 +260,14 @@ static int launch_bwd(const AttnBwdArgs& a, hipStream_t st) {
     hipLaunchKernelGGL((attn_bwd_kernel<DT, NW, 2>), gk, blk, lds, st, a);
     DR_LAUNCH_CHECK();
     return DR_OK;
+}
+
+// the wave count follows the LDS need: the top of a bucket (d = 128: 167 680 B with 4 waves, d = 160: 166 912 B with 3) does not fit NW waves' tiles,
+// so that launch runs with one wave fewer (134 144 B / 125 184 B).  Same kernel body, same wave-order combine: bit-reproducible either way.
+template <int DT, int NW>
+static int launch_bwd_fit(const AttnBwdArgs& a, hipStream_t st) {
+    if (bwd_lds<DT, NW>(a.d) <= BWD_LDS_MAX) return launch_bwd<DT, NW>(a, st);
+    return launch_bwd<DT, NW - 1>(a, st);
 }
 
 }  // namespace
@@ -286,8 +296,8 @@ int dr_attention_backward_f32(int B, int H, int L, int S, int d, const float* q,
     hipStream_t st = (hipStream_t)stream;
     if (d <= 64) return launch_bwd<2, 4>(a, st);
     if (d <= 96) return launch_bwd<3, 4>(a, st);
-    if (d <= 128) return launch_bwd<4, 4>(a, st);
-    if (d <= 160) return launch_bwd<5, 3>(a, st);
+    if (d <= 128) return launch_bwd_fit<4, 4>(a, st);
+    if (d <= 160) return launch_bwd_fit<5, 3>(a, st);
     return DR_ENOSUP;
 }
 

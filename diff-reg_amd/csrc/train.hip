@@ -291,6 +291,9 @@ int dr_motion_l1_f32(int P, int N, const float* s_pcd, const float* flow, const 
 //     vb^T_j = sum_i D_ij,   ub^T_i = sum_j D_ij - sum_j vb^T_j Pv^T_ij,
 //     vb^{t-1}_j = - sum_i ub^t_i Pu^t_ij,   ub^{t-1}_i = - sum_j vb^{t-1}_j Pv^{t-1}_ij,
 //     dL/dZ_ij = D_ij - sum_t (vb^t_j Pv^t_ij + ub^t_i Pu^t_ij);   dL/da = sum over the dustbin row and column of dL/dZ.
+// A marginal of mass 0 (a pair without a valid row: log nu of the dustbin column = log 0; without a valid column: log mu of the dustbin row): its
+// dual variable is -inf, its plan entries exp(Z + u + v - log nu) are finite numbers (v - log nu = -LSE) that "-inf - -inf" cannot form, and its
+// adjoint is exactly 0 at every step (vb^T = 0 on the dustbin, and vb^{t-1} sums plans Pu that carry exp(v^{t-1}) = 0).  Its terms are left out.
 // One workgroup per pair; every step is one sweep over the matrix: row quantities by one wave per row (lanes over the columns, DPP
 // reduction), column quantities by one thread per column (rows in order, coalesced): no atomics, results do not depend on scheduling.
 // The 2 T + 2 T vectors live in the workspace (L2-resident), in double (see sk_backward_kernel).  The library runs the multi-launch form below
@@ -410,7 +413,7 @@ __global__ __launch_bounds__(1024) void sk_backward_kernel(SkBwdArgs A) {
             for (int j = lane; j < Cn; j += 64) {
                 const AT z = zval<AT>(Z, i, j, N, M, a);
                 if (z > -INFINITY) {
-                    s -= vb[j] * xexp(z + u[i] + v[j] - lnu(j));
+                    if (lnu(j) > -INFINITY) s -= vb[j] * xexp(z + u[i] + v[j] - lnu(j));      // (see "a marginal of mass 0" below)
                     if (it == T && i < N && j < M) s += xexp(z + u[i] + v[j] - norm) * (AT)G[(size_t)i * M + j];
                 }
             }
@@ -425,7 +428,7 @@ __global__ __launch_bounds__(1024) void sk_backward_kernel(SkBwdArgs A) {
                 AT s = 0;
                 for (int i = 0; i < R; ++i) {
                     const AT z = zval<AT>(Z, i, j, N, M, a);
-                    if (z > -INFINITY) s -= ub[i] * xexp(z + vprev[j] + u[i] - lmu(i));
+                    if (z > -INFINITY && lmu(i) > -INFINITY) s -= ub[i] * xexp(z + vprev[j] + u[i] - lmu(i));
                 }
                 vbp[j] = s;
             }
@@ -443,8 +446,8 @@ __global__ __launch_bounds__(1024) void sk_backward_kernel(SkBwdArgs A) {
                 if (i < N && j < M) g = xexp(z + uT[i] + vT[j] - norm) * (AT)G[(size_t)i * M + j];
                 for (int it = 1; it <= T; ++it) {
                     const AT ui = U[(size_t)(it - 1) * R + i];
-                    g -= VB[(size_t)(it - 1) * Cn + j] * xexp(z + ui + V[(size_t)it * Cn + j] - lnu(j));
-                    g -= UB[(size_t)(it - 1) * R + i] * xexp(z + V[(size_t)(it - 1) * Cn + j] + ui - lmu(i));
+                    if (lnu(j) > -INFINITY) g -= VB[(size_t)(it - 1) * Cn + j] * xexp(z + ui + V[(size_t)it * Cn + j] - lnu(j));
+                    if (lmu(i) > -INFINITY) g -= UB[(size_t)(it - 1) * R + i] * xexp(z + V[(size_t)(it - 1) * Cn + j] + ui - lmu(i));
                 }
             }
             if (i < N && j < M) A.gscores[((size_t)pair * N + i) * M + j] = (float)g;
@@ -537,8 +540,9 @@ __global__ __launch_bounds__(256) void skb_rows_kernel(SkbCtx A, int it) {
         double s = 0;
         for (int j = lane; j < Cn; j += 64) {
             const double z = skb_z(A, pair, i, j, v.a);
+            const double lnu_j = j < M ? v.norm : v.lnuM;
             if (z > -INFINITY) {
-                s -= vb[j] * xexp(z + ui + vv[j] - (j < M ? v.norm : v.lnuM));
+                if (lnu_j > -INFINITY) s -= vb[j] * xexp(z + ui + vv[j] - lnu_j);             // (a marginal of mass 0: no term)
                 if (it == T && i < N && j < M) s += xexp(z + ui + vv[j] - v.norm) * (double)G[(size_t)i * M + j];
             }
         }
@@ -556,8 +560,8 @@ __global__ __launch_bounds__(256) void skb_rows_kernel(SkbCtx A, int it) {
                 const double lnu_j = j < M ? v.norm : v.lnuM;
                 for (int t2 = 1; t2 <= T; ++t2) {
                     const double ui = v.U[(size_t)(t2 - 1) * R + i];
-                    g -= v.VB[(size_t)(t2 - 1) * Cn + j] * xexp(z + ui + v.V[(size_t)t2 * Cn + j] - lnu_j);
-                    g -= v.UB[(size_t)(t2 - 1) * R + i] * xexp(z + v.V[(size_t)(t2 - 1) * Cn + j] + ui - lmu_i);
+                    if (lnu_j > -INFINITY) g -= v.VB[(size_t)(t2 - 1) * Cn + j] * xexp(z + ui + v.V[(size_t)t2 * Cn + j] - lnu_j);
+                    if (lmu_i > -INFINITY) g -= v.UB[(size_t)(t2 - 1) * R + i] * xexp(z + v.V[(size_t)(t2 - 1) * Cn + j] + ui - lmu_i);
                 }
             }
             if (i < N && j < M) A.gscores[((size_t)pair * N + i) * M + j] = (float)g;
@@ -600,8 +604,8 @@ __global__ __launch_bounds__(64 * SKB_RP) void skb_cols_kernel(SkbCtx A, int it)
             const double* ub = v.UB + (size_t)(it - 1) * R;
             const double vpj = v.V[(size_t)(it - 1) * Cn + j];
             for (int i = p; i < R; i += SKB_RP) {
-                const double z = skb_z(A, pair, i, j, v.a);
-                if (z > -INFINITY) s -= ub[i] * xexp(z + vpj + u[i] - (i < N ? v.norm : v.lmuN));
+                const double z = skb_z(A, pair, i, j, v.a), lmu_i = i < N ? v.norm : v.lmuN;
+                if (z > -INFINITY && lmu_i > -INFINITY) s -= ub[i] * xexp(z + vpj + u[i] - lmu_i);
             }
         }
     }

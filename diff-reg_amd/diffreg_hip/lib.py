@@ -597,46 +597,56 @@ def motion_l1_backward(s_pcd, R_pred, t_pred, R_gt, t_gt, overlap_mask, flow=Non
     return gR, gt.view(P, 3, 1)
 
 
-def layernorm(x, gamma, beta, eps=1e-5):
-    """nn.LayerNorm over the last dim -> (y, mean_rstd [rows,2])"""
+def _out_or_empty(out, shape, like):
+    """the caller's result tensor (float32, contiguous, on the inputs' device, `shape`) or a fresh one"""
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=like.device)
+    if out.dtype != torch.float32 or out.device != like.device or tuple(out.shape) != tuple(shape) or not out.is_contiguous():
+        raise ValueError("out= must be a contiguous float32 tensor of shape %s on %s" % (tuple(shape), like.device))
+    return out
+
+
+def layernorm(x, gamma, beta, eps=1e-5, out=None):
+    """nn.LayerNorm over the last dim -> (y, mean_rstd [rows,2]); out = (y, mean_rstd) to write into"""
     ensure_init()
     x = x.contiguous().float()
     rows, C = x.reshape(-1, x.shape[-1]).shape
-    y = torch.empty_like(x)
-    st = torch.empty(rows, 2, device=x.device)
+    y = _out_or_empty(out[0] if out else None, x.shape, x)
+    st = _out_or_empty(out[1] if out else None, (rows, 2), x)
     check(_lib.dr_layernorm_f32(rows, C, ptr(x), ptr(gamma.contiguous()), ptr(beta.contiguous()), eps, ptr(y), ptr(st), stream_of(x)))
     return y, st
 
 
-def layernorm_backward(x, gamma, mean_rstd, grad_y):
+def layernorm_backward(x, gamma, mean_rstd, grad_y, out=None):
+    """-> (grad_x, grad_gamma, grad_beta); out = the three tensors to write into"""
     ensure_init()
     x, grad_y = x.contiguous().float(), grad_y.contiguous().float()
     rows, C = x.reshape(-1, x.shape[-1]).shape
-    gx = torch.empty_like(x)
-    gg, gb = torch.empty(C, device=x.device), torch.empty(C, device=x.device)
+    gx = _out_or_empty(out[0] if out else None, x.shape, x)
+    gg, gb = _out_or_empty(out[1] if out else None, (C,), x), _out_or_empty(out[2] if out else None, (C,), x)
     ws = torch.empty(_lib.dr_layernorm_backward_workspace_bytes(C), dtype=torch.uint8, device=x.device)
     check(_lib.dr_layernorm_backward_f32(rows, C, ptr(x), ptr(gamma.contiguous()), ptr(mean_rstd), ptr(grad_y), ptr(gx), ptr(gg), ptr(gb), ptr(ws), stream_of(x)))
     return gx, gg, gb
 
 
-def attention(q, k, v, H, q_mask=None, k_mask=None):
+def attention(q, k, v, H, q_mask=None, k_mask=None, out=None):
     """fused softmax(q k^T / sqrt(d)) v per head: q [B,L,C], k / v [B,S,C] (token layout, head h in columns h d ..) -> [B,L,C]"""
     ensure_init()
     B, L, C = q.shape
     S, d = k.shape[1], C // H
     q, k, v = q.contiguous().float(), k.contiguous().float(), v.contiguous().float()
-    out = torch.empty_like(q)
+    out = _out_or_empty(out, q.shape, q)
     check(_lib.dr_attention_f32(B, H, L, S, d, ptr(q), ptr(k), ptr(v), C, ptr(mask_u8(q_mask)), ptr(mask_u8(k_mask)), 1.0 / d ** 0.5, ptr(out), stream_of(q)))
     return out
 
 
-def attention_backward(q, k, v, o, grad_o, H, q_mask=None, k_mask=None):
-    """backward of attention(): -> (grad_q, grad_k, grad_v), fused (dr_attention_backward_f32)"""
+def attention_backward(q, k, v, o, grad_o, H, q_mask=None, k_mask=None, out=None):
+    """backward of attention(): -> (grad_q, grad_k, grad_v), fused (dr_attention_backward_f32); out = the three tensors to write into"""
     ensure_init()
     B, L, C = q.shape
     S, d = k.shape[1], C // H
     q, k, v, o, g = (t_.contiguous().float() for t_ in (q, k, v, o, grad_o))
-    gq, gk, gv = torch.empty_like(q), torch.empty_like(k), torch.empty_like(v)
+    gq, gk, gv = (_out_or_empty(out[i] if out else None, t_.shape, q) for i, t_ in enumerate((q, k, v)))
     wsb = _lib.dr_attention_backward_workspace_bytes(B, H, L)
     ws = torch.empty(wsb, dtype=torch.uint8, device=q.device)
     check(_lib.dr_attention_backward_f32(B, H, L, S, d, ptr(q), ptr(k), ptr(v), ptr(o), ptr(g), C, ptr(mask_u8(q_mask)), ptr(mask_u8(k_mask)), 1.0 / d ** 0.5,
@@ -644,61 +654,62 @@ def attention_backward(q, k, v, o, grad_o, H, q_mask=None, k_mask=None):
     return gq, gk, gv
 
 
-def softmax_rows(scores, scale, q_mask=None, k_mask=None):
+def softmax_rows(scores, scale, q_mask=None, k_mask=None, out=None):
     """scores [B,H,L,S] -> softmax over S of scale * scores with the layer's key mask"""
     ensure_init()
     scores = scores.contiguous().float()
     B, H, L, S = scores.shape
-    P = torch.empty_like(scores)
+    P = _out_or_empty(out, scores.shape, scores)
     qm, km = mask_u8(q_mask), mask_u8(k_mask)
     check(_lib.dr_softmax_rows_f32(B, H, L, S, ptr(scores), float(scale), ptr(qm), ptr(km), ptr(P), stream_of(scores)))
     return P
 
 
-def softmax_backward(P, grad_P, scale):
+def softmax_backward(P, grad_P, scale, out=None):
     ensure_init()
     P, grad_P = P.contiguous(), grad_P.contiguous().float()
-    out = torch.empty_like(P)
+    out = _out_or_empty(out, P.shape, P)
     check(_lib.dr_softmax_backward_f32(P.numel() // P.shape[-1], P.shape[-1], ptr(P), ptr(grad_P), float(scale), ptr(out), stream_of(P)))
     return out
 
 
-def relu_backward(y, grad_y):
+def relu_backward(y, grad_y, out=None):
     ensure_init()
     y, grad_y = y.contiguous(), grad_y.contiguous().float()
-    out = torch.empty_like(y)
+    out = _out_or_empty(out, y.shape, y)
     check(_lib.dr_relu_backward_f32(y.numel(), ptr(y), ptr(grad_y), ptr(out), stream_of(y)))
     return out
 
 
-def rotary(x, cos_t, sin_t, inverse=False, scale=1.0):
+def rotary(x, cos_t, sin_t, inverse=False, scale=1.0, out=None):
     """embed_rotary on rows [rows, C] with half tables [rows, C/2] (inverse = its transpose)"""
     ensure_init()
     x = x.contiguous().float()
-    out = torch.empty_like(x)
+    out = _out_or_empty(out, x.shape, x)
     rows, C = x.reshape(-1, x.shape[-1]).shape
     check(_lib.dr_rotary_f32(rows, C, ptr(x), ptr(cos_t.contiguous()), ptr(sin_t.contiguous()), 1 if inverse else 0, float(scale), ptr(out), stream_of(x)))
     return out
 
 
-def focal_loss_backward(conf, conf_gt, alpha=0.25, gamma=2.0, pos_w=1.0, neg_w=1.0):
+def focal_loss_backward(conf, conf_gt, alpha=0.25, gamma=2.0, pos_w=1.0, neg_w=1.0, out=None):
     """d loss / d conf of the sinkhorn-form focal loss (loss.py:311-314) -> [P,N,M] float32"""
     ensure_init()
     conf, conf_gt = conf.contiguous().float(), conf_gt.contiguous().float()
     P, N, M = conf.shape
-    g = torch.empty_like(conf)
+    g = _out_or_empty(out, conf.shape, conf)
     ws = _train_ws(P, N, M, conf.device)
     check(_lib.dr_focal_loss_backward_f32(P, N, M, ptr(conf), ptr(conf_gt), alpha, gamma, pos_w, neg_w, ptr(g), ptr(ws), stream_of(conf)))
     return g
 
 
-def sinkhorn_backward(scores, bin_score, iters, src_mask, tgt_mask, grad_conf):
-    """backward of conf = exp(log_optimal_transport(scores, bin_score, iters, masks))[:, :-1, :-1] -> (grad_scores [P,N,M], grad_bin_score 0-d)"""
+def sinkhorn_backward(scores, bin_score, iters, src_mask, tgt_mask, grad_conf, out=None):
+    """backward of conf = exp(log_optimal_transport(scores, bin_score, iters, masks))[:, :-1, :-1] -> (grad_scores [P,N,M], grad_bin_score 0-d);
+    out = (grad_scores [P,N,M], grad_bin_score per pair [P]) to write into"""
     ensure_init()
     scores, grad_conf = scores.contiguous().float(), grad_conf.contiguous().float()
     P, N, M = scores.shape
-    gs = torch.empty_like(scores)
-    ga = torch.empty(P, device=scores.device)
+    gs = _out_or_empty(out[0] if out else None, scores.shape, scores)
+    ga = _out_or_empty(out[1] if out else None, (P,), scores)
     wsb = _lib.dr_sinkhorn_backward_workspace_bytes(P, N, M, int(iters))
     ws = torch.empty(wsb, dtype=torch.uint8, device=scores.device)
     sm, tm = mask_u8(src_mask), mask_u8(tgt_mask)
@@ -1249,24 +1260,24 @@ def fine_loss_backward(img_points, img_feats, pcd_points, pcd_pixels, pcd_feats,
     return gi, gp
 
 
-def dual_softmax(sim, temperature, src_mask=None, tgt_mask=None):
+def dual_softmax(sim, temperature, src_mask=None, tgt_mask=None, out=None):
     """sim [P,N,M] float32 -> conf = softmax_dim1(sim / T | source rows) * softmax_dim2(sim / T | target columns) (matching.py:193-205)"""
     ensure_init()
     sim = sim.contiguous().float()
     P, N, M = sim.shape
-    conf = torch.empty_like(sim)
+    conf = _out_or_empty(out, sim.shape, sim)
     stats = torch.empty(2 * P * M, dtype=torch.float32, device=sim.device)
     sm, tm = mask_u8(src_mask), mask_u8(tgt_mask)
     check(_lib.dr_dual_softmax_f32(P, N, M, ptr(sim), float(temperature), ptr(sm), ptr(tm), ptr(conf), ptr(stats), stream_of(sim)))
     return conf
 
 
-def dual_softmax_backward(sim, temperature, src_mask, tgt_mask, grad_conf):
+def dual_softmax_backward(sim, temperature, src_mask, tgt_mask, grad_conf, out=None):
     """d loss / d sim of conf = dual_softmax(sim, temperature, masks) given d loss / d conf (dr_dual_softmax_backward_f32)"""
     ensure_init()
     sim, grad_conf = sim.contiguous().float(), grad_conf.contiguous().float()
     P, N, M = sim.shape
-    gs = torch.empty_like(sim)
+    gs = _out_or_empty(out, sim.shape, sim)
     nb = _lib.dr_dual_softmax_backward_workspace_bytes(P, N, M)
     ws = torch.empty(nb, dtype=torch.uint8, device=sim.device)
     sm, tm = mask_u8(src_mask), mask_u8(tgt_mask)

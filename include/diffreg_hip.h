@@ -938,7 +938,9 @@ int dr_layernorm_backward_f32(int rows, int C, const float* x, const float* gamm
  * under autograd).  Token layout: q / out / grad_o [B L, ld], k / v [B S, ld], head h in columns [h d, (h + 1) d); masks [B L] / [B S] uint8 (both
  * or none): key j is dead for query l when q_mask[l] && !k_mask[j], as the training forward applies them.  The backward is three launches on the
  * f32-input MFMA (per-query log-sum-exp and delta; dQ by query blocks; dK | dV by key blocks), fixed summation orders (bit-reproducible);
- * workspace: dr_attention_backward_workspace_bytes(B, H, L).  d % 4 == 0, d <= 160. */
+ * workspace: dr_attention_backward_workspace_bytes(B, H, L).  d % 4 == 0, d <= 160 (both ways).  The backward's workgroup is 4 waves up to d = 124,
+ * 3 at d = 128 .. 156 and 2 at d = 160 (the waves' K / V tiles have to fit 160 KiB of LDS); the forward runs 136 < d <= 160 on its 32-query kernel only
+ * (no plane-image operands).  Neither path beyond d = 136 has been timed. */
 int dr_attention_f32(int B, int H, int L, int S, int d, const float* q, const float* k, const float* v, int ld, const uint8_t* q_mask,
                      const uint8_t* k_mask, float scale, float* out, void* stream);
 size_t dr_attention_backward_workspace_bytes(int B, int H, int L);

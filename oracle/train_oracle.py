@@ -120,7 +120,10 @@ def focal_loss_backward(conf, conf_gt, alpha=0.25, gamma=2.0, pos_w=1.0, neg_w=1
     pw = pos_w if pos.any() else 0.0
     nw = neg_w if neg.any() else 0.0
     c = conf
-    live = (c >= 1e-6) & (c <= 1 - 1e-6)
+    # the reference clamps float32 tensors, so its bounds are the FLOAT32 numbers nearest 1e-6 and 1 - 1e-6 (torch casts the scalars to the tensor's
+    # type); an evaluation in float64 on float32 values keeps them: conf == float32(1e-6) = 9.99999997e-07 is inside the clamp
+    lo, hi = float(torch.tensor(1e-6, dtype=torch.float32)), float(torch.tensor(1 - 1e-6, dtype=torch.float32))
+    live = (c >= lo) & (c <= hi)
     dpos = -alpha * (-gamma * (1 - c) ** (gamma - 1) * c.log() + (1 - c) ** gamma / c) * (pw / npos)
     dneg = -alpha * (gamma * c ** (gamma - 1) * (1 - c).log() - c ** gamma / (1 - c)) * (nw / nneg)
     g = torch.where(pos, dpos, torch.where(neg, dneg, torch.zeros_like(c)))
