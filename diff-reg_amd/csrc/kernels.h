@@ -169,5 +169,7 @@ int sinkhorn_f64(int B, int N, int M, const double* scores, const double* shift,
 // call_status: the caller's own sticky status word (device, 4 bytes, zero-initialised by the caller): bit 0 = a co-resident Sinkhorn of THIS
 // caller timed out (set beside the process-wide flag of dr_device_status, so that concurrent engines cannot swallow or misattribute a time-out)
 int sinkhorn_call_status(unsigned* word, hipStream_t st, bool clear);
+// device address of the process-wide sticky word dr_device_status reads (bit 1: an evaluation entry skipped an index outside its range)
+unsigned* device_status_word();
 
 }  // namespace dr

@@ -1183,7 +1183,7 @@ static int launch_grid_cpl(const SkArgs& a, int G, hipStream_t st) {
 // ---------------------------------------------------------------------------------------------
 constexpr int SK_COOP_SHARE = 2;
 constexpr unsigned SK_COOP_SPIN = 1u << 22;
-__device__ unsigned g_sk_status;                                   // sticky: bit 0 = a co-resident Sinkhorn timed out
+__device__ unsigned g_sk_status;                                   // sticky: bit 0 = a co-resident Sinkhorn timed out; bit 1 = eval2d3d.hip skipped an index
 static unsigned g_sk_spin_limit = SK_COOP_SPIN;                    // (dr_debug_sinkhorn_spin_limit: the timeout test)
 
 // arrival flags instead of a counter: a workgroup announces "my stores of pass p have left" by ONE sc1 store of p to its own word
@@ -1829,7 +1829,23 @@ int sinkhorn_device_status(hipStream_t st, bool clear) {
         const unsigned z = 0;
         DR_HIP_CHECK(hipMemcpyToSymbol(HIP_SYMBOL(g_sk_status), &z, sizeof(z)));
     }
-    return (h & 1u) ? DR_ETIMEOUT : DR_OK;
+    if (h & 1u) return DR_ETIMEOUT;
+    return (h & 2u) ? DR_EINVAL : DR_OK;     // bit 1: an evaluation entry skipped an index outside its range (eval2d3d.hip)
+}
+
+// device address of the sticky word above, for kernels of other translation units (cached per device: the first query of a device must not
+// fall inside a stream capture -- dr_init makes it for the device current at its call, the header tells callers about every other one; two
+// threads that race on an empty slot both store the same address)
+unsigned* device_status_word() {
+    static unsigned* cache[64];
+    int d = 0;
+    if (hipGetDevice(&d) != hipSuccess || d < 0 || d >= 64) return nullptr;
+    if (!cache[d]) {
+        void* p = nullptr;
+        if (hipGetSymbolAddress(&p, HIP_SYMBOL(g_sk_status)) != hipSuccess) return nullptr;
+        cache[d] = (unsigned*)p;
+    }
+    return cache[d];
 }
 
 // waits for the stream, reads (and clears) a caller's own sticky word (the loops' per-workspace status)

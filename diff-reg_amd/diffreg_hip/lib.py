@@ -278,6 +278,15 @@ SIGNATURES.update({
     "dr_fine_loss_backward_workspace_bytes": (c_size_t, [c_int, c_int]),
     "dr_fine_loss_backward_f32": (c_int, [c_int] * 4 + [c_void_p] * 8 + [c_int, _P(FineLossParams), c_void_p, c_size_t] + [c_void_p] * 4 +
                                   [c_size_t, c_void_p]),
+    # ABI 0.7.0: the 2D-3D evaluation metrics
+    "dr_sparse_corr_eval_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dr_sparse_corr_eval_i64": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p,
+                                        c_void_p, c_size_t, c_void_p]),
+    "dr_corr_eval_workspace_bytes": (c_size_t, [c_int]),
+    "dr_corr_eval_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t,
+                                 c_void_p]),
+    "dr_registration_eval_workspace_bytes": (c_size_t, [c_int]),
+    "dr_registration_eval_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 })
 
 
@@ -291,7 +300,7 @@ def _bind(table):
 _bind(SIGNATURES)
 _INIT_DONE = False
 
-ABI_VERSION = 600          # DR_ABI_VERSION of the include/diffreg_hip.h these signatures were written against
+ABI_VERSION = 700          # DR_ABI_VERSION of the include/diffreg_hip.h these signatures were written against
 if _lib.dr_version() // 100 != ABI_VERSION // 100:
     raise ImportError("libdiffreg_hip.so is ABI %d, this binding is written against %d: rebuild (make -C diff-reg_amd/csrc)"
                       % (_lib.dr_version(), ABI_VERSION))
@@ -335,7 +344,8 @@ def loop_status(workspace, clear=True):
 def device_status(device=None, clear=True):
     """Waits for the current stream of `device` and raises if a kernel reported a device-side failure since the last check
     (DR_ETIMEOUT: the single-launch Sinkhorn gave up waiting for a workgroup that was not resident; the outputs of that call are
-    unspecified -- the flag is process-wide and sticky: the first reader with clear=True consumes it).
+    unspecified -- the flag is process-wide and sticky: the first reader with clear=True consumes it; DR_EINVAL: an evaluation entry of the
+    2D-3D metrics skipped an index outside its range, where the reference raises an IndexError).
     Called wherever the host mirrors synchronise anyway (match counts)."""
     st = torch.cuda.current_stream(device).cuda_stream
     check(_lib.dr_device_status(c_void_p(st), 1 if clear else 0))
@@ -1412,6 +1422,74 @@ def registration_recall(rot_est, trn_est, rot_gt, trn_gt, info, thr=0.2):
                                           ptr(_f32c(trn_gt, (P, 3))), ptr(d(info, (P, 36))), float(thr), ptr(err), ptr(ok),
                                           stream_of(rot_est)))
     return err, ok
+
+
+# ------------------------------------------------------------------------------------------------
+# evaluation metrics of the 2D-3D model (ABI 0.7.0, csrc/eval2d3d.hip): one pair per call, asynchronous, results stay on the device
+# ------------------------------------------------------------------------------------------------
+def _i64c(x, dev):
+    return torch.as_tensor(x).to(device=dev, dtype=torch.int64).reshape(-1).contiguous()
+
+
+def _t44(x, dev):
+    return torch.as_tensor(x).to(device=dev, dtype=torch.float64).reshape(4, 4).contiguous()
+
+
+def sparse_corr_eval(img_num_nodes, pcd_num_nodes, img_node_corr_indices, pcd_node_corr_indices, gt_img_node_corr_indices,
+                     gt_pcd_node_corr_indices, gt_node_corr_min_overlaps=None, acceptance_overlap=0.0):
+    """-> (out [4] float64: list precision, set precision, recall, hit_ratio; counts [4] int32: unique predictions, unique GT, unique positives,
+    listed positives)   (EvalFunction.evaluate_coarse_matching, EXP/loss.py:247-264; evaluate_sparse_correspondences, registration_utils.py:202-225)"""
+    ensure_init()
+    dev = img_node_corr_indices.device
+    pi, pp = _i64c(img_node_corr_indices, dev), _i64c(pcd_node_corr_indices, dev)
+    gi, gp = _i64c(gt_img_node_corr_indices, dev), _i64c(gt_pcd_node_corr_indices, dev)
+    ov = None if gt_node_corr_min_overlaps is None else _f32c(torch.as_tensor(gt_node_corr_min_overlaps).to(dev), (-1,))
+    out = torch.empty(4, dtype=torch.float64, device=dev)
+    counts = torch.empty(4, dtype=torch.int32, device=dev)
+    wsb = _lib.dr_sparse_corr_eval_workspace_bytes(int(img_num_nodes), int(pcd_num_nodes))
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    check(_lib.dr_sparse_corr_eval_i64(int(img_num_nodes), int(pcd_num_nodes), pi.shape[0], ptr(pi) if pi.shape[0] else None,
+                                       ptr(pp) if pi.shape[0] else None, gi.shape[0], ptr(gi) if gi.shape[0] else None,
+                                       ptr(gp) if gi.shape[0] else None, ptr(ov) if gi.shape[0] else None, float(acceptance_overlap), ptr(out),
+                                       ptr(counts), ptr(ws), wsb, stream_of(out)))
+    return out, counts
+
+
+def corr_eval(pcd_corr_points, img_corr_points, transform, positive_radius, sel_indices=None, depth_mask=False):
+    """-> (out [4] float64: inlier ratio, mean residual, overlap, EvalFunction's (depth-masked) IR; counts [4] int32: inliers, overlapping image
+    points, kept by the mask, inliers among those)   (evaluate_correspondences, registration_utils.py:151-173; evaluate_fine_matching,
+    EXP/loss.py:266-278).  sel_indices int64: the correspondences that take part (None = all)."""
+    ensure_init()
+    dev = pcd_corr_points.device
+    n = pcd_corr_points.shape[0]
+    pc, ic = _f32c(pcd_corr_points, (n, 3)), _f32c(img_corr_points, (n, 3))
+    sel = None if sel_indices is None else _i64c(sel_indices, dev)
+    m = n if sel is None else sel.shape[0]
+    out = torch.empty(4, dtype=torch.float64, device=dev)
+    counts = torch.empty(4, dtype=torch.int32, device=dev)
+    wsb = _lib.dr_corr_eval_workspace_bytes(m)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    if sel is not None and m == 0:                              # an empty selection is not "all of them"
+        n, sel = 0, None
+    check(_lib.dr_corr_eval_f32(n, ptr(pc) if n else None, ptr(ic) if n else None, ptr(_t44(transform, dev)), float(positive_radius), m if sel is not None else 0,
+                                ptr(sel), 1 if depth_mask else 0, ptr(out), ptr(counts), ptr(ws), wsb, stream_of(out)))
+    return out, counts
+
+
+def registration_eval(pcd_points, gt_transform, est_transform, rmse_threshold):
+    """-> (out [4] float64: eval.py's RMSE, EvalFunction's "rmse", RRE in degrees, RTE; recall [2] int32: either one < rmse_threshold)
+    (registration_rmse / isotropic_registration_error, array_ops/metrics.py:25-121; EvalFunction.evaluate_registration, EXP/loss.py:280-294)"""
+    ensure_init()
+    dev = gt_transform.device if pcd_points is None else pcd_points.device
+    N = 0 if pcd_points is None else pcd_points.shape[0]
+    pts = None if N == 0 else _f32c(pcd_points, (N, 3))
+    out = torch.empty(4, dtype=torch.float64, device=dev)
+    recall = torch.empty(2, dtype=torch.int32, device=dev)
+    wsb = _lib.dr_registration_eval_workspace_bytes(N)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    check(_lib.dr_registration_eval_f64(N, ptr(pts), ptr(_t44(gt_transform, dev)), ptr(_t44(est_transform, dev)), float(rmse_threshold), ptr(out),
+                                        ptr(recall), ptr(ws), wsb, stream_of(out)))
+    return out, recall
 
 
 # ------------------------------------------------------------------------------------------------

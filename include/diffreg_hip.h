@@ -44,8 +44,10 @@ extern "C" {
  *   0.5.0  the 2D-3D point backbone: dr_group_norm_stats_f32, dr_group_norm_apply_f32, dr_group_norm_backward_f32, dr_knn_interpolate_f32,
  *          dr_knn_interpolate_backward_f32, dr_kpconv_neighbor_count_f32 and their workspace sizes (new entries only; nothing older changed).
  *   0.6.0  the 2D-3D fine loss: dr_fine_loss_f32, dr_fine_loss_backward_f32, their two size queries and the new struct dr_fine_loss_params
- *          (new entries only; nothing older changed). */
-#define DR_ABI_VERSION 600
+ *          (new entries only; nothing older changed).
+ *   0.7.0  the 2D-3D evaluation metrics: dr_sparse_corr_eval_i64, dr_corr_eval_f32, dr_registration_eval_f64 and their workspace sizes (new
+ *          entries only; dr_device_status can now also return DR_EINVAL: one of these entries skipped an index outside its range). */
+#define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
 const char* dr_last_hip_error(void);  /* text of the last failing HIP call on this thread */
@@ -59,7 +61,11 @@ const char* dr_last_hip_error(void);  /* text of the last failing HIP call on th
  * dr_device_status is the ONE entry point that synchronises: it waits for `stream`, reads the flag (clearing it when `clear`
  * is non-zero) and returns DR_OK or DR_ETIMEOUT.  The host mirrors call it wherever they already synchronise to read a match
  * count.  (The launcher checks residency with the occupancy API and takes the multi-launch form when the launch would not
- * fit beside a second one, so the flag means something else holds the CUs: a foreign kernel, a CU mask, a partitioned device.) */
+ * fit beside a second one, so the flag means something else holds the CUs: a foreign kernel, a CU mask, a partitioned device.)
+ * Since ABI 0.7.0 the same word has a second bit: an evaluation entry (dr_sparse_corr_eval_i64, dr_corr_eval_f32) met an index outside its
+ * range and skipped it, where the reference raises an IndexError -> DR_EINVAL (DR_ETIMEOUT wins when both are set).  Those entries look the
+ * word's device address up once per device (hipGetSymbolAddress, then cached): dr_init does it for the device current at its call; on any other
+ * device make the first call of such an entry OUTSIDE a stream capture. */
 int dr_device_status(void* stream, int clear);
 
 /* ---------------------------------------------------------------------------------------------
@@ -875,6 +881,51 @@ int dr_fine_loss_backward_f32(int HW, int N, int M, int C, const float* img_poin
                               const int64_t* pcd_sel_indices, int image_w, const dr_fine_loss_params* params, const void* saved, size_t saved_bytes,
                               const float* grad_loss, float* grad_img_feats, float* grad_pcd_feats, void* workspace, size_t workspace_bytes,
                               void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 0.7.0: the evaluation metrics of the 2D-3D model (csrc/eval2d3d.hip): the two consumers of MATR2D3D.forward's output dict,
+ * EvalFunction (EXP/loss.py:241-301, after every training and test step) and the offline evaluator (EXP/eval.py:121-200 on
+ * vision3d/array_ops/registration_utils.py:151-225 and array_ops/metrics.py:25-166).  One pair per call; pairs queue on the stream.  Nothing
+ * synchronises or reads back; results go to device memory of the caller.  Double arithmetic on the float32 inputs; no float atomics (integer
+ * atomics on bitmaps and counters only); every sum of reals is a set of per-workgroup double partials added in one fixed order: two runs are
+ * bit-identical.  Transforms are 16 doubles on the device, row-major 4 x 4, last row (0, 0, 0, 1) (not read).
+ *
+ * dr_sparse_corr_eval_i64: K predicted node pairs (img_node_corr_indices, pcd_node_corr_indices) against G ground-truth pairs over an
+ *   img_num_nodes x pcd_num_nodes grid.  gt_node_corr_min_overlaps (float32 [G], or NULL = every GT pair counts): a GT pair counts only where its
+ *   overlap is > acceptance_overlap (torch.gt, loss.py:258).  out (4 doubles): [0] LIST precision = mean over the K listed predictions of GT
+ *   membership (EvalFunction.evaluate_coarse_matching: duplicates count each time; K = 0 -> NaN, torch.mean of nothing); [1] SET precision,
+ *   [2] recall, [3] hit_ratio of evaluate_sparse_correspondences (duplicates count once; denominators + 1e-12; hit_ratio from the row / column
+ *   "any" counts).  counts (4 int32): unique predictions, unique GT, unique positives, listed positives.  No dense float matrix: two bit
+ *   matrices in the workspace (dr_sparse_corr_eval_workspace_bytes; zeroed by the call).  Supported: img_num_nodes * round_up(pcd_num_nodes, 32)
+ *   <= 2^26 (1 530 x 4 096 is 6.3e6; two bit matrices of 8 MiB at the limit) -- DR_ENOSUP beyond.  An index outside [0, img_num_nodes) /
+ *   [0, pcd_num_nodes) (negative ones included: no wrap) is skipped -- it marks nothing and is no listed positive, K stays the list's
+ *   denominator -- and sets bit 1 of the device status word (dr_device_status -> DR_EINVAL).
+ * dr_corr_eval_f32: n fine correspondences (pcd_corr_points, img_corr_points float32 [n,3]), the ground-truth transform (cloud -> camera) and
+ *   positive_radius.  sel_indices (int64 [n_sel], or NULL with n_sel = 0 = all n in order): the correspondences that take part (the wrapper's
+ *   top-num_corr by score, eval.py:121-127); m = n_sel or n of them.  out (4 doubles): [0] inlier ratio (registration_inlier_ratio), [1] mean
+ *   residual (registration_corr_distance), [2] overlap (point_cloud_overlap: for every IMAGE point the distance to the nearest TRANSFORMED CLOUD
+ *   point among the m, mean of < radius -- knn(tgt, src)), [3] EvalFunction.evaluate_fine_matching's IR: with depth_mask != 0 over the
+ *   correspondences whose image point has z > 0, 0 when none remain (nan_to_num_); with depth_mask == 0 over all m.  m = 0 writes eval.py's
+ *   {0, 0, 0} (and [3] = 0).  counts (4 int32): inliers, overlapping image points, correspondences kept by the mask (m without it), inliers among those.
+ *   Brute-force nearest neighbour over LDS tiles: m <= 16 384 (DR_ENOSUP beyond).  A selection outside [0, n) is skipped (no numerator, nobody's
+ *   neighbour; m stays the denominator) and sets the status bit.  workspace: dr_corr_eval_workspace_bytes(m).
+ * dr_registration_eval_f64: pcd_points float32 [N,3], the ground-truth and the estimated transform.  out (4 doubles): [0] eval.py's RMSE
+ *   sqrt(mean |T_gt p - T_est p|^2) (registration_rmse), [1] EvalFunction.evaluate_registration's "rmse" mean |inv(T_gt) T_est p - p| (a true
+ *   inverse of the 3 x 3 block, as torch.linalg.inv), [2] RRE in degrees (acos of (trace(R_est^T R_gt) - 1) / 2 clipped to [-1, 1]), [3] RTE.
+ *   recall (2 int32): out[0] < rmse_threshold, out[1] < rmse_threshold.  N = 0: both means NaN, both flags 0, RRE and RTE as usual.
+ *   Grid-stride double partials (at most 256 workgroups), one-workgroup final.  workspace: dr_registration_eval_workspace_bytes(N). */
+size_t dr_sparse_corr_eval_workspace_bytes(int img_num_nodes, int pcd_num_nodes);
+int dr_sparse_corr_eval_i64(int img_num_nodes, int pcd_num_nodes, int K, const int64_t* img_node_corr_indices,
+                            const int64_t* pcd_node_corr_indices, int G, const int64_t* gt_img_node_corr_indices,
+                            const int64_t* gt_pcd_node_corr_indices, const float* gt_node_corr_min_overlaps, float acceptance_overlap,
+                            double* out, int32_t* counts, void* workspace, size_t workspace_bytes, void* stream);
+size_t dr_corr_eval_workspace_bytes(int m);
+int dr_corr_eval_f32(int n, const float* pcd_corr_points, const float* img_corr_points, const double* transform, double positive_radius,
+                     int n_sel, const int64_t* sel_indices, int depth_mask, double* out, int32_t* counts, void* workspace,
+                     size_t workspace_bytes, void* stream);
+size_t dr_registration_eval_workspace_bytes(int N);
+int dr_registration_eval_f64(int N, const float* pcd_points, const double* gt_transform, const double* est_transform, double rmse_threshold,
+                             double* out, int32_t* recall, void* workspace, size_t workspace_bytes, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Forward half of the training branch: the pieces of Pipeline.forward's
