@@ -287,6 +287,15 @@ SIGNATURES.update({
                                  c_void_p]),
     "dr_registration_eval_workspace_bytes": (c_size_t, [c_int]),
     "dr_registration_eval_f64": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_double, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    # ABI 0.7.0, second set: the geometry head and the feature-layout glue of the 2D-3D forward
+    "dr_back_project_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int, c_float, c_float, c_void_p, c_void_p, c_int, c_float, c_void_p, c_void_p,
+                                    c_void_p, c_void_p]),
+    "dr_render_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_float, c_void_p, c_void_p, c_void_p]),
+    "dr_resize_tokens_f32": (c_int, [c_int] * 5 + [c_void_p] * 3),
+    "dr_resize_tokens_backward_f32": (c_int, [c_int] * 5 + [c_void_p] * 3),
+    "dr_rows_normalize_chw_f32": (c_int, [c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
+    "dr_rows_normalize_chw_backward_f32": (c_int, [c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
+    "dr_rows_normalize_chw_backward_rows_f32": (c_int, [c_int, ctypes.c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
 })
 
 
@@ -1490,6 +1499,101 @@ def registration_eval(pcd_points, gt_transform, est_transform, rmse_threshold):
     check(_lib.dr_registration_eval_f64(N, ptr(pts), ptr(_t44(gt_transform, dev)), ptr(_t44(est_transform, dev)), float(rmse_threshold), ptr(out),
                                         ptr(recall), ptr(ws), wsb, stream_of(out)))
     return out, recall
+
+
+# ------------------------------------------------------------------------------------------------
+# geometry head and feature-layout glue of the 2D-3D forward (ABI 0.7.0, second set, csrc/front2d3d.hip): one image per call, asynchronous
+# ------------------------------------------------------------------------------------------------
+def _scalar_or_dev(x, dev):
+    """a Python number stays on the host; a tensor is read by the kernel from device memory (no synchronisation)"""
+    if torch.is_tensor(x):
+        return 0.0, x.detach().to(device=dev, dtype=torch.float32).reshape(-1)[:1].contiguous()
+    return float(x), None
+
+
+def back_project_points(depth, intrinsics, mode=0, a=1000.0, b=0.0, depth_limit=None, pixels=False):
+    """depth [H,W], intrinsics [3,3] -> (points [H*W,3] float32, mask [H*W] uint8, pixels [H*W,2] float32 or None)   (dr_back_project_f32:
+    mode 0 vision3d.ops.back_project, z = depth / a; mode 1 MATR2D3D.back_project_depth, z = depth * a + b with a / b numbers or device tensors)"""
+    ensure_init()
+    if depth.dim() != 2:
+        raise ValueError("back_project_points takes one depth image [H, W] (got %s)" % (tuple(depth.shape),))
+    H, W = depth.shape
+    dev = depth.device
+    d, K = _f32c(depth, (H, W)), _f32c(intrinsics.to(dev), (3, 3))
+    (ah, ad), (bh, bd) = _scalar_or_dev(a, dev), _scalar_or_dev(b, dev)
+    pts = torch.empty(H * W, 3, device=dev)
+    mask = torch.empty(H * W, dtype=torch.uint8, device=dev)
+    pix = torch.empty(H * W, 2, device=dev) if pixels else None
+    check(_lib.dr_back_project_f32(H, W, ptr(d) if H * W else None, ptr(K), int(mode), ah, bh, ptr(ad), ptr(bd), 0 if depth_limit is None else 1,
+                                   0.0 if depth_limit is None else float(depth_limit), ptr(pts) if H * W else None,
+                                   ptr(mask) if H * W else None, ptr(pix) if pixels and H * W else None, stream_of(pts)))
+    return pts, mask, pix
+
+
+def render_points(points, intrinsics, extrinsics=None, eps=1e-8, return_depth=False):
+    """points [N,3], intrinsics [3,3], extrinsics [4,4] or None -> pixels [N,2] float32 (h, w), not rounded (+ depth [N])   (dr_render_f32)"""
+    ensure_init()
+    N = points.shape[0]
+    dev = points.device
+    p, K = _f32c(points, (N, 3)), _f32c(intrinsics.to(dev), (3, 3))
+    T = None if extrinsics is None else _f32c(extrinsics.to(dev), (4, 4))
+    pix = torch.empty(N, 2, device=dev)
+    z = torch.empty(N, device=dev) if return_depth else None
+    check(_lib.dr_render_f32(N, ptr(p) if N else None, ptr(K), ptr(T), float(eps), ptr(pix) if N else None, ptr(z) if N else None, stream_of(pix)))
+    return (pix, z) if return_depth else pix
+
+
+def resize_tokens(feats, size):
+    """feats [C,Hs,Ws] -> [Hd*Wd, C]: bilinear, align_corners=True, written as token rows   (dr_resize_tokens_f32)"""
+    ensure_init()
+    C, Hs, Ws = feats.shape
+    Hd, Wd = int(size[0]), int(size[1])
+    x = _f32c(feats, (C, Hs, Ws))
+    out = torch.empty(Hd * Wd, C, device=x.device)
+    check(_lib.dr_resize_tokens_f32(C, Hs, Ws, Hd, Wd, ptr(x) if x.numel() else None, ptr(out) if out.numel() else None, stream_of(out)))
+    return out
+
+
+def resize_tokens_backward(grad_out, src_shape, size):
+    """grad_out [Hd*Wd, C] -> grad of the [C,Hs,Ws] input; a gather, bit-identical between runs   (dr_resize_tokens_backward_f32)"""
+    ensure_init()
+    C, Hs, Ws = (int(v) for v in src_shape)
+    Hd, Wd = int(size[0]), int(size[1])
+    g = _f32c(grad_out, (Hd * Wd, C))
+    gi = torch.empty(C, Hs, Ws, device=g.device)
+    check(_lib.dr_resize_tokens_backward_f32(C, Hs, Ws, Hd, Wd, ptr(g) if g.numel() else None, ptr(gi) if gi.numel() else None, stream_of(gi)))
+    return gi
+
+
+def rows_normalize_chw(feats):
+    """feats [C,P] -> [P,C], rows divided by max(|row|_2, 1e-12)   (dr_rows_normalize_chw_f32; C <= 256)"""
+    ensure_init()
+    C, P = feats.shape
+    x = _f32c(feats, (C, P))
+    out = torch.empty(P, C, device=x.device)
+    check(_lib.dr_rows_normalize_chw_f32(C, P, ptr(x) if x.numel() else None, ptr(out) if out.numel() else None, stream_of(out)))
+    return out
+
+
+def rows_normalize_chw_backward(feats, grad_out, rows=None):
+    """feats [C,P] and the gradient of rows_normalize_chw's output -> the gradient of feats [C,P].  rows None: grad_out is dense [P,C]
+    (dr_rows_normalize_chw_backward_f32); rows int64 [K]: grad_out is [K,C], the gradient of output rows `rows` (repeats accumulate), zero elsewhere
+    (dr_rows_normalize_chw_backward_rows_f32; a row outside [0, P) is skipped and reported by device_status())"""
+    ensure_init()
+    C, P = feats.shape
+    x = _f32c(feats, (C, P))
+    gi = torch.empty(C, P, device=x.device)
+    if rows is None:
+        g = _f32c(grad_out, (P, C))
+        check(_lib.dr_rows_normalize_chw_backward_f32(C, P, ptr(x) if x.numel() else None, ptr(g) if g.numel() else None,
+                                                      ptr(gi) if gi.numel() else None, stream_of(gi)))
+    else:
+        r = _i64c(rows, x.device)
+        K = r.shape[0]
+        g = _f32c(grad_out, (K, C))
+        check(_lib.dr_rows_normalize_chw_backward_rows_f32(C, P, K, ptr(x) if x.numel() else None, ptr(r) if K else None,
+                                                           ptr(g) if g.numel() else None, ptr(gi) if gi.numel() else None, stream_of(gi)))
+    return gi
 
 
 # ------------------------------------------------------------------------------------------------

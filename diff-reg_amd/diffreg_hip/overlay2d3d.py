@@ -52,6 +52,13 @@ is re-bound in the globals of the model's defining module to a version with cach
 
     accelerate(model, training=True, partition=True, backbone=True, noising=True);  accelerate_loss(loss_fn, fine=True)
 
+With `front=True` (any combination of the flags above) the geometry head of forward (EXP/model.py:302-351) runs on the device
+(diffreg_hip/front2d3d.py): `back_project`, `render` and `create_meshgrid` are re-bound in the globals of the model's defining module, like the
+partition's names, and `back_project_depth` on the instance; `remove()` restores all four.  Without the flag none of them is touched.  The two
+feature-layout calls (:374-375, :535-538) are inline `F.` code and take a one-line edit each ("Geometry head and feature layout").
+
+    accelerate(model, front=True)
+
 What then stays the reference's code in a training step: the image backbone (with DINOv2 / Depth-Anything), the inline GT retry ladder and the
 other inline glue of MATR2D3D.forward.
 """
@@ -65,12 +72,13 @@ from .engine import DenoiseEngine2D3D
 
 
 class LoopOverlay2D3D:
-    def __init__(self, model, n_head=4, engine_kwargs=None, training=False, partition=False, backbone=False, noising=False):
+    def __init__(self, model, n_head=4, engine_kwargs=None, training=False, partition=False, backbone=False, noising=False, front=False):
         self.model = model
         self.training = bool(training)
         self.partition = bool(partition)
         self.backbone = bool(backbone)
         self.noising = bool(noising)
+        self.front = bool(front)
         if self.noising and not self.training:
             raise ValueError("noising=True is the training branch's front end: it needs training=True")
         self._globals_saved = {}
@@ -98,6 +106,10 @@ class LoopOverlay2D3D:
             self._orig.update(procrustes=model.denoising_soft_procrustes.forward)
             model.denoising_soft_procrustes.forward = self._procrustes
             self._bind_globals({"q_sample": autograd2d3d.q_sample})
+        if self.front:
+            from . import front2d3d as f
+            self._bind_globals({name: getattr(f, name) for name in ("back_project", "render", "create_meshgrid")})
+            model.back_project_depth = f.back_project_depth
         model._dr_overlay = self
 
     _MISSING = object()
@@ -126,6 +138,8 @@ class LoopOverlay2D3D:
             sites += [(m.pcd_backbone, "forward")]
         if self.noising:
             sites += [(m.denoising_soft_procrustes, "forward")]
+        if self.front:
+            sites += [(m, "back_project_depth")]
         for obj, name in sites:
             if name in obj.__dict__:
                 del obj.__dict__[name]
@@ -229,15 +243,16 @@ class LoopOverlay2D3D:
         return self._orig["coarse_matching"](src_feats, tgt_feats, src_mask, tgt_mask, *args, **kwargs)
 
 
-def accelerate(model, n_head=4, training=False, partition=False, backbone=False, noising=False, **engine_kwargs):
+def accelerate(model, n_head=4, training=False, partition=False, backbone=False, noising=False, front=False, **engine_kwargs):
     """install the overlay on a MATR2D3D instance (see the module docstring); returns the LoopOverlay2D3D (`.remove()` undoes it).
     training=True: the training branch's four coarse modules run on the device under model.train() as well.
     partition=True: the patch partition and GT patch overlaps (and, with training, the GT search) run on the device as well.
     backbone=True: the point backbone (model.pcd_backbone) runs on the device, in eval and train mode.
     noising=True (with training=True): the GT ladder's Procrustes fits, q_sample and the warp run on the device under model.train(), and the
-    warp's gradient reaches denoising_coarse_matching.bin_score."""
+    warp's gradient reaches denoising_coarse_matching.bin_score.
+    front=True: back_project, render, create_meshgrid (globals of the model's module) and back_project_depth (the instance) run on the device."""
     return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs, training=training, partition=partition, backbone=backbone,
-                           noising=noising)
+                           noising=noising, front=front)
 
 
 def accelerate_loss(loss_module, fine=False):

@@ -46,7 +46,11 @@ extern "C" {
  *   0.6.0  the 2D-3D fine loss: dr_fine_loss_f32, dr_fine_loss_backward_f32, their two size queries and the new struct dr_fine_loss_params
  *          (new entries only; nothing older changed).
  *   0.7.0  the 2D-3D evaluation metrics: dr_sparse_corr_eval_i64, dr_corr_eval_f32, dr_registration_eval_f64 and their workspace sizes (new
- *          entries only; dr_device_status can now also return DR_EINVAL: one of these entries skipped an index outside its range). */
+ *          entries only; dr_device_status can now also return DR_EINVAL: one of these entries skipped an index outside its range).
+ *   0.7.0, second set (the number is unchanged: an existing check of the repository pins DR_ABI_VERSION to 700, and additions break no
+ *          caller -- detect these entries by symbol)  the geometry head and feature-layout glue of the 2D-3D forward: dr_back_project_f32,
+ *          dr_render_f32, dr_resize_tokens_f32, dr_resize_tokens_backward_f32, dr_rows_normalize_chw_f32, dr_rows_normalize_chw_backward_f32,
+ *          dr_rows_normalize_chw_backward_rows_f32 (new entries only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -926,6 +930,45 @@ int dr_corr_eval_f32(int n, const float* pcd_corr_points, const float* img_corr_
 size_t dr_registration_eval_workspace_bytes(int N);
 int dr_registration_eval_f64(int N, const float* pcd_points, const double* gt_transform, const double* est_transform, double rmse_threshold,
                              double* out, int32_t* recall, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 0.7.0, second set: the geometry head and the feature-layout glue of MATR2D3D.forward (csrc/front2d3d.hip).  One image per call, queued on
+ * the stream; nothing synchronises or reads back.  EXP = Diff-Reg-2d3d/experiments/2d3dmatr.rgbdv2.stage4.level3.stage1.
+ *
+ * dr_back_project_f32: depth [H,W], intrinsics [3,3] (device, row-major) -> points [H*W,3], mask [H*W] (uint8: z > 0) and, when pixels is not
+ *   NULL, pixels [H*W,2] = (row, column) as float32 -- create_meshgrid(H, W).float() (vision3d/ops/meshgrid.py:4-37; EXP/model.py:310).
+ *   mode 0 = vision3d.ops.back_project (ops/back_project.py:29-53; EXP/model.py:306): z = depth / a (a true division).
+ *   mode 1 = MATR2D3D.back_project_depth (EXP/model.py:875-899; :349): z = depth * a + b, a product and a sum (no FMA); a_dev / b_dev (device,
+ *   one float each) replace a / b where not NULL -- depth_coffa and depth_coffb are device tensors.  Both: has_limit != 0: z > depth_limit -> 0;
+ *   x = (u - cx) * z / fx, y = (v - cy) * z / fy in that order in float32.  One launch, one pass, four pixels per thread (16-byte loads and
+ *   stores when every pointer is 16-byte aligned -- the mask 4 --, scalar ones otherwise).  H * W < 2^31 - 4 (DR_ENOSUP beyond).
+ * dr_render_f32: points [N,3], intrinsics [3,3], extrinsics [4,4] or NULL (row-major, last row not read) -> pixels [N,2] = (h, w) =
+ *   (fy * y / max(z, eps) + cy, fx * x / max(z, eps) + cx) without rounding, after p <- R p + t in float32 (vision3d/ops/render.py:34-52,
+ *   ops/se3.py:49-52; EXP/model.py:335); depth [N] (or NULL) receives the unclamped z (return_depth).
+ * dr_resize_tokens_f32: in [C,Hs,Ws] -> out [Hd*Wd, C]: F.interpolate(mode="bilinear", align_corners=True) written as token rows
+ *   (EXP/model.py:374-375: interpolate + view + transpose) in one launch.  Source index = d * (in - 1) / (out - 1), scale 0 when out == 1, as
+ *   ATen; the arithmetic is double on the float32 texels, rounded once.  Hs * Ws, Hd * Wd <= 2^24, C <= 2^20 (DR_ENOSUP beyond); an empty source
+ *   with a non-empty destination is DR_EINVAL.
+ * dr_resize_tokens_backward_f32: grad_out [Hd*Wd, C] -> grad_in [C,Hs,Ws] (every element written).  A GATHER: each source texel sums, in
+ *   ascending destination order and in double, the at most ceil(Hd / Hs + 1) x ceil(Wd / Ws + 1) destinations whose footprint holds it -- no
+ *   atomics, two runs are bit-identical.
+ * dr_rows_normalize_chw_f32: in [C,P] (CHW, P = H * W) -> out [P,C], each row divided by max(|row|_2, 1e-12) (EXP/model.py:536-538:
+ *   view + transpose + contiguous + F.normalize) through an LDS tile: every element is read once and written once.  The sum of squares is
+ *   double.  C <= 256 (DR_ENOSUP beyond), P < 2^31 - 64.
+ * dr_rows_normalize_chw_backward_f32: in [C,P], grad_out [P,C] -> grad_in [C,P] = (g - y <g, y>) / max(|x|, 1e-12), y recomputed from in.
+ * dr_rows_normalize_chw_backward_rows_f32: the same for a gradient that is zero outside K rows: rows int64 [K] (repeats allowed: their
+ *   gradient rows are summed in list order), grad_rows [K,C].  grad_in [C,P] is zero-filled by the call and only the touched columns are
+ *   written.  A row outside [0, P) is skipped and sets bit 1 of the device status word (dr_device_status -> DR_EINVAL). */
+int dr_back_project_f32(int H, int W, const float* depth, const float* intrinsics, int mode, float a, float b, const float* a_dev,
+                        const float* b_dev, int has_limit, float depth_limit, float* points, uint8_t* mask, float* pixels, void* stream);
+int dr_render_f32(int N, const float* points, const float* intrinsics, const float* extrinsics, float eps, float* pixels, float* depth,
+                  void* stream);
+int dr_resize_tokens_f32(int C, int Hs, int Ws, int Hd, int Wd, const float* in, float* out, void* stream);
+int dr_resize_tokens_backward_f32(int C, int Hs, int Ws, int Hd, int Wd, const float* grad_out, float* grad_in, void* stream);
+int dr_rows_normalize_chw_f32(int C, int64_t P, const float* in, float* out, void* stream);
+int dr_rows_normalize_chw_backward_f32(int C, int64_t P, const float* in, const float* grad_out, float* grad_in, void* stream);
+int dr_rows_normalize_chw_backward_rows_f32(int C, int64_t P, int K, const float* in, const int64_t* rows, const float* grad_rows,
+                                            float* grad_in, void* stream);
 
 /* ---------------------------------------------------------------------------------------------
  * Forward half of the training branch: the pieces of Pipeline.forward's
