@@ -1,6 +1,8 @@
-// api.hip -- version / error reporting of the C ABI.
+// api.hip -- the parts of the C ABI that stand on their own: version / error reporting, profiling, dr_init and the debug setters, and the
+// entries of the individual ops (position code, linear / batched GEMM, Procrustes, top-1 read-out) -- thin argument checks in front of
+// the launch interface of kernels.h.
 #include <stdlib.h>
-#include "kernels.h"
+#include "loop_common.h"
 #include <vector>
 #include <stdio.h>
 #include <string.h>
@@ -99,3 +101,116 @@ const char* dr_strerror(int code) {
 
 const char* dr_last_hip_error(void) { return dr::g_hip_err; }
 }
+
+using namespace dr;
+
+extern "C" {
+
+int dr_init(void) {
+    int rc = attention_configure();
+    if (rc == DR_OK) rc = gemm_configure();
+    if (rc == DR_OK) rc = pgemm_configure();
+    if (rc == DR_OK && !device_status_word()) rc = DR_ELAUNCH;       // resolved here, outside any stream capture (eval2d3d.hip)
+    return rc;
+}
+
+/* diagnostics for tools/ and tests: force the GEMM tile configuration (-1 auto, 0, 9, 11, 12), run the internal problem form */
+void dr_debug_enable_env(int on) { enable_env_knobs(on != 0); }
+void dr_debug_gemm_config(int c) { gemm_force_config(c); }
+
+int dr_debug_gemm_f32(const dr_debug_gemm_problem* problems, int n, void* stream) {
+    if (!problems || n < 1 || n > 4) return DR_EINVAL;
+    GemmBatch g;
+    memset(&g, 0, sizeof(g));
+    for (int i = 0; i < n; ++i) {
+        const dr_debug_gemm_problem& q = problems[i];
+        const int K1 = q.A2 ? q.K1 : q.K;
+        if (q.rows < 0 || q.ncols <= 0 || q.K <= 0 || !q.A || !q.W || !q.out || q.nbatch < 0) return DR_EINVAL;
+        if (q.lda < K1 || q.ldo < q.ncols || (q.A2 && (K1 <= 0 || K1 >= q.K || q.lda2 < q.K - K1))) return DR_EINVAL;
+        if ((q.epilogue & ~(EPI_RELU | EPI_ROTARY)) ||
+            ((q.epilogue & EPI_ROTARY) && (!q.cos_t || !q.sin_t || q.rot_C <= 0 || (q.rot_C & 1))))
+            return DR_EINVAL;
+        GemmProblem& p = g.p[i];
+        p.A = q.A; p.A2 = q.A2; p.W = q.W; p.out = q.out; p.cosT = q.cos_t; p.sinT = q.sin_t; p.bias = q.bias; p.addend = q.addend;
+        p.rows = q.rows; p.ncols = q.ncols; p.K = q.K; p.K1 = K1; p.lda = q.lda; p.lda2 = q.A2 ? q.lda2 : 0; p.ldo = q.ldo;
+        p.epi = q.epilogue; p.rot_C = q.rot_C; p.scale = q.scale;
+        p.nbatch = q.nbatch; p.sA = q.stride_a; p.sW = q.stride_w; p.sO = q.stride_o;
+    }
+    g.n = n;
+    return launch_gemm(g, (hipStream_t)stream);
+}
+void dr_debug_attention_config(int flash_min_workgroups) { attention_force_flash_min(flash_min_workgroups); }
+void dr_debug_attention_split(int on) { attention_force_split(on); }
+
+int dr_vol_pe_f32(int rows, int rows_per_pair, int C, const float* xyz, const float* R, const float* t, float origin_x,
+                  float origin_y, float origin_z, float voxel, const float* freq, float* cos_out, float* sin_out,
+                  void* stream) {
+    if (rows < 0 || C <= 0 || !xyz || !freq || !cos_out || !sin_out || rows_per_pair < 1) return DR_EINVAL;
+    if ((R == nullptr) != (t == nullptr)) return DR_EINVAL;
+    return launch_vol_pe(xyz, rows, rows_per_pair, R, t, C, origin_x, origin_y, origin_z, voxel, freq, cos_out, sin_out,
+                         (hipStream_t)stream);
+}
+
+int dr_linear_f32(int rows, int ncols, int K, const float* x, const float* W, float* out, int epilogue, const float* cos_t,
+                  const float* sin_t, int rot_C, float scale, void* stream) {
+    if (rows < 0 || ncols <= 0 || K <= 0 || !x || !W || !out) return DR_EINVAL;
+    if ((epilogue & EPI_ROTARY) && (!cos_t || !sin_t || rot_C <= 0 || (rot_C & 1))) return DR_EINVAL;
+    return gemm1(x, K, W, nullptr, out, ncols, rows, ncols, K, epilogue, scale, nullptr, (hipStream_t)stream, cos_t, sin_t, rot_C);
+}
+
+int dr_gemm_nt_batched_f32(int nbatch, int rows, int ncols, int K, const float* A, long long stride_a, const float* W, long long stride_w, float* out,
+                           long long stride_o, float scale, void* stream) {
+    if (nbatch < 0 || rows < 0 || ncols <= 0 || K <= 0 || (K & 3) || !A || !W || !out) return DR_EINVAL;
+    if (nbatch == 0 || rows == 0) return DR_OK;
+    return gemm1(A, K, W, nullptr, out, ncols, rows, ncols, K, EPI_NONE, scale, nullptr, (hipStream_t)stream, nullptr, nullptr, 0, nbatch, stride_a,
+                 stride_w, stride_o);
+}
+
+int dr_linear_ex_f32(int rows, int ncols, int K, const float* x, int lda, const float* W, const float* bias, float* out, int ldo,
+                     int epilogue, float scale, void* stream) {
+    if (rows < 0 || ncols <= 0 || K <= 0 || !x || !W || !out || lda < K || ldo < ncols || (epilogue & EPI_ROTARY)) return DR_EINVAL;
+    return gemm1(x, lda, W, bias, out, ldo, rows, ncols, K, epilogue, scale, nullptr, (hipStream_t)stream);
+}
+
+size_t dr_procrustes_workspace_bytes(int P, int N, int M) {
+    return (P < 1 || N < 1 || M < 1) ? 0 : procrustes_workspace_bytes(P, N, M);
+}
+
+int dr_procrustes_f32(int P, int N, int M, const float* conf, const float* src_pcd, const float* tgt_pcd,
+                      const uint8_t* src_mask, const uint8_t* tgt_mask, int use_mask_len, float sample_rate,
+                      float max_condition_num, float* R, float* t, float* R_forwd, float* t_forwd, double* condition,
+                      int32_t* solution_mask, int32_t* topk_idx, void* workspace, size_t workspace_bytes, void* stream) {
+    if (P < 0 || N < 1 || M < 1 || !conf || !src_pcd || !tgt_pcd || !R || !t || !R_forwd || !t_forwd || !condition || !solution_mask)
+        return DR_EINVAL;
+    if (P == 0) return DR_OK;
+    // tiles beyond 256 x 256 select with the whole chip: the caller's scratch (header contract: the caller owns every buffer)
+    const size_t wsb = procrustes_workspace_bytes(P, N, M);
+    if (wsb && (!workspace || workspace_bytes < wsb)) return DR_EWORKSPACE;
+    return launch_procrustes(conf, src_pcd, tgt_pcd, src_mask, tgt_mask, P, N, M, use_mask_len, sample_rate, max_condition_num,
+                             R, t, R_forwd, t_forwd, condition, solution_mask, topk_idx, (hipStream_t)stream, wsb ? workspace : nullptr, wsb);
+}
+
+size_t dr_top1_union_workspace_bytes(int P, int N, int M, int elem_bytes) {
+    return (P < 1 || N < 1 || M < 1 || (elem_bytes != 4 && elem_bytes != 8)) ? 0 : top1_union_workspace_bytes(P, N, M, (size_t)elem_bytes);
+}
+
+}  // extern "C"
+template <typename T>
+static int top1_union_entry(const T* conf, int P, int N, int M, int64_t* matches, int32_t* count, void* ws, size_t ws_bytes, hipStream_t st) {
+    if (P < 0 || N < 1 || M < 1 || !conf || !matches || !count) return DR_EINVAL;
+    if (P == 0) return DR_OK;
+    const size_t wsb = top1_union_workspace_bytes(P, N, M, sizeof(T));
+    if (wsb && (!ws || ws_bytes < wsb)) return DR_EWORKSPACE;
+    return launch_top1_union<T>(conf, P, N, M, (long long*)matches, count, st, nullptr, nullptr, wsb ? ws : nullptr, wsb);
+}
+extern "C" {
+int dr_top1_union_f64(int P, int N, int M, const double* conf, int64_t* matches, int32_t* count, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+    return top1_union_entry<double>(conf, P, N, M, matches, count, workspace, workspace_bytes, (hipStream_t)stream);
+}
+int dr_top1_union_f32(int P, int N, int M, const float* conf, int64_t* matches, int32_t* count, void* workspace, size_t workspace_bytes,
+                      void* stream) {
+    return top1_union_entry<float>(conf, P, N, M, matches, count, workspace, workspace_bytes, (hipStream_t)stream);
+}
+
+}  // extern "C"

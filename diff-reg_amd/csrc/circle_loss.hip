@@ -204,15 +204,15 @@ struct CircleWs {
     double *la_r, *lb_r, *la_c, *lb_c, *cr, *cc;
     int *rm, *cm;
     static size_t carve(void* buf, CircleWs& w, int M, int N, int C) {
-        Carve c(buf);
+        Carver c(buf);
         const size_t MN = (size_t)M * N, M4 = up4(M), N4 = up4(N);
-        w.S = c.take(MN); w.Omin = c.take(MN); w.Omax = c.take(MN); w.A = c.take(MN); w.Bn = c.take(MN);
-        w.G = c.take((size_t)M * N4); w.GT = c.take((size_t)N * M4); w.Timg = c.take((size_t)C * M4); w.Tpcd = c.take((size_t)C * N4);
-        w.flags = reinterpret_cast<uint8_t*>(c.take((MN + 3) / 4));
-        w.la_r = reinterpret_cast<double*>(c.take(2 * (size_t)M)); w.lb_r = reinterpret_cast<double*>(c.take(2 * (size_t)M));
-        w.la_c = reinterpret_cast<double*>(c.take(2 * (size_t)N)); w.lb_c = reinterpret_cast<double*>(c.take(2 * (size_t)N));
-        w.cr = reinterpret_cast<double*>(c.take(2 * (size_t)M)); w.cc = reinterpret_cast<double*>(c.take(2 * (size_t)N));
-        w.rm = reinterpret_cast<int*>(c.take(M)); w.cm = reinterpret_cast<int*>(c.take(N));
+        w.S = c.take<float>(MN); w.Omin = c.take<float>(MN); w.Omax = c.take<float>(MN); w.A = c.take<float>(MN); w.Bn = c.take<float>(MN);
+        w.G = c.take<float>((size_t)M * N4); w.GT = c.take<float>((size_t)N * M4); w.Timg = c.take<float>((size_t)C * M4); w.Tpcd = c.take<float>((size_t)C * N4);
+        w.flags = reinterpret_cast<uint8_t*>(c.take<float>((MN + 3) / 4));
+        w.la_r = reinterpret_cast<double*>(c.take<float>(2 * (size_t)M)); w.lb_r = reinterpret_cast<double*>(c.take<float>(2 * (size_t)M));
+        w.la_c = reinterpret_cast<double*>(c.take<float>(2 * (size_t)N)); w.lb_c = reinterpret_cast<double*>(c.take<float>(2 * (size_t)N));
+        w.cr = reinterpret_cast<double*>(c.take<float>(2 * (size_t)M)); w.cc = reinterpret_cast<double*>(c.take<float>(2 * (size_t)N));
+        w.rm = reinterpret_cast<int*>(c.take<float>(M)); w.cm = reinterpret_cast<int*>(c.take<float>(N));
         return c.off + 256;
     }
 };

@@ -6,7 +6,7 @@
 // bitonic sort of (key, index) pairs per call, segment heads + scan, and for the neighbours a 27-cell sweep over the supports
 // sorted by cell.  No host synchronisation, no atomics on floats: every float32 sum runs in the reference's order, so the
 // barycentres are bit-exact.
-#include "kernels.h"
+#include "loop_common.h"
 
 // float32 arithmetic below restates the C++ expression by expression (the reference is built without FMA contraction)
 #pragma clang fp contract(off)
@@ -413,7 +413,6 @@ __global__ __launch_bounds__(64) void radius_query_kernel(NbArgs A) {
     }
 }
 
-static size_t align256(size_t x) { return (x + 255) & ~(size_t)255; }
 
 }  // namespace dr
 

@@ -7,7 +7,7 @@
 // (the selection between them is dr_mutual_topk_select_f32, stateops.hip).  Off the hot path: small, memory- / latency-bound
 // kernels; unique_i64 = the bitonic (key, index) sort of collate.hip + a one-workgroup ordered compaction of the segment heads.
 #include <cstring>
-#include "kernels.h"
+#include "loop_common.h"
 
 namespace dr {
 namespace {
@@ -124,7 +124,6 @@ __global__ __launch_bounds__(256) void corr_gather_kernel(const int* __restrict_
     if (lane < 2) { o_img_pix[2 * c + lane] = img_pixels[2 * ii + lane]; o_pcd_pix[2 * c + lane] = pcd_pixels[2 * pj + lane]; }
 }
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 }  // namespace
 }  // namespace dr

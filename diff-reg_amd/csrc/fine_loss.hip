@@ -326,9 +326,9 @@ struct FineSaved {
     double *la, *lb, *coef;
     int* flags;
     static size_t carve(void* buf, FineSaved& w, int M) {
-        Carve c(buf);
-        w.la = reinterpret_cast<double*>(c.take(4 * (size_t)M)); w.lb = reinterpret_cast<double*>(c.take(4 * (size_t)M));
-        w.coef = reinterpret_cast<double*>(c.take(4 * (size_t)M)); w.flags = reinterpret_cast<int*>(c.take(2 * (size_t)M));
+        Carver c(buf);
+        w.la = reinterpret_cast<double*>(c.take<float>(4 * (size_t)M)); w.lb = reinterpret_cast<double*>(c.take<float>(4 * (size_t)M));
+        w.coef = reinterpret_cast<double*>(c.take<float>(4 * (size_t)M)); w.flags = reinterpret_cast<int*>(c.take<float>(2 * (size_t)M));
         return c.off + 256;
     }
 };
@@ -402,8 +402,8 @@ int dr_fine_loss_backward_f32(int HW, int N, int M, int C, const float* img_poin
     FineIn in; FineArgs a; FineSaved w;
     fine_fill(in, a, HW, N, M, C, img_points, img_feats, pcd_points, pcd_pixels, pcd_feats, transform, img_sel_pixels, pcd_sel_indices, image_w, params);
     FineSaved::carve(const_cast<void*>(saved), w, M);
-    Carve cv(workspace);
-    float* Gc = cv.take(2 * (size_t)M * C);
+    Carver cv(workspace);
+    float* Gc = cv.take<float>(2 * (size_t)M * C);
     hipStream_t st = (hipStream_t)stream;
     DR_HIP_CHECK(hipMemsetAsync(grad_img_feats, 0, (size_t)HW * C * sizeof(float), st));
     DR_HIP_CHECK(hipMemsetAsync(grad_pcd_feats, 0, (size_t)N * C * sizeof(float), st));

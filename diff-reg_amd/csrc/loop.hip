@@ -1,29 +1,16 @@
-// loop.hip -- host-side orchestration of the reverse-diffusion matching loop and the public
-// entry points of the individual ops.  Everything is enqueued on the caller's stream; there is no
-// host synchronisation anywhere, so the whole loop can be captured in a HIP graph.
+// loop.hip -- host-side orchestration of the 3D / 4D reverse-diffusion matching loop: the attention layer on both GEMM paths, the
+// denoiser + matching head, and the entries that need them (dr_attention_layer_*, dr_loop_prepack*, dr_denoiser_match_f32,
+// dr_denoise_loop*).  The steps themselves are reverse_sampling() of loop_common.h, shared with loop2d3d.hip; the entries of the
+// individual ops live in api.hip.  Everything is enqueued on the caller's stream; there is no host synchronisation anywhere, so the
+// whole loop can be captured in a HIP graph.
 //
 // Token layout: all src superpoints of all P pairs, then all tgt superpoints:
 //   rows [0, P*N) = src (pair p at p*N), rows [P*N, P*(N+M)) = tgt (pair p at P*N + p*M).
 // Linear layers / LayerNorm / rotary are row-wise, so the P pairs simply widen the GEMMs; only the
 // attention, the N x M matrices and the Procrustes fit know about pair boundaries.
-#include "kernels.h"
-#include "pgemm.h"
-#include <string.h>
+#include "loop_common.h"
 
 namespace dr {
-
-struct Carver {
-    char* base;
-    size_t off, cap;
-    Carver(void* p, size_t c) : base((char*)p), off(0), cap(c) {}
-    template <typename T>
-    T* take(size_t n) {
-        off = (off + 255) & ~(size_t)255;
-        T* r = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += n * sizeof(T);
-        return r;
-    }
-};
 
 // buffers of one attention-layer evaluation over `T` token rows
 struct LayerWs {
@@ -62,7 +49,7 @@ struct Prepack {
     static bool wide_layout(const dr_loop_config& cfg) { return pgemm_bn(cfg.C) > 448 && env_knob("DR_PG_WIDE", 1) != 0; }
     // lays the images out in `buf` (nullptr: size only) and returns the byte count
     static size_t carve(void* buf, const dr_loop_config& cfg, Prepack* pp) {
-        Carver c(buf, (size_t)-1);
+        Carver c(buf);
         const int C = cfg.C, d = C / cfg.H, dp = (d + 15) / 16 * 16, nC = C / 16;
         if (pp) pp->dp = dp;
         auto take = [&](int nblk, int nct, PgW* v) {
@@ -119,11 +106,6 @@ struct Prepack {
     }
 };
 
-// a token tensor of the plane path: fp32 rows [T, C] (the residual stream; may be null), plane image (src part, then tgt
-// part, each padded to 128 rows) and per-row bounds [T]
-struct Tok {
-    float* f32; char* img; float* bnd;
-};
 struct PlanesWs {
     bool on;
     Tok feat0, fa, fb, tgt_l0;
@@ -141,13 +123,7 @@ struct PlanesWs {
     static size_t img_bytes(int PN, int PM, int K) { return plane_image_bytes(PN, K) + plane_image_bytes(PM, K); }
     static void carve(Carver& c, PlanesWs& w, const dr_loop_config& cfg, int P, int N, int M) {
         const int C = cfg.C, PN = P * N, PM = P * M, T = PN + PM;
-        // (crossover re-measured with the 64-row plane workgroups, tools/bench_planes_threshold.py: 256-point pairs 24.5 / 37.7 ms on the
-        //  f32 kernels against 31.6 / 31.9 ms on the plane path at 2048 / 4096 token rows; 512-point 4D pairs 60.9 vs 62.0 ms at 4096)
-        const int min_rows = env_knob("DR_PLANES_MIN_ROWS", 4096);
-        const int enabled = env_knob("DR_PLANES", 1);
-        w.on = enabled && Prepack::supported(cfg) && T >= min_rows;
-        if (cfg.flags & DR_LOOP_PLANES_FORCE) w.on = Prepack::supported(cfg);
-        if (cfg.flags & DR_LOOP_PLANES_OFF) w.on = false;
+        w.on = planes_wanted(cfg.flags, Prepack::supported(cfg), T);
         if (!w.on) return;
         const int dp = (C / cfg.H + 15) / 16 * 16;
         w.side_C = plane_image_bytes(PN, C); w.side_att = plane_image_bytes(PN, cfg.H * dp); w.side_hid = plane_image_bytes(PN, 2 * C);
@@ -168,10 +144,6 @@ struct PlanesWs {
         w.xk_flags = xk ? c.take<unsigned>(pgemm_xk_flag_bytes() / 4) : nullptr;
         w.xk_epoch = 0; w.status = nullptr;
     }
-};
-
-struct Family {   // P segments: queries rows q0 + p*Lq (+Lq) attend keys rows k0 + p*Lk (+Lk)
-    int q0, Lq, k0, Lk;
 };
 
 // One GeometryAttentionLayer call (transformero.py:43-96) on token buffers.
@@ -272,12 +244,6 @@ struct PlCtx {
     const uint8_t* tokmask;
     int attn_f16;                            // DR_LOOP_ATTN_F16
 };
-static PgW pgw_blocks(const PgW& v, int b0, int C) {
-    PgW r = v;
-    if (v.sub == 2) { r.img += (size_t)b0 * v.nct * 576 * 64; r.cinv += (size_t)b0 * 576; r.wnorm += b0; return r; }   // (two sub-blocks of 288 rows per block)
-    r.img += (size_t)b0 * v.nct * pgemm_bn(C) * 64; r.cinv += (size_t)b0 * pgemm_bn(C); r.wnorm += b0;
-    return r;
-}
 // exchange region of a problem whose launch may split its k range over two workgroups (pgemm.h: xk_buf).  The buffer holds PG_XK_MAX_RB units --
 // one per 64-row block of a LayerNorm launch / per 128 x 288 tile of a wide-wave launch; the problems of a launch take consecutive regions
 // (`next`: units handed out so far in this launch); the caller advances pw.xk_epoch once per launch that got regions.
@@ -466,6 +432,15 @@ static int denoiser_and_sim(const dr_loop_config& cfg, const dr_loop_weights& w,
                             const uint8_t* tokmask, DenoiseWs& ws, const float** final_feats, hipStream_t st,
                             bool use_cache = false) {
     const int C = cfg.C, H = cfg.H, T = P * (N + M), PN = P * N, PM = P * M;
+    // the matching head on the f32-input GEMM: src_proj on BOTH sides (quirk Q1), rotary, / sqrt(C) ...
+    auto head = [&](const float* feats) {
+        return gemm1(feats, C, w.src_proj, nullptr, ws.proj, C, T, C, C, EPI_ROTARY, 1.0f / sqrtf((float)C), nullptr, st, ws.cosT, ws.sinT, C);
+    };
+    // ... and sim[p] = a_p b_p^T : one NT GEMM per pair, all P pairs as one strided batch
+    auto sim = [&]() {
+        return gemm1(ws.proj, C, ws.proj + (size_t)PN * C, nullptr, ws.sim, M, N, M, C, EPI_NONE, 1.f, nullptr, st, nullptr, nullptr, 0, P,
+                     (long long)N * C, (long long)M * C, (long long)N * M);
+    };
     if (ws.pl.on) {
         const PlCtx X{ws.pp, &ws.pl, &ws.lw, C, H, P, N, M, ws.cosT, ws.sinT, tokmask, (cfg.flags & DR_LOOP_ATTN_F16) ? 1 : 0};
         const Family self_s{0, N, 0, N}, self_t{PN, M, PN, M}, cross_s{0, N, PN, M}, cross_t{PN, M, 0, N};
@@ -500,22 +475,8 @@ static int denoiser_and_sim(const dr_loop_config& cfg, const dr_loop_weights& w,
         *final_feats = cur->f32;
         if (env_knob("DR_HEAD_F32", 0)) {
             // (experiment: the head's projection on the f32-input MFMA GEMM, 24-bit operands, from the fp32 rows of the last layer)
-            GemmBatch gf;
-            memset(&gf, 0, sizeof(gf));
-            GemmProblem& pf = gf.p[0];
-            pf.A = cur->f32; pf.W = w.src_proj; pf.out = ws.proj; pf.rows = T; pf.ncols = C; pf.K = C; pf.K1 = C; pf.lda = C; pf.ldo = C;
-            pf.epi = EPI_ROTARY; pf.rot_C = C; pf.cosT = ws.cosT; pf.sinT = ws.sinT; pf.scale = 1.0f / sqrtf((float)C);
-            gf.n = 1;
-            int rcf = launch_gemm(gf, st);
-            if (rcf) return rcf;
-            GemmBatch gs;
-            memset(&gs, 0, sizeof(gs));
-            GemmProblem& q = gs.p[0];
-            q.A = ws.proj; q.W = ws.proj + (size_t)PN * C; q.out = ws.sim;
-            q.rows = N; q.ncols = M; q.K = C; q.K1 = C; q.lda = C; q.ldo = M; q.epi = EPI_NONE; q.scale = 1.f;
-            q.nbatch = P; q.sA = (long long)N * C; q.sW = (long long)M * C; q.sO = (long long)N * M;
-            gs.n = 1;
-            return launch_gemm(gs, st);
+            const int rc = head(cur->f32);
+            return rc ? rc : sim();
         }
         // matching head: src_proj on BOTH sides (quirk Q1), rotary, / sqrt(C)
         PgBatch g;
@@ -532,16 +493,8 @@ static int denoiser_and_sim(const dr_loop_config& cfg, const dr_loop_weights& w,
             if (p.W.sub == 2) xk_assign(ws.pl, C, p, xk_next, xk_wide_units(p));
         }
         ++ws.pl.xk_epoch;
-        int rc = launch_pgemm(g, st);
-        if (rc) return rc;
-        GemmBatch gs;
-        memset(&gs, 0, sizeof(gs));
-        GemmProblem& q = gs.p[0];
-        q.A = ws.proj; q.W = ws.proj + (size_t)PN * C; q.out = ws.sim;
-        q.rows = N; q.ncols = M; q.K = C; q.K1 = C; q.lda = C; q.ldo = M; q.epi = EPI_NONE; q.scale = 1.f;
-        q.nbatch = P; q.sA = (long long)N * C; q.sW = (long long)M * C; q.sO = (long long)N * M;
-        gs.n = 1;
-        return launch_gemm(gs, st);
+        const int rc = launch_pgemm(g, st);
+        return rc ? rc : sim();
     }
     const float* cur = feat0;
     float* bufs[2] = {ws.fa, ws.fb};
@@ -577,25 +530,8 @@ static int denoiser_and_sim(const dr_loop_config& cfg, const dr_loop_weights& w,
         which ^= 1;
     }
     *final_feats = cur;
-    // matching head: src_proj on BOTH sides (quirk Q1), rotary, / sqrt(C)
-    GemmBatch g;
-    memset(&g, 0, sizeof(g));
-    GemmProblem& p = g.p[0];
-    p.A = cur; p.W = w.src_proj; p.out = ws.proj; p.rows = T; p.ncols = C; p.K = C; p.K1 = C; p.lda = C; p.ldo = C;
-    p.epi = EPI_ROTARY; p.rot_C = C; p.cosT = ws.cosT; p.sinT = ws.sinT; p.scale = 1.0f / sqrtf((float)C);
-    g.n = 1;
-    int rc = launch_gemm(g, st);
-    if (rc) return rc;
-    // sim[p] = a_p b_p^T : one NT GEMM per pair, all P pairs as one strided batch
-    memset(&g, 0, sizeof(g));
-    GemmProblem& q = g.p[0];
-    q.A = ws.proj; q.W = ws.proj + (size_t)PN * C; q.out = ws.sim;
-    q.rows = N; q.ncols = M; q.K = C; q.K1 = C; q.lda = C; q.ldo = M; q.epi = EPI_NONE; q.scale = 1.f;
-    q.nbatch = P; q.sA = (long long)N * C; q.sW = (long long)M * C; q.sO = (long long)N * M;
-    g.n = 1;
-    rc = launch_gemm(g, st);
-    if (rc) return rc;
-    return DR_OK;
+    const int rc = head(cur);
+    return rc ? rc : sim();
 }
 
 static int fill_pe(const dr_loop_config& cfg, const dr_loop_weights& w, int P, int N, int M, const float* s_pcd,
@@ -644,13 +580,7 @@ struct LoopWs {
         w.tf = c.take<float>((size_t)P * 3);
         w.ok = c.take<int>(P);
         w.tokmask = c.take<uint8_t>(T);
-        const int strict = (cfg.flags & DR_LOOP_STRICT_F64) ? DR_SK_STRICT : 0;
-        size_t a = dr_sinkhorn_workspace_bytes(P, N, M, 8, strict);
-        size_t b = dr_sinkhorn_workspace_bytes(P, N, M, 4, 0);
-        w.skws_bytes = a > b ? a : b;
-        w.skws = w.skws_bytes ? (void*)c.take<char>(w.skws_bytes) : nullptr;
-        w.pws_bytes = procrustes_workspace_bytes(P, N, M);
-        w.pws = w.pws_bytes ? (void*)c.take<char>(w.pws_bytes) : nullptr;
+        sampler_scratch(c, P, N, M, cfg.flags, w.skws, w.skws_bytes, w.pws, w.pws_bytes);
         return c.off + 256;
     }
 };
@@ -684,91 +614,8 @@ using namespace dr;
 
 extern "C" {
 
-int dr_init(void) {
-    int rc = attention_configure();
-    if (rc == DR_OK) rc = gemm_configure();
-    if (rc == DR_OK) rc = pgemm_configure();
-    if (rc == DR_OK && !device_status_word()) rc = DR_ELAUNCH;       // resolved here, outside any stream capture (eval2d3d.hip)
-    return rc;
-}
-
-/* diagnostics for tools/ and tests: force the GEMM tile configuration (-1 auto, 0, 9, 11, 12), run the internal problem form */
-void dr_debug_enable_env(int on) { enable_env_knobs(on != 0); }
-void dr_debug_gemm_config(int c) { gemm_force_config(c); }
-
-int dr_debug_gemm_f32(const dr_debug_gemm_problem* problems, int n, void* stream) {
-    if (!problems || n < 1 || n > 4) return DR_EINVAL;
-    GemmBatch g;
-    memset(&g, 0, sizeof(g));
-    for (int i = 0; i < n; ++i) {
-        const dr_debug_gemm_problem& q = problems[i];
-        const int K1 = q.A2 ? q.K1 : q.K;
-        if (q.rows < 0 || q.ncols <= 0 || q.K <= 0 || !q.A || !q.W || !q.out || q.nbatch < 0) return DR_EINVAL;
-        if (q.lda < K1 || q.ldo < q.ncols || (q.A2 && (K1 <= 0 || K1 >= q.K || q.lda2 < q.K - K1))) return DR_EINVAL;
-        if ((q.epilogue & ~(EPI_RELU | EPI_ROTARY)) ||
-            ((q.epilogue & EPI_ROTARY) && (!q.cos_t || !q.sin_t || q.rot_C <= 0 || (q.rot_C & 1))))
-            return DR_EINVAL;
-        GemmProblem& p = g.p[i];
-        p.A = q.A; p.A2 = q.A2; p.W = q.W; p.out = q.out; p.cosT = q.cos_t; p.sinT = q.sin_t; p.bias = q.bias; p.addend = q.addend;
-        p.rows = q.rows; p.ncols = q.ncols; p.K = q.K; p.K1 = K1; p.lda = q.lda; p.lda2 = q.A2 ? q.lda2 : 0; p.ldo = q.ldo;
-        p.epi = q.epilogue; p.rot_C = q.rot_C; p.scale = q.scale;
-        p.nbatch = q.nbatch; p.sA = q.stride_a; p.sW = q.stride_w; p.sO = q.stride_o;
-    }
-    g.n = n;
-    return launch_gemm(g, (hipStream_t)stream);
-}
-void dr_debug_attention_config(int flash_min_workgroups) { attention_force_flash_min(flash_min_workgroups); }
-void dr_debug_attention_split(int on) { attention_force_split(on); }
-
-int dr_vol_pe_f32(int rows, int rows_per_pair, int C, const float* xyz, const float* R, const float* t, float origin_x,
-                  float origin_y, float origin_z, float voxel, const float* freq, float* cos_out, float* sin_out,
-                  void* stream) {
-    if (rows < 0 || C <= 0 || !xyz || !freq || !cos_out || !sin_out || rows_per_pair < 1) return DR_EINVAL;
-    if ((R == nullptr) != (t == nullptr)) return DR_EINVAL;
-    return launch_vol_pe(xyz, rows, rows_per_pair, R, t, C, origin_x, origin_y, origin_z, voxel, freq, cos_out, sin_out,
-                         (hipStream_t)stream);
-}
-
-int dr_linear_f32(int rows, int ncols, int K, const float* x, const float* W, float* out, int epilogue, const float* cos_t,
-                  const float* sin_t, int rot_C, float scale, void* stream) {
-    if (rows < 0 || ncols <= 0 || K <= 0 || !x || !W || !out) return DR_EINVAL;
-    if ((epilogue & EPI_ROTARY) && (!cos_t || !sin_t || rot_C <= 0 || (rot_C & 1))) return DR_EINVAL;
-    GemmBatch g;
-    memset(&g, 0, sizeof(g));
-    GemmProblem& p = g.p[0];
-    p.A = x; p.W = W; p.out = out; p.rows = rows; p.ncols = ncols; p.K = K; p.K1 = K; p.lda = K; p.ldo = ncols;
-    p.epi = epilogue; p.cosT = cos_t; p.sinT = sin_t; p.rot_C = rot_C; p.scale = scale;
-    g.n = 1;
-    return launch_gemm(g, (hipStream_t)stream);
-}
-
-int dr_gemm_nt_batched_f32(int nbatch, int rows, int ncols, int K, const float* A, long long stride_a, const float* W, long long stride_w, float* out,
-                           long long stride_o, float scale, void* stream) {
-    if (nbatch < 0 || rows < 0 || ncols <= 0 || K <= 0 || (K & 3) || !A || !W || !out) return DR_EINVAL;
-    if (nbatch == 0 || rows == 0) return DR_OK;
-    GemmBatch g;
-    memset(&g, 0, sizeof(g));
-    GemmProblem& p = g.p[0];
-    p.A = A; p.W = W; p.out = out; p.rows = rows; p.ncols = ncols; p.K = K; p.K1 = K; p.lda = K; p.ldo = ncols; p.epi = EPI_NONE; p.scale = scale;
-    p.nbatch = nbatch; p.sA = stride_a; p.sW = stride_w; p.sO = stride_o;
-    g.n = 1;
-    return launch_gemm(g, (hipStream_t)stream);
-}
-
-int dr_linear_ex_f32(int rows, int ncols, int K, const float* x, int lda, const float* W, const float* bias, float* out, int ldo,
-                     int epilogue, float scale, void* stream) {
-    if (rows < 0 || ncols <= 0 || K <= 0 || !x || !W || !out || lda < K || ldo < ncols || (epilogue & EPI_ROTARY)) return DR_EINVAL;
-    GemmBatch g;
-    memset(&g, 0, sizeof(g));
-    GemmProblem& p = g.p[0];
-    p.A = x; p.W = W; p.bias = bias; p.out = out; p.rows = rows; p.ncols = ncols; p.K = K; p.K1 = K; p.lda = lda; p.ldo = ldo;
-    p.epi = epilogue; p.scale = scale;
-    g.n = 1;
-    return launch_gemm(g, (hipStream_t)stream);
-}
-
 size_t dr_attention_layer_workspace_bytes(int P, int Lx, int Ly, int C) {
-    Carver c(nullptr, 0);
+    Carver c(nullptr);
     LayerWs w;
     const size_t T = (size_t)P * (Lx + Ly);
     LayerWs::carve(c, w, T, C);
@@ -801,7 +648,7 @@ int dr_attention_layer_pe_f32(const dr_layer_weights* w, int C, int H, int P, in
     if ((xq == nullptr) != (yk == nullptr) || (xq && rotary)) return DR_EINVAL;   // additive code and rotary code exclude each other (pe_type)
     if (workspace_bytes < dr_attention_layer_workspace_bytes(P, Lx, Ly, C) || !workspace) return DR_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    Carver c(workspace, workspace_bytes);
+    Carver c(workspace);
     LayerWs lw;
     const size_t T = (size_t)P * (Lx + Ly), PX = (size_t)P * Lx, PY = (size_t)P * Ly;
     const int halfC = C / 2;
@@ -837,47 +684,6 @@ int dr_attention_layer_pe_f32(const dr_layer_weights* w, int C, int H, int P, in
     return DR_OK;
 }
 
-size_t dr_procrustes_workspace_bytes(int P, int N, int M) {
-    return (P < 1 || N < 1 || M < 1) ? 0 : procrustes_workspace_bytes(P, N, M);
-}
-
-int dr_procrustes_f32(int P, int N, int M, const float* conf, const float* src_pcd, const float* tgt_pcd,
-                      const uint8_t* src_mask, const uint8_t* tgt_mask, int use_mask_len, float sample_rate,
-                      float max_condition_num, float* R, float* t, float* R_forwd, float* t_forwd, double* condition,
-                      int32_t* solution_mask, int32_t* topk_idx, void* workspace, size_t workspace_bytes, void* stream) {
-    if (P < 0 || N < 1 || M < 1 || !conf || !src_pcd || !tgt_pcd || !R || !t || !R_forwd || !t_forwd || !condition || !solution_mask)
-        return DR_EINVAL;
-    if (P == 0) return DR_OK;
-    // tiles beyond 256 x 256 select with the whole chip: the caller's scratch (header contract: the caller owns every buffer)
-    const size_t wsb = procrustes_workspace_bytes(P, N, M);
-    if (wsb && (!workspace || workspace_bytes < wsb)) return DR_EWORKSPACE;
-    return launch_procrustes(conf, src_pcd, tgt_pcd, src_mask, tgt_mask, P, N, M, use_mask_len, sample_rate, max_condition_num,
-                             R, t, R_forwd, t_forwd, condition, solution_mask, topk_idx, (hipStream_t)stream, wsb ? workspace : nullptr, wsb);
-}
-
-size_t dr_top1_union_workspace_bytes(int P, int N, int M, int elem_bytes) {
-    return (P < 1 || N < 1 || M < 1 || (elem_bytes != 4 && elem_bytes != 8)) ? 0 : top1_union_workspace_bytes(P, N, M, (size_t)elem_bytes);
-}
-
-}  // extern "C"
-template <typename T>
-static int top1_union_entry(const T* conf, int P, int N, int M, int64_t* matches, int32_t* count, void* ws, size_t ws_bytes, hipStream_t st) {
-    if (P < 0 || N < 1 || M < 1 || !conf || !matches || !count) return DR_EINVAL;
-    if (P == 0) return DR_OK;
-    const size_t wsb = top1_union_workspace_bytes(P, N, M, sizeof(T));
-    if (wsb && (!ws || ws_bytes < wsb)) return DR_EWORKSPACE;
-    return launch_top1_union<T>(conf, P, N, M, (long long*)matches, count, st, nullptr, nullptr, wsb ? ws : nullptr, wsb);
-}
-extern "C" {
-int dr_top1_union_f64(int P, int N, int M, const double* conf, int64_t* matches, int32_t* count, void* workspace, size_t workspace_bytes,
-                      void* stream) {
-    return top1_union_entry<double>(conf, P, N, M, matches, count, workspace, workspace_bytes, (hipStream_t)stream);
-}
-int dr_top1_union_f32(int P, int N, int M, const float* conf, int64_t* matches, int32_t* count, void* workspace, size_t workspace_bytes,
-                      void* stream) {
-    return top1_union_entry<float>(conf, P, N, M, matches, count, workspace, workspace_bytes, (hipStream_t)stream);
-}
-
 static int check_cfg(const dr_loop_config* cfg, const dr_loop_weights* w, int P, int N, int M) {
     if (!cfg || !w || P < 1 || N < 1 || M < 1) return DR_EINVAL;
     if (cfg->C % cfg->H || (cfg->C / cfg->H) % 4 || cfg->C % 6 || cfg->n_layers < 1 || cfg->sk_iters < 1) return DR_EINVAL;
@@ -900,14 +706,14 @@ int dr_loop_prepack(const dr_loop_config* cfg, const dr_loop_weights* w, void* p
 
 size_t dr_denoise_loop_workspace_bytes(const dr_loop_config* cfg, int P, int N, int M) {
     if (!cfg || P < 1 || N < 1 || M < 1) return 0;
-    Carver c(nullptr, 0);
+    Carver c(nullptr);
     LoopWs w;
     return LoopWs::carve(c, w, *cfg, P, N, M);
 }
 
 int dr_denoise_loop_status(void* workspace, void* stream, int clear) {
     if (!workspace) return DR_EINVAL;
-    Carver c(workspace, (size_t)-1);
+    Carver c(workspace);
     return sinkhorn_call_status(c.take<unsigned>(4), (hipStream_t)stream, clear != 0);
 }
 
@@ -921,7 +727,7 @@ int dr_denoiser_match_f32(const dr_loop_config* cfg, const dr_loop_weights* w, i
     if ((src_mask == nullptr) != (tgt_mask == nullptr)) return DR_EINVAL;
     if (!workspace || workspace_bytes < dr_denoise_loop_workspace_bytes(cfg, P, N, M)) return DR_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    Carver c(workspace, workspace_bytes);
+    Carver c(workspace);
     LoopWs L;
     LoopWs::carve(c, L, *cfg, P, N, M);
     DR_HIP_CHECK(hipMemsetAsync(L.status, 0, 16, st));          // the status of THIS call (one 16-byte fill per call)
@@ -964,7 +770,7 @@ int dr_denoise_loop(const dr_loop_config* cfg, const dr_loop_weights* w, int P, 
     if (trace && (trace->force_R == nullptr) != (trace->force_t == nullptr)) return DR_EINVAL;
     if (!workspace || workspace_bytes < dr_denoise_loop_workspace_bytes(cfg, P, N, M)) return DR_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    Carver c(workspace, workspace_bytes);
+    Carver c(workspace);
     LoopWs L;
     LoopWs::carve(c, L, *cfg, P, N, M);
     DR_HIP_CHECK(hipMemsetAsync(L.status, 0, 16, st));          // the status of THIS call (one 16-byte fill per call)
@@ -999,77 +805,35 @@ int dr_denoise_loop(const dr_loop_config* cfg, const dr_loop_weights* w, int P, 
     rc = fill_tgt_cache(*cfg, *w, P, N, M, L.feat0, tokmask, L.dw, st);
     if (rc) return rc;
 
-    const double* ac = cfg->h_alphas_cumprod;
+    // -- the steps: x <- x - x.min() first (3D only), per-step noise (4D only); the denoiser of a step is the position code of the warped
+    // source (pipeline.py:306, transformero.py:165), denoising_transformer + denoising_coarse_matching (pipeline.py:243-244) and the
+    // float32 Sinkhorn of the similarity
     const float* fin = nullptr;
-    for (int k = 0; k < cfg->steps; ++k) {
-        const int tcur = cfg->h_times[k], tnext = cfg->h_times[k + 1];
-        // teacher forcing (parity tests): this step starts from the caller's state, not from the loop's own
-        if (trace && trace->force_x) DR_HIP_CHECK(hipMemcpyAsync(L.x, trace->force_x + (size_t)k * NM, NM * 8, hipMemcpyDeviceToDevice, st));
-        // -- x <- x - x.min() (3D only, pipeline.py:239); mask; Sinkhorn; exp; slice; float32 (pipeline.py:293-302)
-        const double* shift = nullptr;
-        if (!v4d) {
-            rc = launch_pair_min(L.x, P, N * M, L.dmin, st, M, rsm, rtm, P <= 32 ? L.pmin : nullptr);
-            if (rc) return rc;
-            shift = L.dmin;
-        }
-        rc = sinkhorn_f64(P, N, M, L.x, shift, src_mask, tgt_mask, w->bin_score, cfg->sk_iters,
-                          DR_SK_OUT_CONF | DR_SK_OUT_F32 | mflag | (k > 0 ? strict : 0), L.wconf, L.skws, L.skws_bytes, st, L.status);
-        if (rc) return rc;
-        // -- denoising_soft_procrustes (pipeline.py:304)
-        int* tk = nullptr;
-        if (trace && trace->topk_idx) {
-            const size_t Kf = (size_t)(int)((float)(N > M ? N : M) * cfg->sample_rate);
-            tk = trace->topk_idx + (size_t)k * P * Kf;
-            DR_HIP_CHECK(hipMemsetAsync(tk, 0xff, (size_t)P * Kf * 4, st));
-        }
-        if (trace && trace->wconf) DR_HIP_CHECK(hipMemcpyAsync(trace->wconf + (size_t)k * NM, L.wconf, NM * 4, hipMemcpyDeviceToDevice, st));
-        rc = launch_procrustes(L.wconf, s_pcd, t_pcd, src_mask, tgt_mask, P, N, M, (v4d || ragged) ? 1 : 0, cfg->sample_rate,
-                               cfg->max_condition_num, L.R, L.t, L.Rf, L.tf, L.cond, L.ok, tk, st, L.pws, L.pws_bytes);
-        if (rc) return rc;
-        if (trace && trace->R_forwd) DR_HIP_CHECK(hipMemcpyAsync(trace->R_forwd + (size_t)k * P * 9, L.Rf, (size_t)P * 36, hipMemcpyDeviceToDevice, st));
-        if (trace && trace->t_forwd) DR_HIP_CHECK(hipMemcpyAsync(trace->t_forwd + (size_t)k * P * 3, L.tf, (size_t)P * 12, hipMemcpyDeviceToDevice, st));
-        if (trace && trace->cond) DR_HIP_CHECK(hipMemcpyAsync(trace->cond + (size_t)k * P, L.cond, (size_t)P * 8, hipMemcpyDeviceToDevice, st));
-        if (trace && trace->force_R) {           // teacher forcing: warp with the caller's pose (the fit above is traced all the same)
-            DR_HIP_CHECK(hipMemcpyAsync(L.Rf, trace->force_R + (size_t)k * P * 9, (size_t)P * 36, hipMemcpyDeviceToDevice, st));
-            DR_HIP_CHECK(hipMemcpyAsync(L.tf, trace->force_t + (size_t)k * P * 3, (size_t)P * 12, hipMemcpyDeviceToDevice, st));
-        }
-        // -- position code of the warped source (pipeline.py:306, transformero.py:165)
-        rc = fill_pe(*cfg, *w, P, N, M, s_pcd, L.Rf, L.tf, t_pcd, true, false, L.dw, st);
-        if (rc) return rc;
-        // -- denoising_transformer + denoising_coarse_matching (pipeline.py:243-244)
-        rc = denoiser_and_sim(*cfg, *w, P, N, M, L.feat0, tokmask, L.dw, &fin, st, true);
-        if (rc) return rc;
-        rc = sinkhorn_f32(P, N, M, L.dw.sim, src_mask, tgt_mask, w->bin_score, cfg->sk_iters, DR_SK_OUT_CONF | mflag, L.x0,
-                          L.skws, L.skws_bytes, st, L.status);
-        if (rc) return rc;
-        if (trace && trace->x0) DR_HIP_CHECK(hipMemcpyAsync(trace->x0 + (size_t)k * NM, L.x0, NM * 4, hipMemcpyDeviceToDevice, st));
-        // -- DDIM update (pipeline.py:246-256)
-        const double a = ac[tcur], an = ac[tnext];
-        DdimArgs d;
-        d.x = L.x; d.x0 = L.x0; d.shift = shift; d.noise = v4d ? noise + (size_t)k * NM : nullptr;
-        d.src_mask = src_mask; d.tgt_mask = tgt_mask; d.N = N; d.M = M; d.first_step = (k == 0);
-        d.sra = sqrt(1.0 / a); d.srm1 = sqrt(1.0 / a - 1.0);
-        d.sigma = 1.0 * sqrt((1.0 - a / an) * (1.0 - an) / (1.0 - a));
-        d.c = sqrt(1.0 - an - d.sigma * d.sigma);
-        d.sqrt_an = (float)sqrt(an);
-        rc = launch_ddim(d, P, st);
-        if (rc) return rc;
-        if (trace && trace->x_next) DR_HIP_CHECK(hipMemcpyAsync(trace->x_next + (size_t)k * NM, L.x, NM * 8, hipMemcpyDeviceToDevice, st));
-    }
-    if (x_final) DR_HIP_CHECK(hipMemcpyAsync(x_final, L.x, NM * 8, hipMemcpyDeviceToDevice, st));
+    SamplerArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.P = P; sa.N = N; sa.M = M; sa.steps = cfg->steps; sa.alphas_cumprod = cfg->h_alphas_cumprod; sa.times = cfg->h_times;
+    sa.sample_rate = cfg->sample_rate; sa.max_condition_num = cfg->max_condition_num; sa.sk_iters = cfg->sk_iters; sa.strict = strict;
+    sa.s_pcd = s_pcd; sa.warp_tgt_pcd = t_pcd; sa.src_mask = src_mask; sa.warp_tgt_mask = tgt_mask;
+    sa.warp_mflag = mflag; sa.use_mask_len = (v4d || ragged) ? 1 : 0;
+    sa.min_shift = !v4d; sa.rsm = rsm; sa.rtm = rtm; sa.dmin = L.dmin; sa.pmin = P <= 32 ? L.pmin : nullptr;
+    sa.noise = v4d ? noise : nullptr; sa.bin_score = w->bin_score; sa.trace = trace;
+    sa.x = L.x; sa.x_final = x_final; sa.x0 = L.x0; sa.wconf = L.wconf; sa.R = L.R; sa.t = L.t; sa.Rf = L.Rf; sa.tf = L.tf; sa.cond = L.cond; sa.ok = L.ok;
+    sa.skws = L.skws; sa.skws_bytes = L.skws_bytes; sa.pws = L.pws; sa.pws_bytes = L.pws_bytes; sa.status = L.status;
+    rc = reverse_sampling(sa, [&](const float* Rf, const float* tf) -> int {
+        int r = fill_pe(*cfg, *w, P, N, M, s_pcd, Rf, tf, t_pcd, true, false, L.dw, st);
+        if (r == DR_OK) r = denoiser_and_sim(*cfg, *w, P, N, M, L.feat0, tokmask, L.dw, &fin, st, true);
+        if (r) return r;
+        return sinkhorn_f32(P, N, M, L.dw.sim, src_mask, tgt_mask, w->bin_score, cfg->sk_iters, DR_SK_OUT_CONF | mflag, L.x0, L.skws, L.skws_bytes, st,
+                            L.status);
+    }, st);
+    if (rc) return rc;
     if (trace && (trace->feats_nopos || trace->feats_pos) && fin) {
         // data["src_feats_nopos"] / ["src_feats"] (+ tgt) of the last Matching.forward (matching.py:177-187): src_proj on both
         // sides (quirk Q1), without and with the rotary embedding of the last step's position code
         for (int pos = 0; pos < 2; ++pos) {
             float* dst = pos ? trace->feats_pos : trace->feats_nopos;
             if (!dst) continue;
-            GemmBatch g;
-            memset(&g, 0, sizeof(g));
-            GemmProblem& p = g.p[0];
-            p.A = fin; p.W = w->src_proj; p.out = dst; p.rows = (int)(PN + PM); p.ncols = C; p.K = C; p.K1 = C; p.lda = C; p.ldo = C;
-            p.epi = pos ? EPI_ROTARY : EPI_NONE; p.rot_C = C; p.cosT = L.dw.cosT; p.sinT = L.dw.sinT; p.scale = 1.f;
-            g.n = 1;
-            rc = launch_gemm(g, st);
+            rc = gemm1(fin, C, w->src_proj, nullptr, dst, C, (int)(PN + PM), C, C, pos ? EPI_ROTARY : EPI_NONE, 1.f, nullptr, st, L.dw.cosT, L.dw.sinT, C);
             if (rc) return rc;
         }
     }

@@ -1,7 +1,8 @@
 // loop2d3d.hip -- orchestration of the 2D-3D variant: CrossModalFusionModule denoiser,
 // position-free matching head, reverse sampling of MATR2D3D.forward.  Same kernels as loop.hip
 // (GEMM with bias / addend epilogues, attention with d_head = 64, post-LN LayerNorm, Sinkhorn,
-// Procrustes, DDIM), enqueued on one stream without host synchronisation.
+// Procrustes, DDIM), enqueued on one stream without host synchronisation.  The steps are reverse_sampling() of loop_common.h, shared
+// with loop.hip.
 //
 // Token layout: image patches of all P pairs (pair p at row p*M), then point nodes (P*M + p*N).
 //
@@ -11,22 +12,9 @@
 // epilogue modes of the plane GEMM (bias, post-add LayerNorm, 256-column geometry) -- five launches per layer call instead of
 // eight, no fp32 round trip of q / k / v / h / hidden.  The image half of layer 0 (a self layer on step-invariant tokens) is
 // evaluated once per call.
-#include "kernels.h"
-#include "pgemm.h"
-#include <string.h>
+#include "loop_common.h"
 
 namespace dr {
-
-struct Carver2 {
-    char* base; size_t off;
-    explicit Carver2(void* p) : base((char*)p), off(0) {}
-    template <typename T> T* take(size_t n) {
-        off = (off + 255) & ~(size_t)255;
-        T* r = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += n * sizeof(T);
-        return r;
-    }
-};
 
 // ---- plane path ---------------------------------------------------------------------------------------------------------------
 struct P2Layer {
@@ -47,7 +35,7 @@ struct Prepack2 {
         return pgemm_shape_ok(cfg.C) && (d == 64 || d == 112 || d == 144) && cfg.C / 16 >= 4;
     }
     static size_t carve(void* buf, const dr_loop2d3d_config& cfg, Prepack2* pp) {
-        Carver2 c(buf);
+        Carver c(buf);
         const int C = cfg.C, nC = C / 16;
         auto take = [&](int nblk, int nct, PgW* v) {
             char* p = c.take<char>(pgemm_weight_bytes(C, nblk, nct));
@@ -105,25 +93,21 @@ struct Prepack2 {
     }
 };
 
-// a token tensor of the plane path: fp32 rows [T, C], plane image (image part, then point part, each padded to 128 rows), bounds [T]
-struct Tok2 { float* f32; char* img; float* bnd; };
 struct Planes2 {
     bool on;
-    Tok2 tok0, ta, tb, l0, z;
+    Tok tok0, ta, tb, l0, z;
     char *qkv_img, *att_img, *hid_img, *feat_img;
     float *qkv_bnd, *att_bnd, *hid_bnd, *feat_bnd, *grp_x;
     size_t qkv_stride, side_C, side_hid;    // bytes from the q image to the k image; offset of the point part in an image of K = C / 2C
     void* own_pack;
     static size_t img_bytes(int PM, int PN, int K) { return plane_image_bytes(PM, K) + plane_image_bytes(PN, K); }
-    static void carve(Carver2& c, Planes2& w, const dr_loop2d3d_config& cfg, int P, int N, int M) {
+    static void carve(Carver& c, Planes2& w, const dr_loop2d3d_config& cfg, int P, int N, int M) {
         const int C = cfg.C, PM = P * M, PN = P * N, T = PM + PN;
-        w.on = env_knob("DR_PLANES", 1) && Prepack2::supported(cfg) && T >= env_knob("DR_PLANES_MIN_ROWS", 4096);
-        if (cfg.flags & DR_LOOP_PLANES_FORCE) w.on = Prepack2::supported(cfg);
-        if (cfg.flags & DR_LOOP_PLANES_OFF) w.on = false;
+        w.on = planes_wanted(cfg.flags, Prepack2::supported(cfg), T);
         if (!w.on) return;
         w.side_C = plane_image_bytes(PM, C); w.side_hid = plane_image_bytes(PM, 2 * C);
-        Tok2* toks[5] = {&w.tok0, &w.ta, &w.tb, &w.l0, &w.z};
-        for (Tok2* t : toks) { t->f32 = nullptr; t->img = c.take<char>(img_bytes(PM, PN, C)); t->bnd = c.take<float>(T); }
+        Tok* toks[5] = {&w.tok0, &w.ta, &w.tb, &w.l0, &w.z};
+        for (Tok* t : toks) { t->f32 = nullptr; t->img = c.take<char>(img_bytes(PM, PN, C)); t->bnd = c.take<float>(T); }
         w.l0.f32 = c.take<float>((size_t)T * C);
         w.qkv_stride = (img_bytes(PM, PN, C) + 255) & ~(size_t)255;
         w.qkv_img = c.take<char>(3 * w.qkv_stride); w.qkv_bnd = c.take<float>(3 * (size_t)T);
@@ -144,7 +128,7 @@ struct F2Ws {
     void* pws; size_t pws_bytes;
     Planes2 pl;
     unsigned* status;                        // the call's own sticky status word (dr_denoise_loop_status): zeroed when a call starts
-    static size_t carve(Carver2& c, F2Ws& w, const dr_loop2d3d_config& cfg, int P, int N, int M) {
+    static size_t carve(Carver& c, F2Ws& w, const dr_loop2d3d_config& cfg, int P, int N, int M) {
         const size_t T = (size_t)P * (N + M), C = cfg.C, NM = (size_t)P * N * M, PM = (size_t)P * M, PN = (size_t)P * N;
         w.status = c.take<unsigned>(4);      // (first, as in the 3D / 4D loop's workspace: dr_denoise_loop_status reads either)
         w.tok0 = c.take<float>(T * C); w.ta = c.take<float>(T * C); w.tb = c.take<float>(T * C);
@@ -157,28 +141,12 @@ struct F2Ws {
         w.R = c.take<float>((size_t)P * 9); w.t = c.take<float>((size_t)P * 3);
         w.Rf = c.take<float>((size_t)P * 9); w.tf = c.take<float>((size_t)P * 3);
         w.x = c.take<double>(NM); w.cond = c.take<double>(P); w.ok = c.take<int>(P);
-        const int strict = (cfg.flags & DR_LOOP_STRICT_F64) ? DR_SK_STRICT : 0;
-        size_t a = dr_sinkhorn_workspace_bytes(P, N, M, 8, strict), b = dr_sinkhorn_workspace_bytes(P, N, M, 4, 0);
-        w.skws_bytes = a > b ? a : b;
-        w.skws = w.skws_bytes ? (void*)c.take<char>(w.skws_bytes) : nullptr;
-        w.pws_bytes = procrustes_workspace_bytes(P, N, M);
-        w.pws = w.pws_bytes ? (void*)c.take<char>(w.pws_bytes) : nullptr;
+        sampler_scratch(c, P, N, M, cfg.flags, w.skws, w.skws_bytes, w.pws, w.pws_bytes);
         Planes2::carve(c, w.pl, cfg, P, N, M);
         if (w.pl.on) { w.pl.tok0.f32 = w.tok0; w.pl.ta.f32 = w.ta; w.pl.tb.f32 = w.tb; w.pl.z.f32 = w.z; }
         return c.off + 256;
     }
 };
-
-static int gemm1(const float* A, int lda, const float* W, const float* bias, float* out, int ldo, int rows, int ncols, int K,
-                 int epi, float scale, const float* addend, hipStream_t st) {
-    GemmBatch g;
-    memset(&g, 0, sizeof(g));
-    GemmProblem& p = g.p[0];
-    p.A = A; p.W = W; p.out = out; p.rows = rows; p.ncols = ncols; p.K = K; p.K1 = K; p.lda = lda; p.ldo = ldo;
-    p.epi = epi; p.scale = scale; p.bias = bias; p.addend = addend;
-    g.n = 1;
-    return launch_gemm(g, st);
-}
 
 // one vision3d TransformerLayer: x rows [xr0, +xrows) of xin attend y rows [yr0, +yrows) of yin
 static int fusion_layer(const dr_fusion_layer_weights& W, int C, int H, int P, const float* xin, int xr0, int xrows, int Lx,
@@ -220,16 +188,10 @@ static int fusion_layer(const dr_fusion_layer_weights& W, int C, int H, int P, c
 
 // ---- one vision3d TransformerLayer call on plane images: five launches ---------------------------------------------------------
 enum { SIDE_IMG = 1, SIDE_PCD = 2, SIDE_BOTH2 = 3 };
-struct Fam2 { int q0, Lq, k0, Lk; };
 struct P2Ctx { const Prepack2* pp; const Planes2* pw; int C, H, P, N, M; int attn_f16; };
-static PgW pgw_blocks2(const PgW& v, int b0, int C) {
-    PgW r = v;
-    r.img += (size_t)b0 * v.nct * pgemm_bn(C) * 64; r.cinv += (size_t)b0 * pgemm_bn(C); r.wnorm += b0;
-    return r;
-}
 // x rows of side(s) xs of `xin` attend the rows of side(s) ys of `yin`; out gets the x sides (fp32 rows + image + bounds)
-static int fusion_layer_planes(const P2Ctx& X, const dr_fusion_layer_weights& W, int l, const Tok2& xin, int xs, const Tok2& yin, int ys,
-                               const Tok2& out, const Fam2& f1, const Fam2* f2, hipStream_t st) {
+static int fusion_layer_planes(const P2Ctx& X, const dr_fusion_layer_weights& W, int l, const Tok& xin, int xs, const Tok& yin, int ys,
+                               const Tok& out, const Family& f1, const Family* f2, hipStream_t st) {
     const int C = X.C, H = X.H, PM = X.P * X.M, PN = X.P * X.N, T = PM + PN, nC = C / 16, d = C / H;
     const P2Layer& L = X.pp->L[l];
     const Planes2& pw = *X.pw;
@@ -249,10 +211,10 @@ static int fusion_layer_planes(const P2Ctx& X, const dr_fusion_layer_weights& W,
         if (ys & side) rc = launch_group_max(yin.bnd + r0(side), X.P, per_pair(side), pw.grp_x + (side == SIDE_PCD ? X.P : 0), st);
     if (rc) return rc;
     // ---- q | k | v = x W^T + b -> three plane images (head h at k = h d), no rotary (vision3d/layers/transformer.py:96-104)
-    auto proj = [&](const Tok2& tin, int side, int b0, int nblk, int grpm) {
+    auto proj = [&](const Tok& tin, int side, int b0, int nblk, int grpm) {
         PgProblem& p = add();
         p.A0 = at(tin.img, pw.side_C, side); p.bnd0 = tin.bnd + r0(side); p.nc0 = nC;
-        p.W = pgw_blocks2(L.qkv, b0, C); p.nblk = nblk; p.rows = nrows(side); p.C = C; p.k_alg = C; p.mode = PG_PLANES; p.scale = 1.f;
+        p.W = pgw_blocks(L.qkv, b0, C); p.nblk = nblk; p.rows = nrows(side); p.C = C; p.k_alg = C; p.mode = PG_PLANES; p.scale = 1.f;
         p.bias = L.qkv_b + (size_t)b0 * C; p.bias_max = L.qkv_bmax + b0;
         p.pimg = at(pw.qkv_img + (size_t)b0 * pw.qkv_stride, pw.side_C, side); p.p_nct = nC; p.pbnd = pw.qkv_bnd + (size_t)b0 * T + r0(side);
         p.pimg_blk_stride = (long long)pw.qkv_stride; p.pbnd_blk_stride = T;
@@ -340,7 +302,7 @@ int dr_loop2d3d_prepack(const dr_loop2d3d_config* cfg, const dr_fusion_weights* 
 
 size_t dr_denoise_loop_2d3d_workspace_bytes(const dr_loop2d3d_config* cfg, int P, int N, int M) {
     if (!cfg || P < 1 || N < 1 || M < 1) return 0;
-    Carver2 c(nullptr);
+    Carver c(nullptr);
     F2Ws w;
     return F2Ws::carve(c, w, *cfg, P, N, M);
 }
@@ -361,7 +323,7 @@ int dr_denoise_loop_2d3d(const dr_loop2d3d_config* cfg, const dr_fusion_weights*
     if (trace && (trace->force_R == nullptr) != (trace->force_t == nullptr)) return DR_EINVAL;
     if (!workspace || workspace_bytes < dr_denoise_loop_2d3d_workspace_bytes(cfg, P, N, M)) return DR_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    Carver2 c(workspace);
+    Carver c(workspace);
     F2Ws L;
     F2Ws::carve(c, L, *cfg, P, N, M);
     DR_HIP_CHECK(hipMemsetAsync(L.status, 0, 16, st));          // the status of THIS call (dr_denoise_loop_status)
@@ -402,7 +364,7 @@ int dr_denoise_loop_2d3d(const dr_loop2d3d_config* cfg, const dr_fusion_weights*
         rc = launch_planes_from_f32(L.tok0, C, PM, C, L.pl.tok0.img, L.pl.tok0.bnd, st);
         if (rc) return rc;
         const P2Ctx X{&pp, &L.pl, C, H, P, N, M, (cfg->flags & DR_LOOP_ATTN_F16) ? 1 : 0};
-        const Fam2 self_i{0, M, 0, M};
+        const Family self_i{0, M, 0, M};
         rc = fusion_layer_planes(X, w->layers[0], 0, L.pl.tok0, SIDE_IMG, L.pl.tok0, SIDE_IMG, L.pl.l0, self_i, nullptr, st);
         if (rc) return rc;
     }
@@ -416,18 +378,18 @@ int dr_denoise_loop_2d3d(const dr_loop2d3d_config* cfg, const dr_fusion_weights*
         if (L.pl.on) {
             const Planes2& pw = L.pl;
             const P2Ctx X{&pp, &pw, C, H, P, N, M, (cfg->flags & DR_LOOP_ATTN_F16) ? 1 : 0};
-            const Fam2 self_i{0, M, 0, M}, self_p{PM, N, PM, N}, cross_i{0, M, PM, N}, cross_p{PM, N, 0, M};
+            const Family self_i{0, M, 0, M}, self_p{PM, N, PM, N}, cross_i{0, M, PM, N}, cross_p{PM, N, 0, M};
             // the point tokens of this step -> their part of the token image (row maxima as bounds)
             r = launch_planes_from_f32(L.tok0 + (size_t)PM * C, C, PN, C, pw.tok0.img + pw.side_C, pw.tok0.bnd + PM, st);
             if (r) return r;
             // layer 0 (self): the image half is step-invariant and sits in pw.l0 already (l0_image_half below); the point half joins it there
             r = fusion_layer_planes(X, w->layers[0], 0, pw.tok0, SIDE_PCD, pw.tok0, SIDE_PCD, pw.l0, self_p, nullptr, st);
             if (r) return r;
-            const Tok2* cur = &pw.l0;
-            const Tok2* bufs[2] = {&pw.ta, &pw.tb};
+            const Tok* cur = &pw.l0;
+            const Tok* bufs[2] = {&pw.ta, &pw.tb};
             int which = 0;
             for (int l = 1; l < cfg->n_layers; ++l) {
-                const Tok2* nxt = bufs[which];
+                const Tok* nxt = bufs[which];
                 if (l % 2 == 0) {
                     r = fusion_layer_planes(X, w->layers[l], l, *cur, SIDE_BOTH2, *cur, SIDE_BOTH2, *nxt, self_i, &self_p, st);
                     if (r) return r;
@@ -465,13 +427,8 @@ int dr_denoise_loop_2d3d(const dr_loop2d3d_config* cfg, const dr_fusion_weights*
             }
             r = launch_pgemm(g, st);
             if (r) return r;
-            GemmBatch gs;
-            memset(&gs, 0, sizeof(gs));
-            GemmProblem& q = gs.p[0];
-            q.A = L.z + (size_t)PM * C; q.W = L.z; q.out = L.sim; q.rows = N; q.ncols = M; q.K = C; q.K1 = C; q.lda = C; q.ldo = M;
-            q.epi = EPI_NONE; q.scale = 1.f; q.nbatch = P; q.sA = (long long)N * C; q.sW = (long long)M * C; q.sO = (long long)N * M;
-            gs.n = 1;
-            r = launch_gemm(gs, st);
+            r = gemm1(L.z + (size_t)PM * C, C, L.z, nullptr, L.sim, M, N, M, C, EPI_NONE, 1.f, nullptr, st, nullptr, nullptr, 0, P, (long long)N * C,
+                      (long long)M * C, (long long)N * M);
             if (r) return r;
             return sinkhorn_f32(P, N, M, L.sim, src_mask, tgt_mask, w->bin_score, cfg->sk_iters, DR_SK_OUT_CONF | mflag, L.x0, L.skws,
                                 L.skws_bytes, st, L.status);
@@ -525,49 +482,18 @@ int dr_denoise_loop_2d3d(const dr_loop2d3d_config* cfg, const dr_fusion_weights*
 
     rc = launch_f32_to_f64(x_T, L.x, NM, st);
     if (rc) return rc;
-    const double* ac = cfg->h_alphas_cumprod;
-    for (int k = 0; k < cfg->steps; ++k) {
-        const int tcur = cfg->h_times[k], tnext = cfg->h_times[k + 1];
-        // teacher forcing (parity tests): this step starts from the caller's state, not from the loop's own
-        if (trace && trace->force_x) DR_HIP_CHECK(hipMemcpyAsync(L.x, trace->force_x + (size_t)k * NM, NM * 8, hipMemcpyDeviceToDevice, st));
-        // warp from the noisy matrix: masks (src, tgt_da), no min-shift (EXP/model.py:830-846)
-        rc = sinkhorn_f64(P, N, M, L.x, nullptr, src_mask, tgt_mask_da, w->bin_score, cfg->sk_iters,
-                          DR_SK_OUT_CONF | DR_SK_OUT_F32 | mflag | (k > 0 ? strict : 0), L.wconf, L.skws, L.skws_bytes, st, L.status);
-        if (rc) return rc;
-        int* tk = nullptr;
-        if (trace && trace->topk_idx) {
-            const size_t Kf = (size_t)(int)((float)(N > M ? N : M) * cfg->sample_rate);
-            tk = trace->topk_idx + (size_t)k * P * Kf;
-            DR_HIP_CHECK(hipMemsetAsync(tk, 0xff, (size_t)P * Kf * 4, st));
-        }
-        if (trace && trace->wconf) DR_HIP_CHECK(hipMemcpyAsync(trace->wconf + (size_t)k * NM, L.wconf, NM * 4, hipMemcpyDeviceToDevice, st));
-        rc = launch_procrustes(L.wconf, s_pcd, t_pcd_da, src_mask, tgt_mask_da, P, N, M, 1, cfg->sample_rate, cfg->max_condition_num,
-                               L.R, L.t, L.Rf, L.tf, L.cond, L.ok, tk, st, L.pws, L.pws_bytes);
-        if (rc) return rc;
-        if (trace && trace->R_forwd) DR_HIP_CHECK(hipMemcpyAsync(trace->R_forwd + (size_t)k * P * 9, L.Rf, (size_t)P * 36, hipMemcpyDeviceToDevice, st));
-        if (trace && trace->t_forwd) DR_HIP_CHECK(hipMemcpyAsync(trace->t_forwd + (size_t)k * P * 3, L.tf, (size_t)P * 12, hipMemcpyDeviceToDevice, st));
-        if (trace && trace->cond) DR_HIP_CHECK(hipMemcpyAsync(trace->cond + (size_t)k * P, L.cond, (size_t)P * 8, hipMemcpyDeviceToDevice, st));
-        if (trace && trace->force_R) {           // teacher forcing: warp with the caller's pose (the fit above is traced all the same)
-            DR_HIP_CHECK(hipMemcpyAsync(L.Rf, trace->force_R + (size_t)k * P * 9, (size_t)P * 36, hipMemcpyDeviceToDevice, st));
-            DR_HIP_CHECK(hipMemcpyAsync(L.tf, trace->force_t + (size_t)k * P * 3, (size_t)P * 12, hipMemcpyDeviceToDevice, st));
-        }
-        rc = evaluate(L.Rf, L.tf);
-        if (rc) return rc;
-        if (trace && trace->x0) DR_HIP_CHECK(hipMemcpyAsync(trace->x0 + (size_t)k * NM, L.x0, NM * 4, hipMemcpyDeviceToDevice, st));
-        const double a = ac[tcur], an = ac[tnext];
-        DdimArgs d;
-        d.x = L.x; d.x0 = L.x0; d.shift = nullptr; d.noise = nullptr;
-        d.src_mask = src_mask; d.tgt_mask = tgt_mask_da;          // the in-place fill of :832-834 persists in x
-        d.N = N; d.M = M; d.first_step = (k == 0);
-        d.sra = sqrt(1.0 / a); d.srm1 = sqrt(1.0 / a - 1.0);
-        d.sigma = 1.0 * sqrt((1.0 - a / an) * (1.0 - an) / (1.0 - a));
-        d.c = sqrt(1.0 - an - d.sigma * d.sigma);
-        d.sqrt_an = (float)sqrt(an);
-        rc = launch_ddim(d, P, st);
-        if (rc) return rc;
-        if (trace && trace->x_next) DR_HIP_CHECK(hipMemcpyAsync(trace->x_next + (size_t)k * NM, L.x, NM * 8, hipMemcpyDeviceToDevice, st));
-    }
-    if (x_final) DR_HIP_CHECK(hipMemcpyAsync(x_final, L.x, NM * 8, hipMemcpyDeviceToDevice, st));
+    // -- the steps: the warp uses the masks (src, tgt_da) and no min-shift (EXP/model.py:830-846); the in-place fill of :832-834 with
+    // tgt_mask_da persists in x
+    SamplerArgs sa;
+    memset(&sa, 0, sizeof(sa));
+    sa.P = P; sa.N = N; sa.M = M; sa.steps = cfg->steps; sa.alphas_cumprod = cfg->h_alphas_cumprod; sa.times = cfg->h_times;
+    sa.sample_rate = cfg->sample_rate; sa.max_condition_num = cfg->max_condition_num; sa.sk_iters = cfg->sk_iters; sa.strict = strict;
+    sa.s_pcd = s_pcd; sa.warp_tgt_pcd = t_pcd_da; sa.src_mask = src_mask; sa.warp_tgt_mask = tgt_mask_da;
+    sa.warp_mflag = mflag; sa.use_mask_len = 1; sa.bin_score = w->bin_score; sa.trace = trace;
+    sa.x = L.x; sa.x_final = x_final; sa.x0 = L.x0; sa.wconf = L.wconf; sa.R = L.R; sa.t = L.t; sa.Rf = L.Rf; sa.tf = L.tf; sa.cond = L.cond; sa.ok = L.ok;
+    sa.skws = L.skws; sa.skws_bytes = L.skws_bytes; sa.pws = L.pws; sa.pws_bytes = L.pws_bytes; sa.status = L.status;
+    rc = reverse_sampling(sa, evaluate, st);
+    if (rc) return rc;
     // read-out: no min-shift, masks (src, tgt) (EXP/model.py:681-694)
     rc = sinkhorn_f64(P, N, M, L.x, nullptr, src_mask, tgt_mask, w->bin_score, cfg->sk_iters, DR_SK_OUT_CONF | mflag | strict, conf,
                       L.skws, L.skws_bytes, st, L.status);

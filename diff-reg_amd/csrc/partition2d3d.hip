@@ -8,7 +8,7 @@
 // Index work: every list comes out in the reference's order (torch.nonzero's row-major order, ascending distance inside a node) by a
 // count / scan / write compaction or a sort -- no atomics on floats, no order that depends on scheduling.  Distances are sums of squared
 // differences in float32.  Nothing of size (nodes x points) or (candidates x Ki x Kc) goes to memory.
-#include "kernels.h"
+#include "loop_common.h"
 
 namespace dr {
 namespace {
@@ -17,7 +17,6 @@ constexpr int PT_MAX_LIMIT = 128;      // point_limit of dr_point_to_node_partit
 constexpr int PT_NODE_CHUNK = 1024;    // nodes staged in LDS at a time (12 KB)
 constexpr int NC_MAX_KI = 256, NC_MAX_KC = 128;
 
-size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
 
 __device__ __forceinline__ float sq_dist3(float ax, float ay, float az, float bx, float by, float bz) {

@@ -1,9 +1,9 @@
 // train_common.h -- host helpers shared by the training entry points (train_layer.hip, train_fusion.hip, circle_loss.hip): a batched
 // transposition (the GEMM contracts along contiguous k: x W for a gradient w.r.t. the input and g^T x for a weight gradient need the transposed
-// operand), a two-operand add, the carving of caller memory into 256-byte aligned arrays and a GemmProblem filler.
+// operand), a two-operand add and a GemmProblem filler (the carving of caller memory into 256-byte aligned arrays: Carver of loop_common.h).
 #pragma once
 #include <string.h>
-#include "kernels.h"
+#include "loop_common.h"
 
 namespace dr {
 namespace {
@@ -61,16 +61,6 @@ __global__ __launch_bounds__(256) void add2_kernel(long long n4, const float4* _
     out[e] = make_float4(x.x + y.x, x.y + y.y, x.z + y.z, x.w + y.w);
 }
 
-struct Carve {
-    char* base; size_t off;
-    explicit Carve(void* p) : base((char*)p), off(0) {}
-    float* take(size_t n) {
-        off = (off + 255) & ~(size_t)255;
-        float* r = base ? reinterpret_cast<float*>(base + off) : nullptr;
-        off += n * sizeof(float);
-        return r;
-    }
-};
 inline int up4(int x) { return (x + 3) & ~3; }
 
 inline void gemm_problem(GemmProblem& p, const float* A, int lda, const float* A2, int lda2, int K1, const float* W, float* out, int ldo, int rows,

@@ -138,10 +138,10 @@ struct FSaved {
     float *q, *k, *v, *o, *a, *z, *e, *f, *st1, *st2;
     uint8_t* ones;
     static size_t carve(void* buf, FSaved& s, size_t R, size_t Q, int C) {
-        Carve c(buf);
-        s.q = c.take(R * C); s.k = c.take(Q * C); s.v = c.take(Q * C); s.o = c.take(R * C); s.a = c.take(R * C); s.z = c.take(R * C);
-        s.e = c.take(R * 2 * C); s.f = c.take(R * C); s.st1 = c.take(2 * R); s.st2 = c.take(2 * R);
-        s.ones = reinterpret_cast<uint8_t*>(c.take((R + 3) / 4));
+        Carver c(buf);
+        s.q = c.take<float>(R * C); s.k = c.take<float>(Q * C); s.v = c.take<float>(Q * C); s.o = c.take<float>(R * C); s.a = c.take<float>(R * C); s.z = c.take<float>(R * C);
+        s.e = c.take<float>(R * 2 * C); s.f = c.take<float>(R * C); s.st1 = c.take<float>(2 * R); s.st2 = c.take<float>(2 * R);
+        s.ones = reinterpret_cast<uint8_t*>(c.take<float>((R + 3) / 4));
         return c.off + 256;
     }
 };
@@ -210,13 +210,13 @@ size_t dr_fusion_layer_backward_workspace_bytes(int B, int H, int L, int S, int 
     if (B < 1 || L < 1 || S < 1 || C < 4 || H < 1) return 0;
     const size_t R = (size_t)B * L, Q = (size_t)B * S, R4 = up4((int)R), Q4 = up4((int)Q), C2 = 2 * (size_t)C;
     const size_t nR = nblk((int)R), nQ = nblk((int)Q);
-    Carve c(nullptr);
-    c.take(R * C); c.take(R * C2); c.take(R * C); c.take(R * C); c.take(R * C); c.take(R * C); c.take(Q * C); c.take(Q * C);  // g_f .. g_v
-    c.take(C2 * C); c.take(C2 * C); c.take((size_t)C * C); c.take((size_t)C * C); c.take(C2 * C);                          // transposed weights
-    c.take(C2 * R4); c.take(C * R4); c.take(C * R4); c.take(C * R4); c.take(C * Q4);                                       // e^T z^T o^T x^T y^T
-    c.take(C * R4); c.take(C2 * R4); c.take(C * R4); c.take(C * R4); c.take(C * Q4); c.take(C * Q4);                       // gradients^T
-    c.take(nR * C * 3); c.take(nR * C2); c.take(nR * C * 3); c.take(nR * C); c.take(nQ * C); c.take(nQ * C);             // column partials
-    c.take(dr_attention_backward_workspace_bytes(B, H, L) / sizeof(float) + 64);
+    Carver c(nullptr);
+    c.take<float>(R * C); c.take<float>(R * C2); c.take<float>(R * C); c.take<float>(R * C); c.take<float>(R * C); c.take<float>(R * C); c.take<float>(Q * C); c.take<float>(Q * C);  // g_f .. g_v
+    c.take<float>(C2 * C); c.take<float>(C2 * C); c.take<float>((size_t)C * C); c.take<float>((size_t)C * C); c.take<float>(C2 * C);                          // transposed weights
+    c.take<float>(C2 * R4); c.take<float>(C * R4); c.take<float>(C * R4); c.take<float>(C * R4); c.take<float>(C * Q4);                                       // e^T z^T o^T x^T y^T
+    c.take<float>(C * R4); c.take<float>(C2 * R4); c.take<float>(C * R4); c.take<float>(C * R4); c.take<float>(C * Q4); c.take<float>(C * Q4);                       // gradients^T
+    c.take<float>(nR * C * 3); c.take<float>(nR * C2); c.take<float>(nR * C * 3); c.take<float>(nR * C); c.take<float>(nQ * C); c.take<float>(nQ * C);             // column partials
+    c.take<float>(dr_attention_backward_workspace_bytes(B, H, L) / sizeof(float) + 64);
     return c.off + 256;
 }
 
@@ -229,19 +229,19 @@ int dr_fusion_layer_backward_f32(const dr_fusion_layer_weights* w, int C, int H,
     const int R = B * L, Q = B * S, d = C / H, R4 = up4(R), Q4 = up4(Q), C2 = 2 * C, nR = nblk(R), nQ = nblk(Q);
     FSaved sv;
     FSaved::carve(const_cast<void*>(saved), sv, R, Q, C);
-    Carve c(workspace);
-    float *g_f = c.take((size_t)R * C), *g_e = c.take((size_t)R * C2), *g_z = c.take((size_t)R * C), *g_a = c.take((size_t)R * C),
-          *g_o = c.take((size_t)R * C), *g_q = c.take((size_t)R * C), *g_k = c.take((size_t)Q * C), *g_v = c.take((size_t)Q * C);
-    float *TWs = c.take((size_t)C2 * C), *TWe = c.take((size_t)C2 * C), *TWl = c.take((size_t)C * C), *TWq = c.take((size_t)C * C),
-          *TWkv = c.take((size_t)C2 * C);
-    float *T_e = c.take((size_t)C2 * R4), *T_z = c.take((size_t)C * R4), *T_o = c.take((size_t)C * R4), *T_x = c.take((size_t)C * R4),
-          *T_y = c.take((size_t)C * Q4);
-    float *T_gf = c.take((size_t)C * R4), *T_ge = c.take((size_t)C2 * R4), *T_ga = c.take((size_t)C * R4), *T_gq = c.take((size_t)C * R4),
-          *T_gk = c.take((size_t)C * Q4), *T_gv = c.take((size_t)C * Q4);
-    float *p_ln2 = c.take((size_t)nR * C * 3), *p_exp = c.take((size_t)nR * C2), *p_ln1 = c.take((size_t)nR * C * 3), *p_q = c.take((size_t)nR * C),
-          *p_k = c.take((size_t)nQ * C), *p_v = c.take((size_t)nQ * C);
+    Carver c(workspace);
+    float *g_f = c.take<float>((size_t)R * C), *g_e = c.take<float>((size_t)R * C2), *g_z = c.take<float>((size_t)R * C), *g_a = c.take<float>((size_t)R * C),
+          *g_o = c.take<float>((size_t)R * C), *g_q = c.take<float>((size_t)R * C), *g_k = c.take<float>((size_t)Q * C), *g_v = c.take<float>((size_t)Q * C);
+    float *TWs = c.take<float>((size_t)C2 * C), *TWe = c.take<float>((size_t)C2 * C), *TWl = c.take<float>((size_t)C * C), *TWq = c.take<float>((size_t)C * C),
+          *TWkv = c.take<float>((size_t)C2 * C);
+    float *T_e = c.take<float>((size_t)C2 * R4), *T_z = c.take<float>((size_t)C * R4), *T_o = c.take<float>((size_t)C * R4), *T_x = c.take<float>((size_t)C * R4),
+          *T_y = c.take<float>((size_t)C * Q4);
+    float *T_gf = c.take<float>((size_t)C * R4), *T_ge = c.take<float>((size_t)C2 * R4), *T_ga = c.take<float>((size_t)C * R4), *T_gq = c.take<float>((size_t)C * R4),
+          *T_gk = c.take<float>((size_t)C * Q4), *T_gv = c.take<float>((size_t)C * Q4);
+    float *p_ln2 = c.take<float>((size_t)nR * C * 3), *p_exp = c.take<float>((size_t)nR * C2), *p_ln1 = c.take<float>((size_t)nR * C * 3), *p_q = c.take<float>((size_t)nR * C),
+          *p_k = c.take<float>((size_t)nQ * C), *p_v = c.take<float>((size_t)nQ * C);
     const size_t att_wsb = dr_attention_backward_workspace_bytes(B, H, L);
-    float* att_ws = c.take(att_wsb / sizeof(float) + 64);
+    float* att_ws = c.take<float>(att_wsb / sizeof(float) + 64);
     const size_t pRC = (size_t)nR * C;
     int rc;
     // ---- everything that only needs the forward's tensors is transposed first, in one launch

@@ -16,9 +16,9 @@ namespace {
 struct Saved {
     float *qw, *kw, *vw, *o, *m_pre, *m, *h, *f_pre, *st1, *st2;
     static size_t carve(void* buf, Saved& s, size_t R, size_t Q, int C) {
-        Carve c(buf);
-        s.qw = c.take(R * C); s.kw = c.take(Q * C); s.vw = c.take(Q * C); s.o = c.take(R * C); s.m_pre = c.take(R * C); s.m = c.take(R * C);
-        s.h = c.take(R * 2 * C); s.f_pre = c.take(R * C); s.st1 = c.take(2 * R); s.st2 = c.take(2 * R);
+        Carver c(buf);
+        s.qw = c.take<float>(R * C); s.kw = c.take<float>(Q * C); s.vw = c.take<float>(Q * C); s.o = c.take<float>(R * C); s.m_pre = c.take<float>(R * C); s.m = c.take<float>(R * C);
+        s.h = c.take<float>(R * 2 * C); s.f_pre = c.take<float>(R * C); s.st1 = c.take<float>(2 * R); s.st2 = c.take<float>(2 * R);
         return c.off + 256;
     }
 };
@@ -88,14 +88,14 @@ int dr_attention_layer_train_forward_f32(const dr_layer_weights* w, int C, int H
 size_t dr_attention_layer_backward_workspace_bytes(int B, int H, int L, int S, int C) {
     if (B < 1 || L < 1 || S < 1 || C < 4 || H < 1) return 0;
     const size_t R = (size_t)B * L, Q = (size_t)B * S, R4 = up4((int)R), Q4 = up4((int)Q);
-    Carve c(nullptr);
-    c.take(R * C); c.take(R * 2 * C); c.take(R * C); c.take(R * C); c.take(R * C); c.take(R * C);   // g_fpre, g_h, g_x1, g_m, g_mpre, g_o
-    c.take(R * C); c.take(Q * C); c.take(Q * C); c.take(R * C); c.take(Q * C);                      // g_qw, g_kw, g_vw, g_qpre, g_kpre
-    c.take((size_t)2 * C * C); c.take((size_t)4 * C * C); c.take((size_t)C * C); c.take((size_t)C * C); c.take((size_t)2 * C * C);   // W2^T, W0^T, Wm^T, Wq^T, [Wk^T | Wv^T]
-    c.take(C * R4); c.take(2 * C * R4); c.take(2 * C * R4); c.take(2 * C * R4); c.take(C * R4); c.take(C * R4); c.take(C * R4);   // transposed activations
-    c.take(C * Q4); c.take(C * Q4); c.take(C * Q4);
-    c.take(dr_layernorm_backward_workspace_bytes(C) / sizeof(float));
-    c.take(dr_attention_backward_workspace_bytes(B, H, L) / sizeof(float) + 64);
+    Carver c(nullptr);
+    c.take<float>(R * C); c.take<float>(R * 2 * C); c.take<float>(R * C); c.take<float>(R * C); c.take<float>(R * C); c.take<float>(R * C);   // g_fpre, g_h, g_x1, g_m, g_mpre, g_o
+    c.take<float>(R * C); c.take<float>(Q * C); c.take<float>(Q * C); c.take<float>(R * C); c.take<float>(Q * C);                      // g_qw, g_kw, g_vw, g_qpre, g_kpre
+    c.take<float>((size_t)2 * C * C); c.take<float>((size_t)4 * C * C); c.take<float>((size_t)C * C); c.take<float>((size_t)C * C); c.take<float>((size_t)2 * C * C);   // W2^T, W0^T, Wm^T, Wq^T, [Wk^T | Wv^T]
+    c.take<float>(C * R4); c.take<float>(2 * C * R4); c.take<float>(2 * C * R4); c.take<float>(2 * C * R4); c.take<float>(C * R4); c.take<float>(C * R4); c.take<float>(C * R4);   // transposed activations
+    c.take<float>(C * Q4); c.take<float>(C * Q4); c.take<float>(C * Q4);
+    c.take<float>(dr_layernorm_backward_workspace_bytes(C) / sizeof(float));
+    c.take<float>(dr_attention_backward_workspace_bytes(B, H, L) / sizeof(float) + 64);
     return c.off + 256;
 }
 
@@ -112,19 +112,19 @@ int dr_attention_layer_backward_f32(const dr_layer_weights* w, int C, int H, int
     const int R = B * L, Q = B * S, d = C / H, R4 = up4(R), Q4 = up4(Q), C2 = 2 * C;
     Saved sv;
     Saved::carve(const_cast<void*>(saved), sv, R, Q, C);
-    Carve c(workspace);
-    float *g_fpre = c.take((size_t)R * C), *g_h = c.take((size_t)R * C2), *g_x1 = c.take((size_t)R * C), *g_m = c.take((size_t)R * C),
-          *g_mpre = c.take((size_t)R * C), *g_o = c.take((size_t)R * C);
-    float *g_qw = c.take((size_t)R * C), *g_kw = c.take((size_t)Q * C), *g_vw = c.take((size_t)Q * C), *g_qpre = c.take((size_t)R * C),
-          *g_kpre = c.take((size_t)Q * C);
-    float *TW2 = c.take((size_t)C2 * C), *TW0 = c.take((size_t)C2 * C2), *TWm = c.take((size_t)C * C), *TWq = c.take((size_t)C * C),
-          *TWkv = c.take((size_t)C * C2);
-    float *T_gf = c.take((size_t)C * R4), *T_h = c.take((size_t)C2 * R4), *T_gh = c.take((size_t)C2 * R4), *T_cat = c.take((size_t)C2 * R4),
-          *T_gm = c.take((size_t)C * R4), *T_o = c.take((size_t)C * R4), *T_gq = c.take((size_t)C * R4);
-    float *T_gk = c.take((size_t)C * Q4), *T_gv = c.take((size_t)C * Q4), *T_y = c.take((size_t)C * Q4);
-    float* ln_ws = c.take(dr_layernorm_backward_workspace_bytes(C) / sizeof(float));
+    Carver c(workspace);
+    float *g_fpre = c.take<float>((size_t)R * C), *g_h = c.take<float>((size_t)R * C2), *g_x1 = c.take<float>((size_t)R * C), *g_m = c.take<float>((size_t)R * C),
+          *g_mpre = c.take<float>((size_t)R * C), *g_o = c.take<float>((size_t)R * C);
+    float *g_qw = c.take<float>((size_t)R * C), *g_kw = c.take<float>((size_t)Q * C), *g_vw = c.take<float>((size_t)Q * C), *g_qpre = c.take<float>((size_t)R * C),
+          *g_kpre = c.take<float>((size_t)Q * C);
+    float *TW2 = c.take<float>((size_t)C2 * C), *TW0 = c.take<float>((size_t)C2 * C2), *TWm = c.take<float>((size_t)C * C), *TWq = c.take<float>((size_t)C * C),
+          *TWkv = c.take<float>((size_t)C * C2);
+    float *T_gf = c.take<float>((size_t)C * R4), *T_h = c.take<float>((size_t)C2 * R4), *T_gh = c.take<float>((size_t)C2 * R4), *T_cat = c.take<float>((size_t)C2 * R4),
+          *T_gm = c.take<float>((size_t)C * R4), *T_o = c.take<float>((size_t)C * R4), *T_gq = c.take<float>((size_t)C * R4);
+    float *T_gk = c.take<float>((size_t)C * Q4), *T_gv = c.take<float>((size_t)C * Q4), *T_y = c.take<float>((size_t)C * Q4);
+    float* ln_ws = c.take<float>(dr_layernorm_backward_workspace_bytes(C) / sizeof(float));
     const size_t att_wsb = dr_attention_backward_workspace_bytes(B, H, L);
-    float* att_ws = c.take(att_wsb / sizeof(float) + 64);
+    float* att_ws = c.take<float>(att_wsb / sizeof(float) + 64);
     int rc;
     // ---- everything that only needs the forward's tensors is transposed first, in one launch
     Transposer T;

@@ -270,3 +270,63 @@ def test_round_6_entries_refuse_bad_calls():
     # the status word of a loop workspace
     assert r.dr_denoise_loop_status(None, st, 1) == EINVAL
     torch.cuda.synchronize()
+
+
+def workspace_size_cases():
+    """-> {size function: {case: thunk}}: every workspace / prepack / saved-bytes function whose value comes out of the library's memory carver,
+    at shapes small enough to cost nothing that cross the carver's branches -- plane path off (a head width the packer refuses, C = 132, and
+    few token rows), forced (flag 4) and refused (flag 8), the size rule's own threshold (4096 token rows), a token count on either side of
+    the plane GEMM's k-split exchange limit ((T + 63) / 64 + 2 against 160 row blocks), both 3D variants, DR_LOOP_STRICT_F64 (flag 1) on and off."""
+    from diffreg_hip import lib
+    r = lib.raw()
+    shapes = ((1, 32, 48), (2, 64, 96), (8, 256, 255), (8, 256, 256), (1, 5056, 5056), (1, 5056, 5120))
+    cases = {}
+
+    def add(fn, case, *args):
+        cases.setdefault(fn, {})[case] = lambda: int(getattr(r, fn)(*args))
+
+    for flags in (0, 1, 4, 5, 8, 9):
+        for C in (132, 256, 432, 528):
+            for variant in (0, 1):
+                cfg = lib.LoopConfig()
+                cfg.variant, cfg.C, cfg.H, cfg.n_layers, cfg.steps, cfg.sk_iters, cfg.flags = variant, C, 4, 6, 2, 3, flags
+                tag = "variant=%d C=%d H=4 layers=6 flags=%d" % (variant, C, flags)
+                add("dr_loop_prepack_bytes", tag, ctypes.byref(cfg))
+                for P, N, M in shapes:
+                    add("dr_denoise_loop_workspace_bytes", "%s P=%d N=%d M=%d" % (tag, P, N, M), ctypes.byref(cfg), P, N, M)
+        for C in (132, 256):
+            cfg = lib.Loop2D3DConfig()
+            cfg.C, cfg.H, cfg.n_layers, cfg.img_dim, cfg.dino_dim, cfg.pcd_dim, cfg.steps, cfg.sk_iters, cfg.flags = C, 4, 6, 512, 1024, 512, 2, 3, flags
+            tag = "C=%d H=4 layers=6 flags=%d" % (C, flags)
+            add("dr_loop2d3d_prepack_bytes", tag, ctypes.byref(cfg))
+            for P, N, M in shapes:
+                add("dr_denoise_loop_2d3d_workspace_bytes", "%s P=%d N=%d M=%d" % (tag, P, N, M), ctypes.byref(cfg), P, N, M)
+    for B, L, S, C in ((1, 32, 48, 132), (2, 64, 96, 256), (2, 101, 75, 432), (3, 7, 5, 8)):
+        tag = "B=%d L=%d S=%d C=%d" % (B, L, S, C)
+        add("dr_attention_layer_workspace_bytes", tag, B, L, S, C)
+        add("dr_attention_layer_train_saved_bytes", tag, B, L, S, C)
+        add("dr_fusion_layer_train_saved_bytes", tag, B, L, S, C)
+        add("dr_attention_layer_backward_workspace_bytes", tag + " H=4", B, 4, L, S, C)
+        add("dr_fusion_layer_backward_workspace_bytes", tag + " H=4", B, 4, L, S, C)
+    for M, N, C in ((1, 1, 4), (48, 32, 132), (97, 130, 256)):
+        add("dr_circle_loss_workspace_bytes", "M=%d N=%d C=%d" % (M, N, C), M, N, C)
+    for M in (1, 63, 64, 1000):
+        add("dr_fine_loss_saved_bytes", "M=%d" % M, M)
+    return cases
+
+
+def test_workspace_sizes_are_the_recorded_ones():
+    """tests/golden/workspace_bytes.json holds what these functions returned before the loops, the single-op entries and the training entries
+    came to share one carver (names, shapes and integers; 0 = a shape the function refuses, e.g. a prepack of a head width the packer does
+    not take): the layouts behind them are an ABI of their own -- callers size and keep these buffers -- and must not move.  Nothing is launched."""
+    import json
+    with open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "workspace_bytes.json")) as f:
+        want = json.load(f)
+    cases = workspace_size_cases()
+    assert set(cases) == set(want) and len(want) == 11
+    for fn, per in cases.items():
+        assert set(per) == set(want[fn]), fn
+        got = {case: thunk() for case, thunk in per.items()}
+        wrong = {case: (got[case], want[fn][case]) for case in per if got[case] != want[fn][case]}
+        assert not wrong, (fn, wrong)
+        assert any(v > 0 for v in got.values()), fn
