@@ -114,6 +114,11 @@ struct PlanesWs {
     char *qkv_img, *kvc_img;                 // q | k | v images (three images of H dp columns, back to back); cached k | v of layer 1
     float *qkv_bnd, *kvc_bnd;                // [3][T] / [2][T]
     float* grp_x;                            // [2 P] bound of x per key group (src groups, then tgt groups)
+    // step-invariant projections, evaluated once per call (fill_step_invariants; `hoist`: diagnostics knob DR_LOOP_HOIST, default on):
+    bool hoist;
+    float* pre0;                             // [PN][2 H dp] layer 0, src rows: q | k in front of the rotary step (the src code moves, feat0 does not)
+    char* v0_img; float *v0_bnd, *grp0;      // layer 0, src rows: the V image, its bounds [PN]; [P] bound of feat0 per src group
+    char* q1_img; float* q1_bnd;             // layer 1, second cross call: q image of the tgt rows (PM rows), its row bounds [T] (token-indexed)
     float* csT;                              // [T][C/2][2] the rotary tables interleaved (cos, sin)
     size_t qkv_stride;                       // bytes from the q image to the k image (= to the next: v)
     size_t side_C, side_att, side_hid;      // byte offset of the tgt part inside an image of K = C / H dp / 2C
@@ -136,6 +141,7 @@ struct PlanesWs {
         w.qkv_img = c.take<char>(3 * w.qkv_stride); w.qkv_bnd = c.take<float>(3 * (size_t)T);
         w.kvc_img = c.take<char>(2 * w.qkv_stride); w.kvc_bnd = c.take<float>(2 * (size_t)T);
         w.grp_x = c.take<float>(2 * (size_t)P);
+        w.hoist = false;                         // (carve_hoist: the buffers live in memory the plane path leaves idle)
         w.csT = c.take<float>((size_t)T * C);
         w.own_pack = c.take<char>(Prepack::carve(nullptr, cfg, nullptr));
         // (only launches of at most half a chip of 64-row workgroups are split: 128 row blocks on 256 CUs)
@@ -143,6 +149,17 @@ struct PlanesWs {
         w.xk_buf = xk ? c.take<float>(pgemm_xk_buf_bytes(pgemm_bn(C)) / 4) : nullptr;
         w.xk_flags = xk ? c.take<unsigned>(pgemm_xk_flag_bytes() / 4) : nullptr;
         w.xk_epoch = 0; w.status = nullptr;
+    }
+    // The buffers of the once-per-call projections take no workspace of their own (the sizes the callers keep do not move): they are laid into
+    // `bytes` at `mem` (nullptr: a size query), memory that no launch of the plane path touches.  Where they do not fit -- forced plane paths of
+    // a few rows, whose images are mostly padding -- the loop keeps the per-step projections.
+    static void carve_hoist(PlanesWs& w, char* mem, size_t bytes, const dr_loop_config& cfg, int P, int N, int M) {
+        const int PN = P * N, PM = P * M, T = PN + PM, Cq = cfg.H * ((cfg.C / cfg.H + 15) / 16 * 16);
+        Carver c(mem);
+        w.pre0 = c.take<float>((size_t)PN * 2 * Cq);
+        w.v0_img = c.take<char>(plane_image_bytes(PN, Cq)); w.v0_bnd = c.take<float>(PN); w.grp0 = c.take<float>(P);
+        w.q1_img = c.take<char>(plane_image_bytes(PM, Cq)); w.q1_bnd = c.take<float>(T);
+        w.hoist = c.off <= bytes && env_knob("DR_LOOP_HOIST", 1) != 0;
     }
 };
 
@@ -255,9 +272,16 @@ static void xk_assign(const PlanesWs& pw, int C, PgProblem& p, size_t& next, siz
 }
 static size_t xk_wide_units(const PgProblem& p) { return (size_t)(p.rows + 127) / 128 * p.nblk * 2; }
 
+// what a call leaves in / takes from the once-per-call buffers of fill_step_invariants (PlanesWs: pre0, v0_*, q1_*)
+struct PlHoist {
+    bool l0_fill = false;   // layer 0, src rows: project q | k up to the rotary step (-> pre0) and V in its final form (-> v0_img) and return
+    bool l0_use = false;    // layer 0, src rows: no projection launch -- q | k images by rot_images from pre0, V is v0_img
+    bool q1_fill = false;   // project ONLY q of the x rows (tgt) into q1_img / q1_bnd and return
+    bool q1_use = false;    // q of the x rows (tgt) is q1_img / q1_bnd: the projection launch carries K | V of the y rows only
+};
 static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, const Tok& xin, int xs, const Tok& yin, int ys,
                              const Tok& out, const Family& f1, const Family* f2, hipStream_t st, const float* kv_cached = nullptr,
-                             float* kv_store = nullptr) {
+                             float* kv_store = nullptr, const PlHoist& hz = PlHoist()) {
     const int C = X.C, H = X.H, PN = X.P * X.N, PM = X.P * X.M, halfC = C / 2, d = C / H, nC = C / 16, dp = X.pp->dp;
     const PrepackLayer& L = X.pp->L[l];
     const PlanesWs& pw = *X.pw;
@@ -283,7 +307,7 @@ static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, c
     // bound of the keys' source rows per group (pair x side): taken inside the projection's own kernel when a group is a whole number of
     // workgroups (the 480 five-microsecond launches of a 20-step loop were 2 - 4 % of it), by a kernel of its own otherwise
     const bool grp_inline = X.N % 128 == 0 && X.M % 128 == 0 && env_knob("DR_LOOP_GRP_INLINE", 1) != 0;
-    if (!cached && !grp_inline) {
+    if (!cached && !grp_inline && !hz.l0_fill && !hz.l0_use && !hz.q1_fill) {
         for (int side = 1; side <= 2 && rc_ok; ++side)
             if (ys & side) rc_ok = launch_group_max(yin.bnd + r0(side), X.P, side == SIDE_TGT ? X.M : X.N, pw.grp_x + (side == SIDE_TGT ? X.P : 0), st) == DR_OK;
         if (!rc_ok) return DR_ELAUNCH;
@@ -306,16 +330,56 @@ static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, c
         ++pw.xk_epoch;
         return launch_pgemm(g, st);
     }
-    const bool self = xs == ys && xin.img == yin.img && !cached;
-    if (self) {
-        for_sides(xs, [&](int side) { proj(xin, side, 0, 3, pw.qkv_img, pw.qkv_bnd, 3, 6); });
-    } else {
-        for_sides(xs, [&](int side) { proj(xin, side, 0, 1, pw.qkv_img, pw.qkv_bnd, 1, 0); });
-        if (!cached) for_sides(ys, [&](int side) { proj(yin, side, 1, 2, kv_img, kv_bnd, 1, 3); });
+    // The once-per-call launches stand in for problems of a per-step launch: they take that launch's geometry (PgBatch::wg_as), so that the
+    // accumulators are summed in its order and the images come out bit for bit as the per-step launch writes them.
+    const int rbS = (PN + 127) / 128, rbT = (PM + 127) / 128;
+    if (hz.l0_fill) {
+        rc = launch_group_max(xin.bnd, X.P, X.N, pw.grp0, st);
+        if (rc) return rc;
+        // q | k: the value in front of the rotary step (the fp32 epilogue without rotary: the same accumulators, column and row scales)
+        proj(xin, SIDE_SRC, 0, 2, pw.qkv_img, pw.qkv_bnd, 0, 0);
+        g.p[0].mode = PG_F32; g.p[0].pimg = nullptr; g.p[0].pbnd = nullptr;
+        g.p[0].out = pw.pre0; g.p[0].ldo = 2 * Cq; g.p[0].blk_stride = Cq;
+        g.wg_as = 3 * rbS;
+        ++pw.xk_epoch;
+        rc = launch_pgemm(g, st);
+        if (rc) return rc;
+        reset();
+        proj(xin, SIDE_SRC, 2, 1, pw.v0_img, pw.v0_bnd, 0, 1);
+        g.p[0].grp_bnd = pw.grp0; g.p[0].grp_first = 0;
+        g.wg_as = 3 * rbS;
+        ++pw.xk_epoch;
+        return launch_pgemm(g, st);
     }
-    ++pw.xk_epoch;
-    rc = launch_pgemm(g, st);
-    if (rc) return rc;
+    if (hz.q1_fill) {
+        proj(xin, SIDE_TGT, 0, 1, pw.qkv_img, pw.qkv_bnd, 1, 0);
+        g.p[0].pimg = pw.q1_img; g.p[0].pbnd = pw.q1_bnd + PN;
+        g.wg_as = rbT + 2 * rbS;
+        ++pw.xk_epoch;
+        return launch_pgemm(g, st);
+    }
+    const bool self = xs == ys && xin.img == yin.img && !cached;
+    if (hz.l0_use) {
+        RotImgArgs r;
+        memset(&r, 0, sizeof(r));
+        r.x = pw.pre0; r.ldx = 2 * Cq; r.x_blk = Cq; r.rows = PN; r.C = Cq; r.nblk = 2;
+        r.csT = pw.csT; r.rot_mask = 3; r.rot_C = C; r.rot_piece_len = d; r.rot_piece_pad = dp; r.scale = 1.f;
+        r.bnd0 = xin.bnd; r.wnorm = L.qkv.wnorm; r.wide_form = L.qkv.sub == 2; r.grp_bnd = pw.grp0; r.grp_mask = 2; r.grp_first = 0; r.grp_rows = X.N;
+        r.pimg = pw.qkv_img; r.p_nct = nq; r.pbnd = pw.qkv_bnd; r.pimg_blk_stride = (long long)pw.qkv_stride; r.pbnd_blk_stride = T;
+        rc = launch_rot_images(r, st);
+        if (rc) return rc;
+    } else {
+        if (self) {
+            for_sides(xs, [&](int side) { proj(xin, side, 0, 3, pw.qkv_img, pw.qkv_bnd, 3, 6); });
+        } else {
+            if (!hz.q1_use) for_sides(xs, [&](int side) { proj(xin, side, 0, 1, pw.qkv_img, pw.qkv_bnd, 1, 0); });
+            else g.wg_as = rbT + 2 * rbS;
+            if (!cached) for_sides(ys, [&](int side) { proj(yin, side, 1, 2, kv_img, kv_bnd, 1, 3); });
+        }
+        ++pw.xk_epoch;
+        rc = launch_pgemm(g, st);
+        if (rc) return rc;
+    }
 
     // ---- attention on the images -> plane image of the heads' outputs (head h at k = h dp)
     AttnArgs a;
@@ -334,6 +398,8 @@ static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, c
         a.kimg[0] = kimg; a.kimg[1] = kimg + pw.side_att;
         a.vimg[0] = kimg + pw.qkv_stride; a.vimg[1] = kimg + pw.qkv_stride + pw.side_att;
         a.qbnd = pw.qkv_bnd; a.kgb = kb; a.vgb = kb + T;
+        if (hz.l0_use) { a.vimg[0] = pw.v0_img; a.vgb = pw.v0_bnd; }          // (src keys only: rows below PN)
+        if (hz.q1_use) { a.qimg[1] = pw.q1_img; a.qbnd = pw.q1_bnd; }          // (tgt queries only: rows from PN)
         a.f16_single = X.attn_f16;
     }
     rc = launch_attention(a, st);
@@ -391,8 +457,12 @@ struct DenoiseWs {
     static void carve(Carver& c, DenoiseWs& w, const dr_loop_config& cfg, int P, int N, int M) {
         const int C = cfg.C;
         const size_t T = (size_t)P * (N + M);
+        const size_t lw_begin = align256(c.off);
         LayerWs::carve(c, w.lw, T, C);
+        const size_t lw_end = c.off;
         PlanesWs::carve(c, w.pl, cfg, P, N, M);
+        // (the activations of the f32-input layers: layer_call's alone -- a call on the plane path never reads or writes them)
+        if (w.pl.on) PlanesWs::carve_hoist(w.pl, c.base ? c.base + lw_begin : nullptr, lw_end - lw_begin, cfg, P, N, M);
         w.tgt_l0 = c.take<float>(T * C);
         w.kv_l1 = c.take<float>(T * 2 * C);
         w.fa = c.take<float>(T * C);
@@ -409,17 +479,27 @@ struct DenoiseWs {
 // then the matching head's projection + N x M similarity (matching.py:173-207).  PE tables must be
 // filled.  On return *final points at the buffer holding the refined features and ws.sim holds sim.
 // The tgt cloud never moves and layer 0 is a self layer, so the tgt half of layer 0 and the K|V projections of
-// layer 1's first cross call do not depend on the step (the reference recomputes them 20 times): fill_tgt_cache
+// layer 1's first cross call do not depend on the step (the reference recomputes them 20 times): fill_step_invariants
 // evaluates them once per loop, denoiser_and_sim(use_cache) reuses them.  Results are bit-identical.
-static int fill_tgt_cache(const dr_loop_config& cfg, const dr_loop_weights& w, int P, int N, int M, const float* feat0,
+// On the plane path two more pieces stay from step to step (PlanesWs::hoist): layer 0's q | k | v projections of the SRC rows up to the rotary
+// step (their input is the caller's feat0; only the src position code moves: a row-wise kernel applies it per step, V is final), and the q image of
+// layer 1's second cross call (tgt_l0 and the tgt code).
+static int fill_step_invariants(const dr_loop_config& cfg, const dr_loop_weights& w, int P, int N, int M, const float* feat0,
                           const uint8_t* tokmask, DenoiseWs& ws, hipStream_t st) {
     const int C = cfg.C, H = cfg.H, PN = P * N, PM = P * M;
     const Family self_t{PN, M, PN, M};
     if (ws.pl.on) {
         const PlCtx X{ws.pp, &ws.pl, &ws.lw, C, H, P, N, M, ws.cosT, ws.sinT, tokmask, (cfg.flags & DR_LOOP_ATTN_F16) ? 1 : 0};
         int rc = layer_call_planes(X, w.layers[0], 0, ws.pl.feat0, SIDE_TGT, ws.pl.feat0, SIDE_TGT, ws.pl.tgt_l0, self_t, nullptr, st);
+        if (rc == DR_OK && ws.pl.hoist) {
+            PlHoist hz; hz.l0_fill = true;
+            rc = layer_call_planes(X, w.layers[0], 0, ws.pl.feat0, SIDE_SRC, ws.pl.feat0, SIDE_SRC, ws.pl.tgt_l0, Family{0, N, 0, N}, nullptr, st, nullptr, nullptr, hz);
+        }
         if (rc || cfg.n_layers < 2) return rc;
-        return layer_call_planes(X, w.layers[1], 1, ws.pl.tgt_l0, 0, ws.pl.tgt_l0, SIDE_TGT, ws.pl.tgt_l0, self_t, nullptr, st, nullptr, ws.kv_l1);
+        rc = layer_call_planes(X, w.layers[1], 1, ws.pl.tgt_l0, 0, ws.pl.tgt_l0, SIDE_TGT, ws.pl.tgt_l0, self_t, nullptr, st, nullptr, ws.kv_l1);
+        if (rc || !ws.pl.hoist) return rc;
+        PlHoist hz; hz.q1_fill = true;
+        return layer_call_planes(X, w.layers[1], 1, ws.pl.tgt_l0, SIDE_TGT, ws.pl.tgt_l0, 0, ws.pl.tgt_l0, self_t, nullptr, st, nullptr, nullptr, hz);
     }
     int rc = layer_call(w.layers[0], C, H, P, feat0, PN, PM, feat0, PN, PM, ws.cosT, ws.sinT, tokmask, self_t, nullptr, ws.lw,
                         ws.tgt_l0, st);
@@ -454,7 +534,8 @@ static int denoiser_and_sim(const dr_loop_config& cfg, const dr_loop_weights& w,
                 // the tgt half of layer 0 is the cache (rows, plane image, bounds): the src half is written beside it, into the cache's
                 // own token buffer -- layer 1 reads both halves there and nothing later writes to it (no copy of the cached half)
                 nxt = &ws.pl.tgt_l0;
-                rc = layer_call_planes(X, w.layers[0], 0, *cur, SIDE_SRC, *cur, SIDE_SRC, *nxt, self_s, nullptr, st);
+                PlHoist hz; hz.l0_use = ws.pl.hoist;
+                rc = layer_call_planes(X, w.layers[0], 0, *cur, SIDE_SRC, *cur, SIDE_SRC, *nxt, self_s, nullptr, st, nullptr, nullptr, hz);
                 if (rc) return rc;
                 cur = nxt;
                 continue;
@@ -466,7 +547,9 @@ static int denoiser_and_sim(const dr_loop_config& cfg, const dr_loop_weights& w,
                 rc = layer_call_planes(X, w.layers[l], l, *cur, SIDE_SRC, *cur, SIDE_TGT, *nxt, cross_s, nullptr, st,
                                        (use_cache && l == 1) ? ws.kv_l1 : nullptr);
                 if (rc) return rc;
-                rc = layer_call_planes(X, w.layers[l], l, *cur, SIDE_TGT, *nxt, SIDE_SRC, *nxt, cross_t, nullptr, st);
+                // (layer 1 with the cache: the queries are tgt_l0's rows under the tgt code -- projected once per call)
+                PlHoist hz; hz.q1_use = use_cache && l == 1 && ws.pl.hoist;
+                rc = layer_call_planes(X, w.layers[l], l, *cur, SIDE_TGT, *nxt, SIDE_SRC, *nxt, cross_t, nullptr, st, nullptr, nullptr, hz);
                 if (rc) return rc;
             }
             cur = nxt;
@@ -802,7 +885,7 @@ int dr_denoise_loop(const dr_loop_config* cfg, const dr_loop_weights* w, int P, 
     // every step, transformero.py:166)
     rc = fill_pe(*cfg, *w, P, N, M, s_pcd, nullptr, nullptr, t_pcd, false, true, L.dw, st);
     if (rc) return rc;
-    rc = fill_tgt_cache(*cfg, *w, P, N, M, L.feat0, tokmask, L.dw, st);
+    rc = fill_step_invariants(*cfg, *w, P, N, M, L.feat0, tokmask, L.dw, st);
     if (rc) return rc;
 
     // -- the steps: x <- x - x.min() first (3D only), per-step noise (4D only); the denoiser of a step is the position code of the warped

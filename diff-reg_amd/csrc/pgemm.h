@@ -71,7 +71,9 @@ struct PgProblem {
 constexpr int PG_XK_MAX_RB = 160;                                  // row blocks (of 64 rows) a split launch can have: xk_buf / xk_flags are sized for it
 inline size_t pgemm_xk_buf_bytes(int bn) { return (size_t)PG_XK_MAX_RB * 2 * 4 * (bn / 64) * 2 * 64 * 16; }
 inline size_t pgemm_xk_flag_bytes() { return (size_t)PG_XK_MAX_RB * 2 * sizeof(unsigned); }
-struct PgBatch { PgProblem p[3]; int n; int dbg; };   // dbg (debug knob DR_PG_NOEPI): 1 = return behind the main loop (timing builds)
+struct PgBatch { PgProblem p[3]; int n; int dbg; int wg_as; };   // dbg (debug knob DR_PG_NOEPI): 1 = return behind the main loop (timing builds)
+// wg_as > 0: choose the geometry (64- / 128-row workgroups, k split of the wide-wave tiles) as a launch of wg_as 128-row workgroups would -- a
+// launch that evaluates, once per call, some of the problems of a per-step launch must sum in that launch's order to give its bits
 
 bool pgemm_shape_ok(int C);                      // column-block widths the kernel is built for
 int pgemm_bn(int C);                             // rows of a packed weight block (256 for C <= 256, 448 for C <= 448, 576 above)
@@ -93,6 +95,22 @@ void pgemm16w_weight_view(void* buf, int nblk, int nct, PgW* view);
 int pgemm16w_pack_weights_block(const float* W, int C, int K, int piece_len, int piece_pad, const PgW& view, int nb, hipStream_t st, int out_len = 0,
                                 int out_pad = 0);
 int launch_group_max(const float* bnd, int ngroups, int grp_rows, float* out, hipStream_t st);
+
+// The tail of a PG_PLANES epilogue on its own (rot_images_kernel, the twin of pgemm_kernel's finish_round + image store): fp32 rows that a
+// PG_F32 launch with rot_mask = 0 wrote (block b at column b * x_blk) -> rotary, scale, bound, plane image -- byte for byte what the PG_PLANES
+// launch of the same problem writes.  Serves projections whose input stays while the rotary code moves (layer 0 of the denoise loop).
+struct RotImgArgs {
+    const float* x; int ldx, x_blk;     // the rows in front of the rotary step
+    int rows, C, nblk;                  // C: columns of a block (= of its image), C % 16 == 0; nblk <= 3
+    const float* csT; int rot_mask, rot_C, rot_piece_len, rot_piece_pad; float scale;   // as in PgProblem
+    const float* bnd0;                  // bound of the GEMM's input rows
+    const float* wnorm;                 // [nblk] PgW::wnorm of the blocks
+    int wide_form;                      // the weights are in the wide-wave layout (PgW::sub == 2): the launch stood in for runs pgemm16w_kernel, whose
+                                        // rotary rounds differently from pgemm_kernel's (see the kernel)
+    const float* grp_bnd; int grp_mask, grp_first, grp_rows;   // as in PgProblem; grp_bnd must be given where grp_mask != 0
+    char* pimg; int p_nct; float* pbnd; long long pimg_blk_stride, pbnd_blk_stride;   // every block its own image / bound array
+};
+int launch_rot_images(const RotImgArgs& a, hipStream_t st);
 
 // fp32 rows -> plane image with bound[row] = max |x[row][:]| (the external features entering the first layer)
 int launch_planes_from_f32(const float* x, int ldx, int rows, int K, char* img, float* bnd, hipStream_t st, const float* bnd_in = nullptr);

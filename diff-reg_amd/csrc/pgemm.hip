@@ -1631,6 +1631,7 @@ static int launch_pgemm16w(const PgBatch& g, hipStream_t st) {
         ksplit = ksplit && p.xk_buf && p.xk_flags && tl_ <= p.xk_cap && (p.A1 ? (p.nc0 >= 5 && p.nc1 >= 5) : p.nc0 >= 12);
         tiles += tl_;
     }
+    if (g.wg_as > 0) tiles = 2L * g.wg_as;                     // (pgemm.h: split as the launch this one stands in for would)
     ksplit = ksplit && 2 * tiles <= (long)device_cu_count();
     for (int i = 0; i < g.n; ++i) {
         const PgProblem& p = g.p[i];
@@ -1664,6 +1665,7 @@ int launch_pgemm(const PgBatch& g, hipStream_t st) {
     const int n_cu = device_cu_count();
     long wg128 = 0;
     for (int i = 0; i < g.n; ++i) wg128 += (long)((g.p[i].rows + 127) / 128) * g.p[i].nblk;
+    if (g.wg_as > 0) wg128 = g.wg_as;                          // (pgemm.h: the geometry of the launch this one stands in for)
     // 64-row workgroups up to HALF a chip of 128-row ones: above that they would run in two rounds, slower than one round of 128-row workgroups on
     // some of the CUs (cfg5 at 8 pairs: 192 of them, 28.4 -> 27.6 ms per call; DR_PG_HALF_PCT: the threshold in percent of the CU count)
     const bool half = bn == G9::BN || half_env == 2 || (half_env == 1 && wg128 * 100 < (long)n_cu * env_knob("DR_PG_HALF_PCT", 51));
@@ -1809,6 +1811,87 @@ __global__ __launch_bounds__(256) void group_max_kernel(const float* __restrict_
 int launch_group_max(const float* bnd, int ngroups, int grp_rows, float* out, hipStream_t st) {
     if (ngroups < 1) return DR_OK;
     hipLaunchKernelGGL(group_max_kernel, dim3((ngroups + 3) / 4), dim3(256), 0, st, bnd, ngroups, grp_rows, out);
+    DR_LAUNCH_CHECK();
+    return DR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// rot_images_kernel: rotary + scale + bound + plane image of rows whose projection was evaluated earlier (pgemm.h: RotImgArgs).  The TWIN of
+// the PG_PLANES epilogue of pgemm_kernel / pgemm16w_kernel (PG_TABLE_INDEX, finish_round, s_bound of stage_inputs, the image store): the same
+// rotary arithmetic in the same operand order and rounding, the same a-priori bound, the same split -- a change there is a change here.
+// A thread owns 8 columns of a row (one hi and one lo unit of a k-chunk) in every block: the table entries are loaded once for q and k.  Four
+// lanes cover 32 columns of a row (128-byte reads), a wave 16 rows x 2 chunks (two 1 KB runs of the image), a workgroup 64 rows.
+// ---------------------------------------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void rot_images_kernel(RotImgArgs A) {
+    const int t = threadIdx.x, row = blockIdx.x * 64 + (t >> 2), j = t & 3;
+    const int kc = 2 * blockIdx.y + (j >> 1), hh = j & 1, col0 = kc * 16 + hh * 8;
+    if (row >= A.rows || col0 >= A.C) return;
+    const int halfC = A.rot_C >> 1, rpad = A.rot_piece_pad, rlen = A.rot_piece_len;
+    float4 tb[2];
+    if (A.rot_mask) {
+        const float* pp = A.csT + (size_t)row * halfC * 2;
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            int col = min(col0 + 4 * i, A.C - 4);
+            if (rpad > 0) { const int hq = col / rpad; col = hq * rlen + min(col - hq * rpad, rlen - 4); }
+            if (col >= A.rot_C) col %= A.rot_C;
+            const float4 cs = *reinterpret_cast<const float4*>(pp + 2 * (col >> 1));
+            tb[i] = make_float4(cs.x, cs.z, cs.y, cs.w);
+        }
+    }
+    const float b0 = A.bnd0[row], scale = A.scale;
+    const int rl = row & 127, swz = (rl >> 2) & 3;
+    typedef unsigned u32x4v __attribute__((ext_vector_type(4)));
+    for (int nb = 0; nb < A.nblk; ++nb) {
+        const bool rot = (A.rot_mask >> nb) & 1;
+        const float* xp = A.x + (size_t)row * A.ldx + (size_t)nb * A.x_blk + col0;
+        float4 v[2] = {*reinterpret_cast<const float4*>(xp), *reinterpret_cast<const float4*>(xp + 4)};
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            float4 x = v[i];
+            if (rot) {
+                // The epilogues write __fadd_rn(__fmul_rn(x0, c), __fmul_rn(-x1, s)) and its siblings; the intrinsics are the plain operators in this
+                // toolchain, and the compiler contracts each sum to ONE fma with the other product rounded on its own (v_pk_mul_f32 + two
+                // v_pk_fma_f32 per pair, in every instantiation).  Which product it fuses is its choice: the even element fuses the cos product
+                // everywhere; the odd element fuses the cos product in pgemm_kernel and the SIN product in pgemm16w_kernel (A.wide_form).  Left
+                // to the compiler, the same expression came out in a third form here, so the forms are spelled out; they cannot move on this
+                // side, and tests/test_invariant_projections_gpu.py holds them against both kernels.
+                const float x0 = x.x, x1 = x.y, x2 = x.z, x3 = x.w;
+                x.x = __builtin_fmaf(x0, tb[i].x, -(x1 * tb[i].z));
+                x.z = __builtin_fmaf(x2, tb[i].y, -(x3 * tb[i].w));
+                if (A.wide_form) {
+                    x.y = __builtin_fmaf(x0, tb[i].z, x1 * tb[i].x);
+                    x.w = __builtin_fmaf(x2, tb[i].w, x3 * tb[i].y);
+                } else {
+                    x.y = __builtin_fmaf(x1, tb[i].x, x0 * tb[i].z);
+                    x.w = __builtin_fmaf(x3, tb[i].y, x2 * tb[i].w);
+                }
+            }
+            x.x *= scale; x.y *= scale; x.z *= scale; x.w *= scale;
+            v[i] = x;
+        }
+        const float bin = ((A.grp_mask >> nb) & 1) ? A.grp_bnd[A.grp_first + row / A.grp_rows] : fmaxf(b0, 0.f);
+        const float bound = (bin * A.wnorm[nb] + 0.f) * (rot ? 1.41421366f : 1.f) * fabsf(scale);
+        if (col0 == 0) A.pbnd[(size_t)nb * A.pbnd_blk_stride + row] = bound;
+        const float sc = pow2i(scale_exp(bound));
+        unsigned h0, l0, h1, l1, h2, l2, h3, l3;
+        split2(v[0].x * sc, v[0].y * sc, h0, l0); split2(v[0].z * sc, v[0].w * sc, h1, l1);
+        split2(v[1].x * sc, v[1].y * sc, h2, l2); split2(v[1].z * sc, v[1].w * sc, h3, l3);
+        const u32x4v hi = {h0, h1, h2, h3}, lo = {l0, l1, l2, l3};
+        char* const rowp = A.pimg + (size_t)nb * A.pimg_blk_stride + (((size_t)(row >> 7) * A.p_nct + kc) * 128 + rl) * 64;
+        __builtin_nontemporal_store(hi, reinterpret_cast<u32x4v*>(rowp + ((hh ^ swz) << 4)));
+        __builtin_nontemporal_store(lo, reinterpret_cast<u32x4v*>(rowp + (((2 + hh) ^ swz) << 4)));
+    }
+}
+int launch_rot_images(const RotImgArgs& a, hipStream_t st) {
+    if (a.rows < 1) return DR_OK;
+    if (a.nblk < 1 || a.nblk > 3 || a.C < 16 || a.C % 16 || a.C / 16 > a.p_nct || a.ldx % 4 || a.x_blk % 4 || ((uintptr_t)a.x & 15) || !a.x || !a.bnd0 ||
+        !a.wnorm || !a.pimg || !a.pbnd || ((uintptr_t)a.pimg & 15) || (a.grp_mask && (!a.grp_bnd || a.grp_rows < 1)))
+        return DR_EINVAL;
+    if (a.rot_mask && (!a.csT || ((uintptr_t)a.csT & 15) || a.rot_C % 4 || a.rot_piece_len % 4 || a.rot_piece_pad % 4)) return DR_EINVAL;
+    // bytes moved: the rows in, the tables, the images (4 bytes per element) out
+    ProfScope ps(PK_PE, (double)a.rows * (8.0 * a.nblk * a.C + (a.rot_mask ? 4.0 * a.rot_C : 0.0)), st);
+    hipLaunchKernelGGL(rot_images_kernel, dim3((a.rows + 63) / 64, (a.C / 16 + 1) / 2), dim3(256), 0, st, a);
     DR_LAUNCH_CHECK();
     return DR_OK;
 }
@@ -1986,6 +2069,28 @@ int dr_linear_planes_f32(const dr_planes_linear* a, void* stream) {
         (void)bn;
     }
     return launch_pgemm(g, (hipStream_t)stream);
+}
+
+int dr_rotary_planes_f32(int rows, int C, int nblk, const float* x, int ldx, int x_blk, const float* cs_t, int rot_mask, int rot_C, float scale,
+                         const float* bound0, const void* packed, int k, int weight_layout, void* out_image, long long image_blk_stride,
+                         float* out_bound, long long bound_blk_stride, void* stream) {
+    if (rows < 0 || nblk < 1 || nblk > 3 || !x || !bound0 || !packed || !out_image || !out_bound || k < 16 || k % 16 || ldx < C || C < 16 || C % 16 ||
+        (rot_mask && (!cs_t || rot_C < 4))) return DR_EINVAL;
+    PgW v;
+    if (weight_layout == DR_PL_LAYOUT_WIDE) {
+        if (!pgemm16w_shape_ok(C)) return DR_EINVAL;
+        pgemm16w_weight_view((void*)packed, nblk, k / 16, &v);
+    } else if (weight_layout == DR_PL_LAYOUT_BLOCK) {
+        if (!pgemm_shape_ok(C)) return DR_EINVAL;
+        pgemm_weight_view((void*)packed, C, nblk, k / 16, &v);
+    } else return DR_EINVAL;
+    RotImgArgs r;
+    memset(&r, 0, sizeof(r));
+    r.x = x; r.ldx = ldx; r.x_blk = x_blk; r.rows = rows; r.C = C; r.nblk = nblk;
+    r.csT = cs_t; r.rot_mask = rot_mask; r.rot_C = rot_C; r.scale = scale;
+    r.bnd0 = bound0; r.wnorm = v.wnorm; r.wide_form = v.sub == 2;
+    r.pimg = (char*)out_image; r.p_nct = C / 16; r.pbnd = out_bound; r.pimg_blk_stride = image_blk_stride; r.pbnd_blk_stride = bound_blk_stride;
+    return launch_rot_images(r, (hipStream_t)stream);
 }
 
 size_t dr_plane_split_workspace_bytes(int C) {

@@ -133,6 +133,8 @@ SIGNATURES.update({
     "dr_ln_bound_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dr_linear_planes_f32": (c_int, [ctypes.POINTER(PlanesLinear), c_void_p]),
     "dr_bias_max_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_void_p]),
+    "dr_rotary_planes_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_int, c_void_p, c_int, c_int, c_float, c_void_p, c_void_p, c_int, c_int,
+                                     c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p]),
     "dr_loop2d3d_prepack_bytes": (c_size_t, [ctypes.POINTER(Loop2D3DConfig)]),
     "dr_loop2d3d_prepack": (c_int, [ctypes.POINTER(Loop2D3DConfig), ctypes.POINTER(FusionWeights), c_void_p, c_size_t, c_void_p]),
     "dr_gemm_nt_batched_f32": (c_int, [c_int, c_int, c_int, c_int, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong, c_void_p, ctypes.c_longlong,
@@ -495,6 +497,14 @@ def linear_planes(rows, C, nblk, a0, b0, k0, packed, mode, *, a1=None, b1=None, 
     a.weight_layout = 1 if wide else 0
     a.split_workspace, a.split_workspace_bytes = dp(split_ws), (split_ws.numel() if split_ws is not None else 0)
     check(_lib.dr_linear_planes_f32(ctypes.byref(a), stream_of(a0)))
+
+
+def rotary_planes(x, x_blk, C, nblk, cs_t, rot_mask, rot_C, b0, packed, k, out_image, image_blk_stride, out_bound, bound_blk_stride, scale=1.0,
+                  wide=False):
+    """dr_rotary_planes_f32: x [rows, ldx] fp32 (what linear_planes wrote in PL_F32 mode without rotary) -> the images and bounds of PL_PLANES"""
+    ensure_init()
+    check(_lib.dr_rotary_planes_f32(x.shape[0], C, nblk, ptr(x), x.stride(0), x_blk, ptr(cs_t), rot_mask, rot_C, scale, ptr(b0), ptr(packed), k,
+                                    1 if wide else 0, ptr(out_image), image_blk_stride, ptr(out_bound), bound_blk_stride, stream_of(x)))
 
 
 def plane_split_workspace(C, device):

@@ -50,7 +50,8 @@ extern "C" {
  *   0.7.0, second set (the number is unchanged: an existing check of the repository pins DR_ABI_VERSION to 700, and additions break no
  *          caller -- detect these entries by symbol)  the geometry head and feature-layout glue of the 2D-3D forward: dr_back_project_f32,
  *          dr_render_f32, dr_resize_tokens_f32, dr_resize_tokens_backward_f32, dr_rows_normalize_chw_f32, dr_rows_normalize_chw_backward_f32,
- *          dr_rows_normalize_chw_backward_rows_f32 (new entries only; nothing older changed). */
+ *          dr_rows_normalize_chw_backward_rows_f32 (new entries only; nothing older changed).
+ *   0.7.0, third set (same rule)  dr_rotary_planes_f32: the rotary + image tail of a DR_PL_PLANES launch on its own (new entry only). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -233,6 +234,14 @@ int dr_plane_split_status(void* split_workspace, void* stream, int clear);
 #define DR_PL_LAYOUT_BLOCK 0   /* dr_pack_weight_planes_f32                                                           */
 #define DR_PL_LAYOUT_WIDE 1    /* dr_pack_weight_planes_wide_f32 (DR_PL_F32 / DR_PL_PLANES only)                      */
 int dr_linear_planes_f32(const dr_planes_linear* args, void* stream);
+/* The tail of a DR_PL_PLANES launch on its own, for projections whose input stays while the rotary code moves: x [rows, ldx] holds what
+ * dr_linear_planes_f32 wrote in DR_PL_F32 mode with rot_mask = 0 and scale = 1 (block nb at column nb * x_blk); this applies the rotary code
+ * (bit nb of rot_mask; cs_t [rows, rot_C / 2, 2] = (cos, sin) interleaved), `scale`, and writes block nb's plane image of C columns at
+ * out_image + nb * image_blk_stride and its row bounds at out_bound + nb * bound_blk_stride -- byte for byte what the DR_PL_PLANES launch of the
+ * same problem (a0 with bound0, `packed` of nblk blocks over k columns) writes with out_image_k = C per block. */
+int dr_rotary_planes_f32(int rows, int C, int nblk, const float* x, int ldx, int x_blk, const float* cs_t, int rot_mask, int rot_C, float scale,
+                         const float* bound0, const void* packed, int k, int weight_layout, void* out_image, long long image_blk_stride,
+                         float* out_bound, long long bound_blk_stride, void* stream);
 /* out[b] = max |bias[b n .. b n + n - 1]| (1 + 1e-4), b < nblk */
 int dr_bias_max_f32(int nblk, int n, const float* bias, float* out, void* stream);
 
