@@ -11,6 +11,7 @@
 // source texel sums its destinations in ascending order), the sparse normalise backward lets the first occurrence of a row sum its repeats in
 // list order -- two runs are bit-identical.
 #include "kernels.h"
+#include "resize_index.h"
 
 // the geometry kernels restate float32 expressions of the reference term by term: no a * b + c becomes an FMA in this file
 #pragma clang fp contract(off)
@@ -114,15 +115,7 @@ __global__ void __launch_bounds__(FR_BLOCK) render_kernel(int N, const float* __
 // ------------------------------------------------------------------------------------------------------------
 constexpr int RS_TC = 32, RS_TP = 64;             // tile: 32 channels x 64 pixels, [c][p] in LDS with one word of padding per row
 
-// ATen's area_pixel_compute_source_index with align_corners: scale = (in - 1) / (out - 1), 0 when out == 1
-__host__ __device__ inline double resize_scale(int in, int out) { return out > 1 ? (double)(in - 1) / (double)(out - 1) : 0.0; }
-__device__ __forceinline__ void resize_src(double scale, int d, int in, int& i0, int& i1, double& l1) {
-    const double s = scale * d;
-    i0 = (int)s;
-    if (i0 > in - 1) i0 = in - 1;
-    i1 = i0 + (i0 < in - 1 ? 1 : 0);
-    l1 = s - i0;
-}
+// resize_scale / resize_src / resize_blend: resize_index.h (shared with dr_resize_rows_f32)
 
 __global__ void __launch_bounds__(FR_BLOCK) resize_tokens_kernel(int C, int Hs, int Ws, int Hd, int Wd, const float* __restrict__ in,
                                                                  float* __restrict__ out) {
@@ -140,7 +133,7 @@ __global__ void __launch_bounds__(FR_BLOCK) resize_tokens_kernel(int C, int Hs, 
             for (int cl = threadIdx.x / RS_TP; cl < RS_TC && c0 + cl < C; cl += FR_BLOCK / RS_TP) {
                 const float* src = in + (size_t)(c0 + cl) * Hs * Ws;
                 const double v00 = src[y0 * Ws + x0], v01 = src[y0 * Ws + x1], v10 = src[y1 * Ws + x0], v11 = src[y1 * Ws + x1];
-                tile[cl * (RS_TP + 1) + pl] = (float)((1.0 - ly) * ((1.0 - lx) * v00 + lx * v01) + ly * ((1.0 - lx) * v10 + lx * v11));
+                tile[cl * (RS_TP + 1) + pl] = resize_blend(ly, lx, v00, v01, v10, v11);
             }
         }
     }

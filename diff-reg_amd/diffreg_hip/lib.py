@@ -298,6 +298,9 @@ SIGNATURES.update({
     "dr_rows_normalize_chw_f32": (c_int, [c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p]),
     "dr_rows_normalize_chw_backward_f32": (c_int, [c_int, ctypes.c_int64, c_void_p, c_void_p, c_void_p, c_void_p]),
     "dr_rows_normalize_chw_backward_rows_f32": (c_int, [c_int, ctypes.c_int64, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_void_p]),
+    # ABI 0.7.0, fourth set: the image backbone's inference forward on token rows
+    "dr_conv2d_rows_f32": (c_int, [c_int] * 8 + [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "dr_resize_rows_f32": (c_int, [c_int] * 5 + [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
 })
 
 
@@ -1573,6 +1576,54 @@ def resize_tokens_backward(grad_out, src_shape, size):
     gi = torch.empty(C, Hs, Ws, device=g.device)
     check(_lib.dr_resize_tokens_backward_f32(C, Hs, Ws, Hd, Wd, ptr(g) if g.numel() else None, ptr(gi) if gi.numel() else None, stream_of(gi)))
     return gi
+
+
+def conv_out_size(n, k, stride=1, padding=0, dilation=1):
+    """nn.Conv2d's output extent (conv_index.h: conv_out_size)"""
+    span = n + 2 * padding - dilation * (k - 1) - 1
+    return 0 if span < 0 else span // stride + 1
+
+
+def pack_conv_weight(weight):
+    """nn.Conv2d weight [Cout, Cin, k, k] -> the packed [Cout, k k Cin] (tap-major, ci-minor) dr_conv2d_rows_f32 reads"""
+    Cout, Cin, kh, kw = weight.shape
+    if kh != kw:
+        raise NotImplementedError("libdiffreg_hip: conv2d_rows takes square kernels (got %d x %d)" % (kh, kw))
+    return weight.detach().float().permute(0, 2, 3, 1).reshape(Cout, kh * kw * Cin).contiguous()
+
+
+def conv2d_rows(x, size, w_packed, k, bias=None, stride=1, padding=0, dilation=1, addend=None, out=None):
+    """nn.Conv2d on token rows: x [Hi*Wi, Cin] (a row stride >= Cin is taken as the leading dimension), size = (Hi, Wi), w_packed from
+    pack_conv_weight -> (out [Ho*Wo, Cout], (Ho, Wo)); addend [Ho*Wo, Cout] is added last   (dr_conv2d_rows_f32)"""
+    ensure_init()
+    Hi, Wi = int(size[0]), int(size[1])
+    Cin, Cout = x.shape[1], w_packed.shape[0]
+    if x.shape[0] != Hi * Wi or w_packed.shape[1] != k * k * Cin or (Cin > 1 and x.stride(1) != 1):
+        raise ValueError("conv2d_rows: x %s / weight %s do not fit a %d x %d image and a %d x %d kernel" % (tuple(x.shape), tuple(w_packed.shape),
+                                                                                                         Hi, Wi, k, k))
+    Ho, Wo = conv_out_size(Hi, k, stride, padding, dilation), conv_out_size(Wi, k, stride, padding, dilation)
+    if out is None:
+        out = torch.empty(max(Ho * Wo, 0), Cout, device=x.device)
+    rawp = lambda t_: None if t_ is None else c_void_p(t_.data_ptr())
+    check(_lib.dr_conv2d_rows_f32(Hi, Wi, Cin, Cout, k, stride, padding, dilation, rawp(x), x.stride(0), ptr(w_packed), ptr(bias), rawp(addend),
+                                  addend.stride(0) if addend is not None else 0, rawp(out), out.stride(0), stream_of(x)))
+    return out, (Ho, Wo)
+
+
+def resize_rows(x, src_size, size, addend=None, out=None):
+    """x [Hs*Ws, C] rows -> [Hd*Wd, C] rows: bilinear, align_corners=True, out = addend + resample(x)   (dr_resize_rows_f32)"""
+    ensure_init()
+    Hs, Ws = int(src_size[0]), int(src_size[1])
+    Hd, Wd = int(size[0]), int(size[1])
+    C = x.shape[1]
+    if x.shape[0] != Hs * Ws or (C > 1 and x.stride(1) != 1):
+        raise ValueError("resize_rows: x %s is not a %d x %d image of rows" % (tuple(x.shape), Hs, Ws))
+    if out is None:
+        out = torch.empty(Hd * Wd, C, device=x.device)
+    rawp = lambda t_: None if t_ is None else c_void_p(t_.data_ptr())
+    check(_lib.dr_resize_rows_f32(C, Hs, Ws, Hd, Wd, rawp(x), x.stride(0), rawp(addend), addend.stride(0) if addend is not None else 0, rawp(out),
+                                  out.stride(0), stream_of(x)))
+    return out
 
 
 def rows_normalize_chw(feats):

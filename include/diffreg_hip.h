@@ -51,7 +51,9 @@ extern "C" {
  *          caller -- detect these entries by symbol)  the geometry head and feature-layout glue of the 2D-3D forward: dr_back_project_f32,
  *          dr_render_f32, dr_resize_tokens_f32, dr_resize_tokens_backward_f32, dr_rows_normalize_chw_f32, dr_rows_normalize_chw_backward_f32,
  *          dr_rows_normalize_chw_backward_rows_f32 (new entries only; nothing older changed).
- *   0.7.0, third set (same rule)  dr_rotary_planes_f32: the rotary + image tail of a DR_PL_PLANES launch on its own (new entry only). */
+ *   0.7.0, third set (same rule)  dr_rotary_planes_f32: the rotary + image tail of a DR_PL_PLANES launch on its own (new entry only).
+ *   0.7.0, fourth set (same rule: a minor bump was asked for, and the pinned 700 of that older check forbids it)  the 2D-3D image backbone's
+ *          inference forward on token rows: dr_conv2d_rows_f32, dr_resize_rows_f32 (new entries only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1073,6 +1075,29 @@ size_t dr_sinkhorn_backward_workspace_bytes(int P, int N, int M, int iters);
 int dr_sinkhorn_backward_f32(int P, int N, int M, const float* scores, const uint8_t* src_mask, const uint8_t* tgt_mask, const float* bin_score,
                              int iters, const float* grad_conf, float* grad_scores, float* grad_bin_score, void* workspace,
                              size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 0.7.0, fourth set: the 2D-3D image backbone's inference forward (ImageBackbone.forward, EXP/image_backbone.py:254-289, called at
+ * EXP/model.py:358-361) on token rows.  csrc/conv2d.hip, index arithmetic in csrc/conv_index.h.  Every activation is [H W, C] float32 (NHWC)
+ * with a leading dimension -- the rows dr_group_norm_stats_f32 / dr_group_norm_apply_f32 take, so nn.GroupNorm(G, C) over [1, C, H, W] is
+ * dr_group_norm_stats_f32(N = H W, C, G).  Nothing synchronises, nothing allocates, no atomics: two runs are bit-equal.
+ *
+ * dr_conv2d_rows_f32: nn.Conv2d(Cin, Cout, k, stride, padding, dilation, groups = 1, padding_mode = "zeros") (vision3d/layers/conv_block.py:118-119;
+ *   every conv of EXP/image_backbone.py:21-57 and :81-252): x [Hi Wi, ldx] -> out [Ho Wo, ldo], Ho = (Hi + 2 padding - dilation (k - 1) - 1) / stride
+ *   + 1.  weight is PACKED [Cout, k k Cin], tap-major and ci-minor (the module's [Cout, Cin, k, k] permuted to [Cout, k, k, Cin]).  bias [Cout]
+ *   or NULL; addend [Ho Wo, lda] or NULL is added last (the sums of EXP/image_backbone.py:272, :277, :280).  Cin % 4 == 0: implicit GEMM on the
+ *   f32-input MFMA, A gathered per (output pixel, tap) with 16-byte loads, no im2col buffer, a tap in the padding loads nothing (scalar loads when
+ *   x or weight is not 16-byte aligned or ldx % 4 != 0); other Cin: a direct kernel.  Pointers must be 4-byte aligned, Ho, Wo >= 1 (DR_EINVAL);
+ *   Hi Wi, Ho Wo <= 2^24, Cin, Cout <= 2^16, k k Cin <= 2^20, k <= 31, stride, dilation <= 64, padding <= 1024, leading dimensions <= 2^20
+ *   (DR_ENOSUP beyond).
+ * dr_resize_rows_f32: F.interpolate(mode = "bilinear", align_corners = True) from rows to rows (EXP/image_backbone.py:264, :270, :275, :281):
+ *   in [Hs Ws, ldi] -> out [Hd Wd, ldo] = addend + resample(in), addend [Hd Wd, lda] or NULL (the sums of :267, :272, :277).  Source index and
+ *   weights as dr_resize_tokens_f32 computes them (one shared statement: the two agree bit for bit).  Limits as dr_resize_tokens_f32; every
+ *   extent >= 1. */
+int dr_conv2d_rows_f32(int Hi, int Wi, int Cin, int Cout, int k, int stride, int padding, int dilation, const float* x, int ldx,
+                       const float* weight, const float* bias, const float* addend, int lda, float* out, int ldo, void* stream);
+int dr_resize_rows_f32(int C, int Hs, int Ws, int Hd, int Wd, const float* in, int ldi, const float* addend, int lda, float* out, int ldo,
+                       void* stream);
 
 #ifdef __cplusplus
 }
