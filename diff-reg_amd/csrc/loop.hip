@@ -6,6 +6,7 @@
 //
 // Token layout: all src superpoints of all P pairs, then all tgt superpoints:
 //   rows [0, P*N) = src (pair p at p*N), rows [P*N, P*(N+M)) = tgt (pair p at P*N + p*M).
+// In the terms of loop_common.h's Sides: side A = src (N rows per pair), side B = tgt (M rows per pair).
 // Linear layers / LayerNorm / rotary are row-wise, so the P pairs simply widen the GEMMs; only the
 // attention, the N x M matrices and the Procrustes fit know about pair boundaries.
 #include "loop_common.h"
@@ -52,27 +53,18 @@ struct Prepack {
         Carver c(buf);
         const int C = cfg.C, d = C / cfg.H, dp = (d + 15) / 16 * 16, nC = C / 16;
         if (pp) pp->dp = dp;
-        auto take = [&](int nblk, int nct, PgW* v) {
-            char* p = c.take<char>(pgemm_weight_bytes(C, nblk, nct));
-            if (pp && buf) pgemm_weight_view(p, C, nblk, nct, v);
-        };
         // the launches without LayerNorm of the 576-column geometry (4DMatch) run on the wide-wave kernel: their weights in its layout
         const bool wide = wide_layout(cfg);
-        auto takew = [&](int nblk, int nct, PgW* v) {
-            if (!wide) return take(nblk, nct, v);
-            char* p = c.take<char>(pgemm16w_weight_bytes(nblk, nct));
-            if (pp && buf) pgemm16w_weight_view(p, nblk, nct, v);
-        };
         for (int l = 0; l < cfg.n_layers; ++l) {
             PrepackLayer* L = pp ? &pp->L[l] : nullptr;
-            takew(3, nC, L ? &L->qkv : nullptr);           // (C' = H dp output columns per block: same image size, C' <= BN)
-            take(1, cfg.H * dp / 16, L ? &L->merge : nullptr);
-            takew(2, 2 * nC, L ? &L->mlp0 : nullptr);
-            take(1, 2 * nC, L ? &L->mlp2 : nullptr);
+            take_weight(c, C, 3, nC, L ? &L->qkv : nullptr, wide);           // (C' = H dp output columns per block: same image size, C' <= BN)
+            take_weight(c, C, 1, cfg.H * dp / 16, L ? &L->merge : nullptr);
+            take_weight(c, C, 2, 2 * nC, L ? &L->mlp0 : nullptr, wide);
+            take_weight(c, C, 1, 2 * nC, L ? &L->mlp2 : nullptr);
             float* b = c.take<float>(2);
             if (L && buf) { L->lnB1 = b; L->lnB2 = b + 1; }
         }
-        takew(1, nC, pp ? &pp->head : nullptr);
+        take_weight(c, C, 1, nC, pp ? &pp->head : nullptr, wide);
         return c.off + 256;
     }
     static int fill(void* buf, const dr_loop_config& cfg, const dr_loop_weights& W, hipStream_t st) {
@@ -86,23 +78,18 @@ struct Prepack {
             const PrepackLayer& L = pp.L[l];
             // q | k | v: output columns padded per head (d -> dp) so that the images the GEMM writes start every head at a k-chunk
             const int Cq = cfg.H * pp.dp;
-            auto packw = [&](const float* Wm, int Cc, int K, int plen, int ppad, const PgW& v, int nb, int olen = 0, int opad = 0) {
-                return v.sub == 2 ? pgemm16w_pack_weights_block(Wm, Cc, K, plen, ppad, v, nb, st, olen, opad)
-                                  : pgemm_pack_weights_block(Wm, Cc, K, plen, ppad, v, nb, st, olen, opad);
-            };
-            int rc = packw(w.q_proj, Cq, C, C, C, L.qkv, 0, d, pp.dp);
-            if (rc == DR_OK) rc = packw(w.k_proj, Cq, C, C, C, L.qkv, 1, d, pp.dp);
-            if (rc == DR_OK) rc = packw(w.v_proj, Cq, C, C, C, L.qkv, 2, d, pp.dp);
-            if (rc == DR_OK) rc = pgemm_pack_weights_block(w.merge, C, C, d, pp.dp, L.merge, 0, st);
-            if (rc == DR_OK) rc = packw(w.mlp0, C, 2 * C, 2 * C, 2 * C, L.mlp0, 0);
-            if (rc == DR_OK) rc = packw(w.mlp0 + (size_t)C * 2 * C, C, 2 * C, 2 * C, 2 * C, L.mlp0, 1);
-            if (rc == DR_OK) rc = pgemm_pack_weights_block(w.mlp2, C, 2 * C, 2 * C, 2 * C, L.mlp2, 0, st);
+            int rc = pack_weight_block(w.q_proj, Cq, C, C, C, L.qkv, 0, st, d, pp.dp);
+            if (rc == DR_OK) rc = pack_weight_block(w.k_proj, Cq, C, C, C, L.qkv, 1, st, d, pp.dp);
+            if (rc == DR_OK) rc = pack_weight_block(w.v_proj, Cq, C, C, C, L.qkv, 2, st, d, pp.dp);
+            if (rc == DR_OK) rc = pack_weight_block(w.merge, C, C, d, pp.dp, L.merge, 0, st);
+            if (rc == DR_OK) rc = pack_weight_block(w.mlp0, C, 2 * C, 2 * C, 2 * C, L.mlp0, 0, st);
+            if (rc == DR_OK) rc = pack_weight_block(w.mlp0 + (size_t)C * 2 * C, C, 2 * C, 2 * C, 2 * C, L.mlp0, 1, st);
+            if (rc == DR_OK) rc = pack_weight_block(w.mlp2, C, 2 * C, 2 * C, 2 * C, L.mlp2, 0, st);
             if (rc == DR_OK) rc = launch_ln_bound(w.norm1_w, w.norm1_b, C, (float*)L.lnB1, st);
             if (rc == DR_OK) rc = launch_ln_bound(w.norm2_w, w.norm2_b, C, (float*)L.lnB2, st);
             if (rc) return rc;
         }
-        return pp.head.sub == 2 ? pgemm16w_pack_weights_block(W.src_proj, C, C, C, C, pp.head, 0, st)
-                                : pgemm_pack_weights_block(W.src_proj, C, C, C, C, pp.head, 0, st);
+        return pack_weight_block(W.src_proj, C, C, C, C, pp.head, 0, st);
     }
 };
 
@@ -213,10 +200,7 @@ static int layer_call(const dr_layer_weights& W, int C, int H, int P, const floa
     a.ldq = a.ldk = a.ldv = 3 * C; a.ldo = C; a.H = H; a.d = d;
     if (kv_cached) { a.k = kv_cached; a.v = kv_cached + C; a.ldk = a.ldv = 2 * C; }
     a.qmask = tokmask; a.kmask = tokmask;
-    a.nseg = P; a.q0 = f1.q0; a.qstride = f1.Lq; a.Lq = f1.Lq; a.k0 = f1.k0; a.kstride = f1.Lk; a.Lk = f1.Lk;
-    if (f2) {
-        a.nseg2 = P; a.q0b = f2->q0; a.qstrideb = f2->Lq; a.Lqb = f2->Lq; a.k0b = f2->k0; a.kstrideb = f2->Lk; a.Lkb = f2->Lk;
-    }
+    attn_families(a, P, f1, f2);
     a.scale = 1.0f / sqrtf((float)d);
     rc = launch_attention(a, st);
     if (rc) return rc;
@@ -253,14 +237,7 @@ static int layer_call(const dr_layer_weights& W, int C, int H, int P, const floa
 
 
 // ---- the plane path of one GeometryAttentionLayer call (transformero.py:43-96): five launches ---------------------------------
-enum { SIDE_SRC = 1, SIDE_TGT = 2, SIDE_BOTH = 3 };
-struct PlCtx {
-    const Prepack* pp; const PlanesWs* pw; const LayerWs* lw;
-    int C, H, P, N, M;
-    const float *cosT, *sinT;
-    const uint8_t* tokmask;
-    int attn_f16;                            // DR_LOOP_ATTN_F16
-};
+using PlCtx = PlaneCtx<Prepack, PlanesWs>;
 // exchange region of a problem whose launch may split its k range over two workgroups (pgemm.h: xk_buf).  The buffer holds PG_XK_MAX_RB units --
 // one per 64-row block of a LayerNorm launch / per 128 x 288 tile of a wide-wave launch; the problems of a launch take consecutive regions
 // (`next`: units handed out so far in this launch); the caller advances pw.xk_epoch once per launch that got regions.
@@ -282,21 +259,17 @@ struct PlHoist {
 static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, const Tok& xin, int xs, const Tok& yin, int ys,
                              const Tok& out, const Family& f1, const Family* f2, hipStream_t st, const float* kv_cached = nullptr,
                              float* kv_store = nullptr, const PlHoist& hz = PlHoist()) {
-    const int C = X.C, H = X.H, PN = X.P * X.N, PM = X.P * X.M, halfC = C / 2, d = C / H, nC = C / 16, dp = X.pp->dp;
+    const Sides& S = X.S;
+    const int C = X.C, H = X.H, PN = S.rows_a, PM = S.rows_b, halfC = C / 2, d = C / H, nC = C / 16, dp = X.pp->dp;
     const PrepackLayer& L = X.pp->L[l];
     const PlanesWs& pw = *X.pw;
-    auto r0 = [&](int side) { return side == SIDE_TGT ? PN : 0; };
-    auto nrows = [&](int side) { return side == SIDE_TGT ? PM : PN; };
-    auto at = [&](char* img, size_t side_off, int side) { return img + (side == SIDE_TGT ? side_off : 0); };
     PgBatch g;
     size_t xk_next = 0;                   // exchange units handed to the problems of the launch being assembled
     auto reset = [&]() { memset(&g, 0, sizeof(g)); xk_next = 0; };
     auto add = [&]() -> PgProblem& { return g.p[g.n++]; };
-    auto for_sides = [&](int mask, auto fn) { for (int side = 1; side <= 2; ++side) if (mask & side) fn(side); };
     // KSPLIT exchange region of a LayerNorm problem (launch_pgemm decides whether the launch is split): the tgt side's row blocks behind the src side's
     auto xk = [&](PgProblem& p, size_t units) { xk_assign(pw, C, p, xk_next, units); };
     int rc;
-    bool rc_ok = true;
 
     // ---- q | k | v projections + rotary -> three plane images of H dp columns (head h at k = h dp): the attention kernel's
     // operands.  q keeps a scale per row; all keys of a pair's side share ONE scale (k, v blocks take the bound of the row's group).
@@ -306,27 +279,26 @@ static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, c
     float* const kv_bnd = kv_store ? pw.kvc_bnd : pw.qkv_bnd + T;
     // bound of the keys' source rows per group (pair x side): taken inside the projection's own kernel when a group is a whole number of
     // workgroups (the 480 five-microsecond launches of a 20-step loop were 2 - 4 % of it), by a kernel of its own otherwise
-    const bool grp_inline = X.N % 128 == 0 && X.M % 128 == 0 && env_knob("DR_LOOP_GRP_INLINE", 1) != 0;
+    const bool grp_inline = S.La % 128 == 0 && S.Lb % 128 == 0 && env_knob("DR_LOOP_GRP_INLINE", 1) != 0;
     if (!cached && !grp_inline && !hz.l0_fill && !hz.l0_use && !hz.q1_fill) {
-        for (int side = 1; side <= 2 && rc_ok; ++side)
-            if (ys & side) rc_ok = launch_group_max(yin.bnd + r0(side), X.P, side == SIDE_TGT ? X.M : X.N, pw.grp_x + (side == SIDE_TGT ? X.P : 0), st) == DR_OK;
-        if (!rc_ok) return DR_ELAUNCH;
+        rc = side_group_max(S, ys, yin.bnd, pw.grp_x, st);
+        if (rc) return rc;
     }
     auto proj = [&](const Tok& tin, int side, int b0, int nblk, char* img, float* bnd, int rotm, int grpm) {
         PgProblem& p = add();
-        p.A0 = at(tin.img, pw.side_C, side); p.bnd0 = tin.bnd + r0(side); p.nc0 = nC;
-        p.W = pgw_blocks(L.qkv, b0, C); p.nblk = nblk; p.rows = nrows(side); p.C = Cq; p.k_alg = C; p.mode = PG_PLANES;
+        p.A0 = S.at(tin.img, pw.side_C, side); p.bnd0 = tin.bnd + S.r0(side); p.nc0 = nC;
+        p.W = pgw_blocks(L.qkv, b0, C); p.nblk = nblk; p.rows = S.rows(side); p.C = Cq; p.k_alg = C; p.mode = PG_PLANES;
         p.rot_mask = rotm; p.rot_C = C; p.rot_piece_len = d; p.rot_piece_pad = dp; p.scale = 1.f;
-        p.cosT = X.cosT + (size_t)r0(side) * halfC; p.sinT = X.sinT + (size_t)r0(side) * halfC;
-        p.csT = X.pw->csT + (size_t)r0(side) * halfC * 2;
-        p.pimg = at(img, pw.side_att, side); p.p_nct = nq; p.pbnd = bnd + r0(side);
+        p.cosT = X.cosT + (size_t)S.r0(side) * halfC; p.sinT = X.sinT + (size_t)S.r0(side) * halfC;
+        p.csT = X.pw->csT + (size_t)S.r0(side) * halfC * 2;
+        p.pimg = S.at(img, pw.side_att, side); p.p_nct = nq; p.pbnd = bnd + S.r0(side);
         p.pimg_blk_stride = (long long)pw.qkv_stride; p.pbnd_blk_stride = T;
-        p.grp_bnd = grp_inline ? nullptr : pw.grp_x; p.grp_mask = grpm; p.grp_first = side == SIDE_TGT ? X.P : 0; p.grp_rows = side == SIDE_TGT ? X.M : X.N;
+        p.grp_bnd = grp_inline ? nullptr : pw.grp_x; p.grp_mask = grpm; p.grp_first = S.grp_first(side); p.grp_rows = S.per_pair(side);
         if (p.W.sub == 2) xk(p, xk_wide_units(p));
     };
     reset();
     if (kv_store) {
-        for_sides(ys, [&](int side) { proj(yin, side, 1, 2, kv_img, kv_bnd, 1, 3); });
+        S.for_sides(ys, [&](int side) { proj(yin, side, 1, 2, kv_img, kv_bnd, 1, 3); });
         ++pw.xk_epoch;
         return launch_pgemm(g, st);
     }
@@ -334,10 +306,10 @@ static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, c
     // accumulators are summed in its order and the images come out bit for bit as the per-step launch writes them.
     const int rbS = (PN + 127) / 128, rbT = (PM + 127) / 128;
     if (hz.l0_fill) {
-        rc = launch_group_max(xin.bnd, X.P, X.N, pw.grp0, st);
+        rc = launch_group_max(xin.bnd, S.P, S.La, pw.grp0, st);
         if (rc) return rc;
         // q | k: the value in front of the rotary step (the fp32 epilogue without rotary: the same accumulators, column and row scales)
-        proj(xin, SIDE_SRC, 0, 2, pw.qkv_img, pw.qkv_bnd, 0, 0);
+        proj(xin, SIDE_A, 0, 2, pw.qkv_img, pw.qkv_bnd, 0, 0);
         g.p[0].mode = PG_F32; g.p[0].pimg = nullptr; g.p[0].pbnd = nullptr;
         g.p[0].out = pw.pre0; g.p[0].ldo = 2 * Cq; g.p[0].blk_stride = Cq;
         g.wg_as = 3 * rbS;
@@ -345,14 +317,14 @@ static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, c
         rc = launch_pgemm(g, st);
         if (rc) return rc;
         reset();
-        proj(xin, SIDE_SRC, 2, 1, pw.v0_img, pw.v0_bnd, 0, 1);
+        proj(xin, SIDE_A, 2, 1, pw.v0_img, pw.v0_bnd, 0, 1);
         g.p[0].grp_bnd = pw.grp0; g.p[0].grp_first = 0;
         g.wg_as = 3 * rbS;
         ++pw.xk_epoch;
         return launch_pgemm(g, st);
     }
     if (hz.q1_fill) {
-        proj(xin, SIDE_TGT, 0, 1, pw.qkv_img, pw.qkv_bnd, 1, 0);
+        proj(xin, SIDE_B, 0, 1, pw.qkv_img, pw.qkv_bnd, 1, 0);
         g.p[0].pimg = pw.q1_img; g.p[0].pbnd = pw.q1_bnd + PN;
         g.wg_as = rbT + 2 * rbS;
         ++pw.xk_epoch;
@@ -364,17 +336,17 @@ static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, c
         memset(&r, 0, sizeof(r));
         r.x = pw.pre0; r.ldx = 2 * Cq; r.x_blk = Cq; r.rows = PN; r.C = Cq; r.nblk = 2;
         r.csT = pw.csT; r.rot_mask = 3; r.rot_C = C; r.rot_piece_len = d; r.rot_piece_pad = dp; r.scale = 1.f;
-        r.bnd0 = xin.bnd; r.wnorm = L.qkv.wnorm; r.wide_form = L.qkv.sub == 2; r.grp_bnd = pw.grp0; r.grp_mask = 2; r.grp_first = 0; r.grp_rows = X.N;
+        r.bnd0 = xin.bnd; r.wnorm = L.qkv.wnorm; r.wide_form = L.qkv.sub == 2; r.grp_bnd = pw.grp0; r.grp_mask = 2; r.grp_first = 0; r.grp_rows = S.La;
         r.pimg = pw.qkv_img; r.p_nct = nq; r.pbnd = pw.qkv_bnd; r.pimg_blk_stride = (long long)pw.qkv_stride; r.pbnd_blk_stride = T;
         rc = launch_rot_images(r, st);
         if (rc) return rc;
     } else {
         if (self) {
-            for_sides(xs, [&](int side) { proj(xin, side, 0, 3, pw.qkv_img, pw.qkv_bnd, 3, 6); });
+            S.for_sides(xs, [&](int side) { proj(xin, side, 0, 3, pw.qkv_img, pw.qkv_bnd, 3, 6); });
         } else {
-            if (!hz.q1_use) for_sides(xs, [&](int side) { proj(xin, side, 0, 1, pw.qkv_img, pw.qkv_bnd, 1, 0); });
+            if (!hz.q1_use) S.for_sides(xs, [&](int side) { proj(xin, side, 0, 1, pw.qkv_img, pw.qkv_bnd, 1, 0); });
             else g.wg_as = rbT + 2 * rbS;
-            if (!cached) for_sides(ys, [&](int side) { proj(yin, side, 1, 2, kv_img, kv_bnd, 1, 3); });
+            if (!cached) S.for_sides(ys, [&](int side) { proj(yin, side, 1, 2, kv_img, kv_bnd, 1, 3); });
         }
         ++pw.xk_epoch;
         rc = launch_pgemm(g, st);
@@ -386,8 +358,7 @@ static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, c
     memset(&a, 0, sizeof(a));
     a.H = H; a.d = d;
     a.qmask = X.tokmask; a.kmask = X.tokmask;
-    a.nseg = X.P; a.q0 = f1.q0; a.qstride = f1.Lq; a.Lq = f1.Lq; a.k0 = f1.k0; a.kstride = f1.Lk; a.Lk = f1.Lk;
-    if (f2) { a.nseg2 = X.P; a.q0b = f2->q0; a.qstrideb = f2->Lq; a.Lqb = f2->Lq; a.k0b = f2->k0; a.kstrideb = f2->Lk; a.Lkb = f2->Lk; }
+    attn_families(a, S.P, f1, f2);
     a.scale = 1.0f / sqrtf((float)d);
     a.pimg[0] = pw.att_img; a.pimg[1] = pw.att_img + pw.side_att; a.p_split = PN; a.p_nct = nq; a.p_dp = dp;
     a.pbnd = pw.att_bnd;
@@ -407,12 +378,12 @@ static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, c
 
     // ---- message = norm1(merge(o)) -> plane image
     reset();
-    for_sides(xs, [&](int side) {
+    S.for_sides(xs, [&](int side) {
         PgProblem& p = add();
-        p.A0 = at(pw.att_img, pw.side_att, side); p.bnd0 = pw.att_bnd + r0(side); p.nc0 = H * dp / 16;
-        p.W = L.merge; p.nblk = 1; p.rows = nrows(side); p.C = C; p.mode = PG_LN; p.k_alg = C;
+        p.A0 = S.at(pw.att_img, pw.side_att, side); p.bnd0 = pw.att_bnd + S.r0(side); p.nc0 = H * dp / 16;
+        p.W = L.merge; p.nblk = 1; p.rows = S.rows(side); p.C = C; p.mode = PG_LN; p.k_alg = C;
         p.gamma = W.norm1_w; p.beta = W.norm1_b; p.lnB = L.lnB1;
-        p.pimg = at(pw.msg_img, pw.side_C, side); p.p_nct = nC; p.pbnd = pw.msg_bnd + r0(side);
+        p.pimg = S.at(pw.msg_img, pw.side_C, side); p.p_nct = nC; p.pbnd = pw.msg_bnd + S.r0(side);
         xk(p, (size_t)(p.rows + 63) / 64);
     });
     ++pw.xk_epoch;
@@ -420,12 +391,12 @@ static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, c
     if (rc) return rc;
     // ---- hidden = relu(mlp0([x | message])) -> plane image
     reset();
-    for_sides(xs, [&](int side) {
+    S.for_sides(xs, [&](int side) {
         PgProblem& p = add();
-        p.A0 = at(xin.img, pw.side_C, side); p.bnd0 = xin.bnd + r0(side); p.nc0 = nC;
-        p.A1 = at(pw.msg_img, pw.side_C, side); p.bnd1 = pw.msg_bnd + r0(side); p.nc1 = nC;
-        p.W = L.mlp0; p.nblk = 2; p.rows = nrows(side); p.C = C; p.mode = PG_PLANES; p.relu = 1; p.scale = 1.f;
-        p.pimg = at(pw.hid_img, pw.side_hid, side); p.p_nct = 2 * nC; p.pbnd = pw.hid_bnd + r0(side);
+        p.A0 = S.at(xin.img, pw.side_C, side); p.bnd0 = xin.bnd + S.r0(side); p.nc0 = nC;
+        p.A1 = S.at(pw.msg_img, pw.side_C, side); p.bnd1 = pw.msg_bnd + S.r0(side); p.nc1 = nC;
+        p.W = L.mlp0; p.nblk = 2; p.rows = S.rows(side); p.C = C; p.mode = PG_PLANES; p.relu = 1; p.scale = 1.f;
+        p.pimg = S.at(pw.hid_img, pw.side_hid, side); p.p_nct = 2 * nC; p.pbnd = pw.hid_bnd + S.r0(side);
         if (p.W.sub == 2) xk(p, xk_wide_units(p));
     });
     ++pw.xk_epoch;
@@ -433,14 +404,14 @@ static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, c
     if (rc) return rc;
     // ---- out = x + norm2(mlp2(hidden)) -> fp32 rows (the residual stream) + plane image (the next GEMMs' operand)
     reset();
-    for_sides(xs, [&](int side) {
+    S.for_sides(xs, [&](int side) {
         PgProblem& p = add();
-        p.A0 = at(pw.hid_img, pw.side_hid, side); p.bnd0 = pw.hid_bnd + r0(side); p.nc0 = 2 * nC;
-        p.W = L.mlp2; p.nblk = 1; p.rows = nrows(side); p.C = C; p.mode = PG_LN;
+        p.A0 = S.at(pw.hid_img, pw.side_hid, side); p.bnd0 = pw.hid_bnd + S.r0(side); p.nc0 = 2 * nC;
+        p.W = L.mlp2; p.nblk = 1; p.rows = S.rows(side); p.C = C; p.mode = PG_LN;
         p.gamma = W.norm2_w; p.beta = W.norm2_b; p.lnB = L.lnB2;
-        p.resid = xin.f32 + (size_t)r0(side) * C; p.ldr = C; p.bnd_res = xin.bnd + r0(side);
-        p.out = out.f32 + (size_t)r0(side) * C; p.ldo = C;
-        p.pimg = at(out.img, pw.side_C, side); p.p_nct = nC; p.pbnd = out.bnd + r0(side);
+        p.resid = xin.f32 + (size_t)S.r0(side) * C; p.ldr = C; p.bnd_res = xin.bnd + S.r0(side);
+        p.out = out.f32 + (size_t)S.r0(side) * C; p.ldo = C;
+        p.pimg = S.at(out.img, pw.side_C, side); p.p_nct = nC; p.pbnd = out.bnd + S.r0(side);
         xk(p, (size_t)(p.rows + 63) / 64);
     });
     ++pw.xk_epoch;
@@ -454,8 +425,10 @@ struct DenoiseWs {
     float *tgt_l0, *kv_l1;      // step-invariant: layer-0 output of the tgt rows, layer-1 K|V of those rows
     PlanesWs pl;
     const Prepack* pp;          // packed weights of the plane path (set per call)
+    Sides S;                    // src rows, then tgt rows
     static void carve(Carver& c, DenoiseWs& w, const dr_loop_config& cfg, int P, int N, int M) {
         const int C = cfg.C;
+        w.S = Sides(P, N, M);
         const size_t T = (size_t)P * (N + M);
         const size_t lw_begin = align256(c.off);
         LayerWs::carve(c, w.lw, T, C);
@@ -484,136 +457,111 @@ struct DenoiseWs {
 // On the plane path two more pieces stay from step to step (PlanesWs::hoist): layer 0's q | k | v projections of the SRC rows up to the rotary
 // step (their input is the caller's feat0; only the src position code moves: a row-wise kernel applies it per step, V is final), and the q image of
 // layer 1's second cross call (tgt_l0 and the tgt code).
-static int fill_step_invariants(const dr_loop_config& cfg, const dr_loop_weights& w, int P, int N, int M, const float* feat0,
-                          const uint8_t* tokmask, DenoiseWs& ws, hipStream_t st) {
-    const int C = cfg.C, H = cfg.H, PN = P * N, PM = P * M;
-    const Family self_t{PN, M, PN, M};
-    if (ws.pl.on) {
-        const PlCtx X{ws.pp, &ws.pl, &ws.lw, C, H, P, N, M, ws.cosT, ws.sinT, tokmask, (cfg.flags & DR_LOOP_ATTN_F16) ? 1 : 0};
-        int rc = layer_call_planes(X, w.layers[0], 0, ws.pl.feat0, SIDE_TGT, ws.pl.feat0, SIDE_TGT, ws.pl.tgt_l0, self_t, nullptr, st);
-        if (rc == DR_OK && ws.pl.hoist) {
-            PlHoist hz; hz.l0_fill = true;
-            rc = layer_call_planes(X, w.layers[0], 0, ws.pl.feat0, SIDE_SRC, ws.pl.feat0, SIDE_SRC, ws.pl.tgt_l0, Family{0, N, 0, N}, nullptr, st, nullptr, nullptr, hz);
-        }
-        if (rc || cfg.n_layers < 2) return rc;
-        rc = layer_call_planes(X, w.layers[1], 1, ws.pl.tgt_l0, 0, ws.pl.tgt_l0, SIDE_TGT, ws.pl.tgt_l0, self_t, nullptr, st, nullptr, ws.kv_l1);
-        if (rc || !ws.pl.hoist) return rc;
-        PlHoist hz; hz.q1_fill = true;
-        return layer_call_planes(X, w.layers[1], 1, ws.pl.tgt_l0, SIDE_TGT, ws.pl.tgt_l0, 0, ws.pl.tgt_l0, self_t, nullptr, st, nullptr, nullptr, hz);
-    }
-    int rc = layer_call(w.layers[0], C, H, P, feat0, PN, PM, feat0, PN, PM, ws.cosT, ws.sinT, tokmask, self_t, nullptr, ws.lw,
-                        ws.tgt_l0, st);
-    if (rc || cfg.n_layers < 2) return rc;
-    return layer_call(w.layers[1], C, H, P, nullptr, 0, 0, ws.tgt_l0, PN, PM, ws.cosT, ws.sinT, tokmask, self_t, nullptr, ws.lw,
-                      nullptr, st, nullptr, ws.kv_l1);
+static PlCtx plane_ctx(const dr_loop_config& cfg, const DenoiseWs& ws, const uint8_t* tokmask) {
+    return PlCtx{ws.pp, &ws.pl, ws.S, cfg.C, cfg.H, (cfg.flags & DR_LOOP_ATTN_F16) ? 1 : 0, ws.cosT, ws.sinT, tokmask};
+}
+// layer_call on the rows of side(s) xs of x and ys of y
+static int layer_call_sides(const dr_loop_config& cfg, const dr_layer_weights& W, const float* x, int xs, const float* y, int ys, const uint8_t* tokmask,
+                            const Family& f1, const Family* f2, const DenoiseWs& ws, float* out, hipStream_t st, const float* kv_cached = nullptr,
+                            float* kv_store = nullptr) {
+    const Sides& S = ws.S;
+    return layer_call(W, cfg.C, cfg.H, S.P, x, S.r0(xs), S.rows(xs), y, S.r0(ys), S.rows(ys), ws.cosT, ws.sinT, tokmask, f1, f2, ws.lw, out, st,
+                      kv_cached, kv_store);
 }
 
-static int denoiser_and_sim(const dr_loop_config& cfg, const dr_loop_weights& w, int P, int N, int M, const float* feat0,
-                            const uint8_t* tokmask, DenoiseWs& ws, const float** final_feats, hipStream_t st,
-                            bool use_cache = false) {
-    const int C = cfg.C, H = cfg.H, T = P * (N + M), PN = P * N, PM = P * M;
+static int fill_step_invariants(const dr_loop_config& cfg, const dr_loop_weights& w, const float* feat0, const uint8_t* tokmask, DenoiseWs& ws,
+                                hipStream_t st) {
+    const Family self_s = ws.S.self_a(), self_t = ws.S.self_b();
+    if (ws.pl.on) {
+        const PlCtx X = plane_ctx(cfg, ws, tokmask);
+        int rc = layer_call_planes(X, w.layers[0], 0, ws.pl.feat0, SIDE_B, ws.pl.feat0, SIDE_B, ws.pl.tgt_l0, self_t, nullptr, st);
+        if (rc == DR_OK && ws.pl.hoist) {
+            PlHoist hz; hz.l0_fill = true;
+            rc = layer_call_planes(X, w.layers[0], 0, ws.pl.feat0, SIDE_A, ws.pl.feat0, SIDE_A, ws.pl.tgt_l0, self_s, nullptr, st, nullptr, nullptr, hz);
+        }
+        if (rc || cfg.n_layers < 2) return rc;
+        rc = layer_call_planes(X, w.layers[1], 1, ws.pl.tgt_l0, 0, ws.pl.tgt_l0, SIDE_B, ws.pl.tgt_l0, self_t, nullptr, st, nullptr, ws.kv_l1);
+        if (rc || !ws.pl.hoist) return rc;
+        PlHoist hz; hz.q1_fill = true;
+        return layer_call_planes(X, w.layers[1], 1, ws.pl.tgt_l0, SIDE_B, ws.pl.tgt_l0, 0, ws.pl.tgt_l0, self_t, nullptr, st, nullptr, nullptr, hz);
+    }
+    int rc = layer_call_sides(cfg, w.layers[0], feat0, SIDE_B, feat0, SIDE_B, tokmask, self_t, nullptr, ws, ws.tgt_l0, st);
+    if (rc || cfg.n_layers < 2) return rc;
+    return layer_call_sides(cfg, w.layers[1], nullptr, 0, ws.tgt_l0, SIDE_B, tokmask, self_t, nullptr, ws, nullptr, st, nullptr, ws.kv_l1);
+}
+
+static int denoiser_and_sim(const dr_loop_config& cfg, const dr_loop_weights& w, const float* feat0, const uint8_t* tokmask, DenoiseWs& ws,
+                            const float** final_feats, hipStream_t st, bool use_cache = false) {
+    const Sides& S = ws.S;
+    const int C = cfg.C, P = S.P, N = S.La, M = S.Lb, PN = S.rows_a;
     // the matching head on the f32-input GEMM: src_proj on BOTH sides (quirk Q1), rotary, / sqrt(C) ...
     auto head = [&](const float* feats) {
-        return gemm1(feats, C, w.src_proj, nullptr, ws.proj, C, T, C, C, EPI_ROTARY, 1.0f / sqrtf((float)C), nullptr, st, ws.cosT, ws.sinT, C);
+        return gemm1(feats, C, w.src_proj, nullptr, ws.proj, C, S.rows(SIDE_BOTH), C, C, EPI_ROTARY, 1.0f / sqrtf((float)C), nullptr, st, ws.cosT, ws.sinT, C);
     };
     // ... and sim[p] = a_p b_p^T : one NT GEMM per pair, all P pairs as one strided batch
     auto sim = [&]() {
         return gemm1(ws.proj, C, ws.proj + (size_t)PN * C, nullptr, ws.sim, M, N, M, C, EPI_NONE, 1.f, nullptr, st, nullptr, nullptr, 0, P,
                      (long long)N * C, (long long)M * C, (long long)N * M);
     };
+    // with the cache, layer 0 runs on the src half only, written beside the cached tgt half into the cache's own token buffer (rows, plane image,
+    // bounds): layer 1 reads both halves there and nothing later writes to it (no copy of the cached half).  The schedule then starts at layer 1,
+    // whose first cross call takes the cached K | V of the tgt rows (and, on the plane path, whose second takes the q image projected once per call).
+    const int l_begin = use_cache ? 1 : 0;
     if (ws.pl.on) {
-        const PlCtx X{ws.pp, &ws.pl, &ws.lw, C, H, P, N, M, ws.cosT, ws.sinT, tokmask, (cfg.flags & DR_LOOP_ATTN_F16) ? 1 : 0};
-        const Family self_s{0, N, 0, N}, self_t{PN, M, PN, M}, cross_s{0, N, PN, M}, cross_t{PN, M, 0, N};
+        const PlCtx X = plane_ctx(cfg, ws, tokmask);
         const Tok* cur = &ws.pl.feat0;
-        const Tok* bufs[2] = {&ws.pl.fa, &ws.pl.fb};
-        int which = 0;
-        for (int l = 0; l < cfg.n_layers; ++l) {
-            const Tok* nxt = bufs[which];
-            int rc;
-            if (use_cache && l == 0) {
-                // the tgt half of layer 0 is the cache (rows, plane image, bounds): the src half is written beside it, into the cache's
-                // own token buffer -- layer 1 reads both halves there and nothing later writes to it (no copy of the cached half)
-                nxt = &ws.pl.tgt_l0;
-                PlHoist hz; hz.l0_use = ws.pl.hoist;
-                rc = layer_call_planes(X, w.layers[0], 0, *cur, SIDE_SRC, *cur, SIDE_SRC, *nxt, self_s, nullptr, st, nullptr, nullptr, hz);
-                if (rc) return rc;
-                cur = nxt;
-                continue;
-            } else if (l % 2 == 0) {
-                rc = layer_call_planes(X, w.layers[l], l, *cur, SIDE_BOTH, *cur, SIDE_BOTH, *nxt, self_s, &self_t, st);
-                if (rc) return rc;
-            } else {
-                // src attends tgt, then tgt attends the UPDATED src (quirk Q11)
-                rc = layer_call_planes(X, w.layers[l], l, *cur, SIDE_SRC, *cur, SIDE_TGT, *nxt, cross_s, nullptr, st,
-                                       (use_cache && l == 1) ? ws.kv_l1 : nullptr);
-                if (rc) return rc;
-                // (layer 1 with the cache: the queries are tgt_l0's rows under the tgt code -- projected once per call)
-                PlHoist hz; hz.q1_use = use_cache && l == 1 && ws.pl.hoist;
-                rc = layer_call_planes(X, w.layers[l], l, *cur, SIDE_TGT, *nxt, SIDE_SRC, *nxt, cross_t, nullptr, st, nullptr, nullptr, hz);
-                if (rc) return rc;
-            }
-            cur = nxt;
-            which ^= 1;
+        int rc = DR_OK;
+        if (use_cache) {
+            PlHoist hz; hz.l0_use = ws.pl.hoist;
+            rc = layer_call_planes(X, w.layers[0], 0, *cur, SIDE_A, *cur, SIDE_A, ws.pl.tgt_l0, S.self_a(), nullptr, st, nullptr, nullptr, hz);
+            cur = &ws.pl.tgt_l0;
         }
+        if (rc == DR_OK)
+            rc = layer_schedule(S, l_begin, cfg.n_layers, cur, (const Tok*)&ws.pl.fa, (const Tok*)&ws.pl.fb,
+                                [&](int l, int xs, const Tok* x, int ys, const Tok* y, const Tok* out, const Family& f1, const Family* f2) {
+                const bool l1 = use_cache && l == 1;
+                PlHoist hz; hz.q1_use = l1 && xs == SIDE_B && ws.pl.hoist;
+                return layer_call_planes(X, w.layers[l], l, *x, xs, *y, ys, *out, f1, f2, st, (l1 && xs == SIDE_A) ? ws.kv_l1 : nullptr, nullptr, hz);
+            });
+        if (rc) return rc;
         *final_feats = cur->f32;
         if (env_knob("DR_HEAD_F32", 0)) {
             // (experiment: the head's projection on the f32-input MFMA GEMM, 24-bit operands, from the fp32 rows of the last layer)
-            const int rc = head(cur->f32);
+            rc = head(cur->f32);
             return rc ? rc : sim();
         }
         // matching head: src_proj on BOTH sides (quirk Q1), rotary, / sqrt(C)
         PgBatch g;
         memset(&g, 0, sizeof(g));
         size_t xk_next = 0;
-        for (int side = 1; side <= 2; ++side) {
+        S.for_sides(SIDE_BOTH, [&](int side) {
             PgProblem& p = g.p[g.n++];
-            const int r0 = side == SIDE_TGT ? PN : 0;
-            p.A0 = cur->img + (side == SIDE_TGT ? ws.pl.side_C : 0); p.bnd0 = cur->bnd + r0; p.nc0 = C / 16;
-            p.W = ws.pp->head; p.nblk = 1; p.rows = side == SIDE_TGT ? PM : PN; p.C = C; p.mode = PG_F32;
+            const int r0 = S.r0(side);
+            p.A0 = S.at(cur->img, ws.pl.side_C, side); p.bnd0 = cur->bnd + r0; p.nc0 = C / 16;
+            p.W = ws.pp->head; p.nblk = 1; p.rows = S.rows(side); p.C = C; p.mode = PG_F32;
             p.out = ws.proj + (size_t)r0 * C; p.ldo = C; p.blk_stride = 0; p.rot_mask = 1; p.rot_C = C; p.scale = 1.0f / sqrtf((float)C);
             p.cosT = ws.cosT + (size_t)r0 * (C / 2); p.sinT = ws.sinT + (size_t)r0 * (C / 2);
             p.csT = ws.pl.csT + (size_t)r0 * C;
             if (p.W.sub == 2) xk_assign(ws.pl, C, p, xk_next, xk_wide_units(p));
-        }
+        });
         ++ws.pl.xk_epoch;
-        const int rc = launch_pgemm(g, st);
+        rc = launch_pgemm(g, st);
         return rc ? rc : sim();
     }
     const float* cur = feat0;
-    float* bufs[2] = {ws.fa, ws.fb};
-    int which = 0;
-    const Family self_s{0, N, 0, N}, self_t{PN, M, PN, M}, cross_s{0, N, PN, M}, cross_t{PN, M, 0, N};
-    for (int l = 0; l < cfg.n_layers; ++l) {
-        float* nxt = bufs[which];
-        int rc;
-        if (use_cache && l == 0) {
-            // src half only, written beside the cached tgt half (into the cache's own buffer: nothing later writes to it)
-            nxt = ws.tgt_l0;
-            rc = layer_call(w.layers[0], C, H, P, cur, 0, PN, cur, 0, PN, ws.cosT, ws.sinT, tokmask, self_s, nullptr, ws.lw, nxt, st);
-            if (rc) return rc;
-            cur = nxt;
-            continue;
-        } else if (use_cache && l == 1) {
-            rc = layer_call(w.layers[1], C, H, P, cur, 0, PN, cur, PN, PM, ws.cosT, ws.sinT, tokmask, cross_s, nullptr, ws.lw, nxt, st,
-                            ws.kv_l1);
-            if (rc) return rc;
-            rc = layer_call(w.layers[1], C, H, P, cur, PN, PM, nxt, 0, PN, ws.cosT, ws.sinT, tokmask, cross_t, nullptr, ws.lw, nxt, st);
-            if (rc) return rc;
-        } else if (l % 2 == 0) {
-            rc = layer_call(w.layers[l], C, H, P, cur, 0, T, cur, 0, T, ws.cosT, ws.sinT, tokmask, self_s, &self_t, ws.lw, nxt, st);
-            if (rc) return rc;
-        } else {
-            // src attends tgt, then tgt attends the UPDATED src (quirk Q11)
-            rc = layer_call(w.layers[l], C, H, P, cur, 0, PN, cur, PN, PM, ws.cosT, ws.sinT, tokmask, cross_s, nullptr, ws.lw, nxt, st);
-            if (rc) return rc;
-            rc = layer_call(w.layers[l], C, H, P, cur, PN, PM, nxt, 0, PN, ws.cosT, ws.sinT, tokmask, cross_t, nullptr, ws.lw, nxt, st);
-            if (rc) return rc;
-        }
-        cur = nxt;
-        which ^= 1;
+    int rc = DR_OK;
+    if (use_cache) {
+        rc = layer_call_sides(cfg, w.layers[0], cur, SIDE_A, cur, SIDE_A, tokmask, S.self_a(), nullptr, ws, ws.tgt_l0, st);
+        cur = ws.tgt_l0;
     }
+    if (rc == DR_OK)
+        rc = layer_schedule(S, l_begin, cfg.n_layers, cur, ws.fa, ws.fb,
+                            [&](int l, int xs, const float* x, int ys, const float* y, float* out, const Family& f1, const Family* f2) {
+            return layer_call_sides(cfg, w.layers[l], x, xs, y, ys, tokmask, f1, f2, ws, out, st, (use_cache && l == 1 && xs == SIDE_A) ? ws.kv_l1 : nullptr);
+        });
+    if (rc) return rc;
     *final_feats = cur;
-    const int rc = head(cur);
+    rc = head(cur);
     return rc ? rc : sim();
 }
 
@@ -670,25 +618,34 @@ struct LoopWs {
 
 // plane path, once per call: the packed weights (the caller's, or packed now into the workspace) and the plane image of the
 // external features with their row maxima as bounds
-static int planes_begin(const dr_loop_config& cfg, const dr_loop_weights& w, int P, int N, int M, DenoiseWs& ws, Prepack& pp,
-                        hipStream_t st) {
+static int planes_begin(const dr_loop_config& cfg, const dr_loop_weights& w, DenoiseWs& ws, Prepack& pp, hipStream_t st) {
     if (!ws.pl.on) return DR_OK;
-    void* buf = const_cast<void*>(w.prepacked);
-    if (!buf) {
-        buf = ws.pl.own_pack;
-        const int rc = Prepack::fill(buf, cfg, w, st);
-        if (rc) return rc;
-    }
-    Prepack::carve(buf, cfg, &pp);
+    int rc = packed_or_own(cfg, w, ws.pl.own_pack, pp, st);
+    if (rc) return rc;
     ws.pp = &pp;
-    const int C = cfg.C, PN = P * N, PM = P * M;
     if (ws.pl.xk_flags) {
         DR_HIP_CHECK(hipMemsetAsync(ws.pl.xk_flags, 0, pgemm_xk_flag_bytes(), st));
         ws.pl.xk_epoch = 0;
     }
-    int rc = launch_planes_from_f32(ws.pl.feat0.f32, C, PN, C, ws.pl.feat0.img, ws.pl.feat0.bnd, st);
-    if (rc == DR_OK) rc = launch_planes_from_f32(ws.pl.feat0.f32 + (size_t)PN * C, C, PM, C, ws.pl.feat0.img + ws.pl.side_C, ws.pl.feat0.bnd + PN, st);
+    ws.S.for_sides(SIDE_BOTH, [&](int side) { if (rc == DR_OK) rc = side_planes_from_f32(ws.S, side, ws.pl.feat0, cfg.C, ws.pl.side_C, st); });
     return rc;
+}
+
+// what both loop entries do first: lay out the workspace, zero the call's status word, gather the features and the masks in token order
+static int loop_begin(const dr_loop_config& cfg, int P, int N, int M, const float* src_feats, const float* tgt_feats, const uint8_t* src_mask,
+                      const uint8_t* tgt_mask, void* workspace, LoopWs& L, hipStream_t st) {
+    Carver c(workspace);
+    LoopWs::carve(c, L, cfg, P, N, M);
+    DR_HIP_CHECK(hipMemsetAsync(L.status, 0, 16, st));          // the status of THIS call (one 16-byte fill per call)
+    L.dw.pl.status = L.status;
+    const size_t PN = (size_t)P * N, PM = (size_t)P * M;
+    DR_HIP_CHECK(hipMemcpyAsync(L.feat0, src_feats, PN * cfg.C * 4, hipMemcpyDeviceToDevice, st));
+    DR_HIP_CHECK(hipMemcpyAsync(L.feat0 + PN * cfg.C, tgt_feats, PM * cfg.C * 4, hipMemcpyDeviceToDevice, st));
+    if (src_mask) {
+        DR_HIP_CHECK(hipMemcpyAsync(L.tokmask, src_mask, PN, hipMemcpyDeviceToDevice, st));
+        DR_HIP_CHECK(hipMemcpyAsync(L.tokmask + PN, tgt_mask, PM, hipMemcpyDeviceToDevice, st));
+    }
+    return DR_OK;
 }
 
 }  // namespace dr
@@ -810,26 +767,18 @@ int dr_denoiser_match_f32(const dr_loop_config* cfg, const dr_loop_weights* w, i
     if ((src_mask == nullptr) != (tgt_mask == nullptr)) return DR_EINVAL;
     if (!workspace || workspace_bytes < dr_denoise_loop_workspace_bytes(cfg, P, N, M)) return DR_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    Carver c(workspace);
     LoopWs L;
-    LoopWs::carve(c, L, *cfg, P, N, M);
-    DR_HIP_CHECK(hipMemsetAsync(L.status, 0, 16, st));          // the status of THIS call (one 16-byte fill per call)
-    L.dw.pl.status = L.status;
+    rc = loop_begin(*cfg, P, N, M, src_feats, tgt_feats, src_mask, tgt_mask, workspace, L, st);
+    if (rc) return rc;
     const int C = cfg->C;
     const size_t PN = (size_t)P * N, PM = (size_t)P * M;
-    DR_HIP_CHECK(hipMemcpyAsync(L.feat0, src_feats, PN * C * 4, hipMemcpyDeviceToDevice, st));
-    DR_HIP_CHECK(hipMemcpyAsync(L.feat0 + PN * C, tgt_feats, PM * C * 4, hipMemcpyDeviceToDevice, st));
-    if (src_mask) {
-        DR_HIP_CHECK(hipMemcpyAsync(L.tokmask, src_mask, PN, hipMemcpyDeviceToDevice, st));
-        DR_HIP_CHECK(hipMemcpyAsync(L.tokmask + PN, tgt_mask, PM, hipMemcpyDeviceToDevice, st));
-    }
     Prepack pp;
-    rc = planes_begin(*cfg, *w, P, N, M, L.dw, pp, st);
+    rc = planes_begin(*cfg, *w, L.dw, pp, st);
     if (rc) return rc;
     rc = fill_pe(*cfg, *w, P, N, M, s_pcd_warped, nullptr, nullptr, t_pcd, true, true, L.dw, st);
     if (rc) return rc;
     const float* fin = nullptr;
-    rc = denoiser_and_sim(*cfg, *w, P, N, M, L.feat0, src_mask ? L.tokmask : nullptr, L.dw, &fin, st);
+    rc = denoiser_and_sim(*cfg, *w, L.feat0, src_mask ? L.tokmask : nullptr, L.dw, &fin, st);
     if (rc) return rc;
     if (src_out) DR_HIP_CHECK(hipMemcpyAsync(src_out, fin, PN * C * 4, hipMemcpyDeviceToDevice, st));
     if (tgt_out) DR_HIP_CHECK(hipMemcpyAsync(tgt_out, fin + PN * C, PM * C * 4, hipMemcpyDeviceToDevice, st));
@@ -853,11 +802,9 @@ int dr_denoise_loop(const dr_loop_config* cfg, const dr_loop_weights* w, int P, 
     if (trace && (trace->force_R == nullptr) != (trace->force_t == nullptr)) return DR_EINVAL;
     if (!workspace || workspace_bytes < dr_denoise_loop_workspace_bytes(cfg, P, N, M)) return DR_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    Carver c(workspace);
     LoopWs L;
-    LoopWs::carve(c, L, *cfg, P, N, M);
-    DR_HIP_CHECK(hipMemsetAsync(L.status, 0, 16, st));          // the status of THIS call (one 16-byte fill per call)
-    L.dw.pl.status = L.status;
+    rc = loop_begin(*cfg, P, N, M, src_feats, tgt_feats, src_mask, tgt_mask, workspace, L, st);
+    if (rc) return rc;
     const int C = cfg->C;
     const size_t PN = (size_t)P * N, PM = (size_t)P * M, NM = (size_t)P * N * M;
     const uint8_t* tokmask = src_mask ? L.tokmask : nullptr;
@@ -868,24 +815,18 @@ int dr_denoise_loop(const dr_loop_config* cfg, const dr_loop_weights* w, int P, 
     const uint8_t* rsm = ragged ? src_mask : nullptr;
     const uint8_t* rtm = ragged ? tgt_mask : nullptr;
 
-    DR_HIP_CHECK(hipMemcpyAsync(L.feat0, src_feats, PN * C * 4, hipMemcpyDeviceToDevice, st));
-    DR_HIP_CHECK(hipMemcpyAsync(L.feat0 + PN * C, tgt_feats, PM * C * 4, hipMemcpyDeviceToDevice, st));
-    if (src_mask) {
-        DR_HIP_CHECK(hipMemcpyAsync(L.tokmask, src_mask, PN, hipMemcpyDeviceToDevice, st));
-        DR_HIP_CHECK(hipMemcpyAsync(L.tokmask + PN, tgt_mask, PM, hipMemcpyDeviceToDevice, st));
-    }
     rc = launch_f32_to_f64(x_T, L.x, NM, st);     // exact widening; step 1 keeps float32 semantics
     if (rc) return rc;
     if (!v4d && P <= 32)                          // arrival counters of the multi-workgroup minimum (few pairs: stateops.hip)
         DR_HIP_CHECK(hipMemsetAsync((char*)L.pmin + pair_min_scratch_bytes(P) - 64 * (size_t)P, 0, 64 * (size_t)P, st));
     Prepack pp;
-    rc = planes_begin(*cfg, *w, P, N, M, L.dw, pp, st);
+    rc = planes_begin(*cfg, *w, L.dw, pp, st);
     if (rc) return rc;
     // the target cloud never moves: its position code is computed once (the reference recomputes it
     // every step, transformero.py:166)
     rc = fill_pe(*cfg, *w, P, N, M, s_pcd, nullptr, nullptr, t_pcd, false, true, L.dw, st);
     if (rc) return rc;
-    rc = fill_step_invariants(*cfg, *w, P, N, M, L.feat0, tokmask, L.dw, st);
+    rc = fill_step_invariants(*cfg, *w, L.feat0, tokmask, L.dw, st);
     if (rc) return rc;
 
     // -- the steps: x <- x - x.min() first (3D only), per-step noise (4D only); the denoiser of a step is the position code of the warped
@@ -904,7 +845,7 @@ int dr_denoise_loop(const dr_loop_config* cfg, const dr_loop_weights* w, int P, 
     sa.skws = L.skws; sa.skws_bytes = L.skws_bytes; sa.pws = L.pws; sa.pws_bytes = L.pws_bytes; sa.status = L.status;
     rc = reverse_sampling(sa, [&](const float* Rf, const float* tf) -> int {
         int r = fill_pe(*cfg, *w, P, N, M, s_pcd, Rf, tf, t_pcd, true, false, L.dw, st);
-        if (r == DR_OK) r = denoiser_and_sim(*cfg, *w, P, N, M, L.feat0, tokmask, L.dw, &fin, st, true);
+        if (r == DR_OK) r = denoiser_and_sim(*cfg, *w, L.feat0, tokmask, L.dw, &fin, st, true);
         if (r) return r;
         return sinkhorn_f32(P, N, M, L.dw.sim, src_mask, tgt_mask, w->bin_score, cfg->sk_iters, DR_SK_OUT_CONF | mflag, L.x0, L.skws, L.skws_bytes, st,
                             L.status);

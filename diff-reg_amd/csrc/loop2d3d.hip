@@ -5,6 +5,7 @@
 // with loop.hip.
 //
 // Token layout: image patches of all P pairs (pair p at row p*M), then point nodes (P*M + p*N).
+// In the terms of loop_common.h's Sides: side A = image patches (M rows per pair), side B = point nodes (N rows per pair).
 //
 // Round 4: calls of >= 4096 token rows (two cfg5 pairs or more) run the layer on fp16 hi / lo plane images (pgemm.h) like
 // dr_denoise_loop: the biased q | k | v projections write the attention kernel's operand images, attention_planes_kernel (d = 64)
@@ -37,24 +38,20 @@ struct Prepack2 {
     static size_t carve(void* buf, const dr_loop2d3d_config& cfg, Prepack2* pp) {
         Carver c(buf);
         const int C = cfg.C, nC = C / 16;
-        auto take = [&](int nblk, int nct, PgW* v) {
-            char* p = c.take<char>(pgemm_weight_bytes(C, nblk, nct));
-            if (pp && buf) pgemm_weight_view(p, C, nblk, nct, v);
-        };
         for (int l = 0; l < cfg.n_layers; ++l) {
             P2Layer* L = pp ? &pp->L[l] : nullptr;
-            take(3, nC, L ? &L->qkv : nullptr);
-            take(1, nC, L ? &L->lin : nullptr);
-            take(2, nC, L ? &L->expand : nullptr);
-            take(1, 2 * nC, L ? &L->squeeze : nullptr);
+            take_weight(c, C, 3, nC, L ? &L->qkv : nullptr);
+            take_weight(c, C, 1, nC, L ? &L->lin : nullptr);
+            take_weight(c, C, 2, nC, L ? &L->expand : nullptr);
+            take_weight(c, C, 1, 2 * nC, L ? &L->squeeze : nullptr);
             float* b = c.take<float>(3 * (size_t)C + 16);
             if (L && buf) {
                 L->qkv_b = b; L->qkv_bmax = b + 3 * C; L->lin_bmax = b + 3 * C + 3; L->exp_bmax = b + 3 * C + 4; L->sq_bmax = b + 3 * C + 6;
                 L->lnB1 = b + 3 * C + 7; L->lnB2 = b + 3 * C + 8;
             }
         }
-        take(1, nC, pp ? &pp->out : nullptr);
-        take(1, nC, pp ? &pp->head : nullptr);
+        take_weight(c, C, 1, nC, pp ? &pp->out : nullptr);
+        take_weight(c, C, 1, nC, pp ? &pp->head : nullptr);
         float* ob = c.take<float>(4);
         if (pp && buf) pp->out_bmax = ob;
         return c.off + 256;
@@ -149,9 +146,8 @@ struct F2Ws {
 };
 
 // one vision3d TransformerLayer: x rows [xr0, +xrows) of xin attend y rows [yr0, +yrows) of yin
-static int fusion_layer(const dr_fusion_layer_weights& W, int C, int H, int P, const float* xin, int xr0, int xrows, int Lx,
-                        const float* yin, int yr0, int yrows, int Ly, int nfam, int xr0b, int Lxb, int yr0b, int Lyb,
-                        const F2Ws& ws, float* out, hipStream_t st) {
+static int fusion_layer(const dr_fusion_layer_weights& W, int C, int H, int P, const float* xin, int xr0, int xrows, const float* yin, int yr0,
+                        int yrows, const Family& f1, const Family* f2, const F2Ws& ws, float* out, hipStream_t st) {
     GemmBatch g;
     memset(&g, 0, sizeof(g));
     auto proj = [&](GemmProblem& p, const float* in, int r0, int rows, const float* Wm, const float* b, int coloff) {
@@ -168,8 +164,7 @@ static int fusion_layer(const dr_fusion_layer_weights& W, int C, int H, int P, c
     memset(&a, 0, sizeof(a));
     a.q = ws.qkv; a.k = ws.qkv + C; a.v = ws.qkv + 2 * C; a.out = ws.att;
     a.ldq = a.ldk = a.ldv = 3 * C; a.ldo = C; a.H = H; a.d = C / H;
-    a.nseg = P; a.q0 = xr0; a.qstride = Lx; a.Lq = Lx; a.k0 = yr0; a.kstride = Ly; a.Lk = Ly;
-    if (nfam == 2) { a.nseg2 = P; a.q0b = xr0b; a.qstrideb = Lxb; a.Lqb = Lxb; a.k0b = yr0b; a.kstrideb = Lyb; a.Lkb = Lyb; }
+    attn_families(a, P, f1, f2);
     a.scale = 1.0f / sqrtf((float)(C / H));
     rc = launch_attention(a, st);
     if (rc) return rc;
@@ -187,45 +182,38 @@ static int fusion_layer(const dr_fusion_layer_weights& W, int C, int H, int P, c
 }
 
 // ---- one vision3d TransformerLayer call on plane images: five launches ---------------------------------------------------------
-enum { SIDE_IMG = 1, SIDE_PCD = 2, SIDE_BOTH2 = 3 };
-struct P2Ctx { const Prepack2* pp; const Planes2* pw; int C, H, P, N, M; int attn_f16; };
+using P2Ctx = PlaneCtx<Prepack2, Planes2>;
 // x rows of side(s) xs of `xin` attend the rows of side(s) ys of `yin`; out gets the x sides (fp32 rows + image + bounds)
 static int fusion_layer_planes(const P2Ctx& X, const dr_fusion_layer_weights& W, int l, const Tok& xin, int xs, const Tok& yin, int ys,
                                const Tok& out, const Family& f1, const Family* f2, hipStream_t st) {
-    const int C = X.C, H = X.H, PM = X.P * X.M, PN = X.P * X.N, T = PM + PN, nC = C / 16, d = C / H;
+    const Sides& S = X.S;
+    const int C = X.C, H = X.H, PM = S.rows_a, T = S.rows(SIDE_BOTH), nC = C / 16, d = C / H;
     const P2Layer& L = X.pp->L[l];
     const Planes2& pw = *X.pw;
-    auto r0 = [&](int side) { return side == SIDE_PCD ? PM : 0; };
-    auto nrows = [&](int side) { return side == SIDE_PCD ? PN : PM; };
-    auto per_pair = [&](int side) { return side == SIDE_PCD ? X.N : X.M; };
-    auto at = [&](char* img, size_t side_off, int side) { return img + (side == SIDE_PCD ? side_off : 0); };
     PgBatch g;
     auto reset = [&]() { memset(&g, 0, sizeof(g)); };
     auto add = [&]() -> PgProblem& { return g.p[g.n++]; };
-    auto for_sides = [&](int mask, auto fn) { for (int side = 1; side <= 2; ++side) if (mask & side) fn(side); };
-    int rc = DR_OK;
     // bound of the keys' source rows per group (pair x side): all keys of a group share one scale in the k and v images
     // (taken inside the projection's kernel when a group is a whole number of workgroups: pgemm.h)
-    const bool grp_inline = X.N % 128 == 0 && X.M % 128 == 0 && env_knob("DR_LOOP_GRP_INLINE", 1) != 0;
-    for (int side = 1; side <= 2 && rc == DR_OK && !grp_inline; ++side)
-        if (ys & side) rc = launch_group_max(yin.bnd + r0(side), X.P, per_pair(side), pw.grp_x + (side == SIDE_PCD ? X.P : 0), st);
+    const bool grp_inline = S.La % 128 == 0 && S.Lb % 128 == 0 && env_knob("DR_LOOP_GRP_INLINE", 1) != 0;
+    int rc = grp_inline ? DR_OK : side_group_max(S, ys, yin.bnd, pw.grp_x, st);
     if (rc) return rc;
     // ---- q | k | v = x W^T + b -> three plane images (head h at k = h d), no rotary (vision3d/layers/transformer.py:96-104)
     auto proj = [&](const Tok& tin, int side, int b0, int nblk, int grpm) {
         PgProblem& p = add();
-        p.A0 = at(tin.img, pw.side_C, side); p.bnd0 = tin.bnd + r0(side); p.nc0 = nC;
-        p.W = pgw_blocks(L.qkv, b0, C); p.nblk = nblk; p.rows = nrows(side); p.C = C; p.k_alg = C; p.mode = PG_PLANES; p.scale = 1.f;
+        p.A0 = S.at(tin.img, pw.side_C, side); p.bnd0 = tin.bnd + S.r0(side); p.nc0 = nC;
+        p.W = pgw_blocks(L.qkv, b0, C); p.nblk = nblk; p.rows = S.rows(side); p.C = C; p.k_alg = C; p.mode = PG_PLANES; p.scale = 1.f;
         p.bias = L.qkv_b + (size_t)b0 * C; p.bias_max = L.qkv_bmax + b0;
-        p.pimg = at(pw.qkv_img + (size_t)b0 * pw.qkv_stride, pw.side_C, side); p.p_nct = nC; p.pbnd = pw.qkv_bnd + (size_t)b0 * T + r0(side);
+        p.pimg = S.at(pw.qkv_img + (size_t)b0 * pw.qkv_stride, pw.side_C, side); p.p_nct = nC; p.pbnd = pw.qkv_bnd + (size_t)b0 * T + S.r0(side);
         p.pimg_blk_stride = (long long)pw.qkv_stride; p.pbnd_blk_stride = T;
-        p.grp_bnd = grp_inline ? nullptr : pw.grp_x; p.grp_mask = grpm; p.grp_first = side == SIDE_PCD ? X.P : 0; p.grp_rows = per_pair(side);
+        p.grp_bnd = grp_inline ? nullptr : pw.grp_x; p.grp_mask = grpm; p.grp_first = S.grp_first(side); p.grp_rows = S.per_pair(side);
     };
     reset();
     if (xs == ys && xin.img == yin.img) {
-        for_sides(xs, [&](int side) { proj(xin, side, 0, 3, 6); });
+        S.for_sides(xs, [&](int side) { proj(xin, side, 0, 3, 6); });
     } else {
-        for_sides(xs, [&](int side) { proj(xin, side, 0, 1, 0); });
-        for_sides(ys, [&](int side) { proj(yin, side, 1, 2, 3); });
+        S.for_sides(xs, [&](int side) { proj(xin, side, 0, 1, 0); });
+        S.for_sides(ys, [&](int side) { proj(yin, side, 1, 2, 3); });
     }
     rc = launch_pgemm(g, st);
     if (rc) return rc;
@@ -233,8 +221,7 @@ static int fusion_layer_planes(const P2Ctx& X, const dr_fusion_layer_weights& W,
     AttnArgs a;
     memset(&a, 0, sizeof(a));
     a.H = H; a.d = d;
-    a.nseg = X.P; a.q0 = f1.q0; a.qstride = f1.Lq; a.Lq = f1.Lq; a.k0 = f1.k0; a.kstride = f1.Lk; a.Lk = f1.Lk;
-    if (f2) { a.nseg2 = X.P; a.q0b = f2->q0; a.qstrideb = f2->Lq; a.Lqb = f2->Lq; a.k0b = f2->k0; a.kstrideb = f2->Lk; a.Lkb = f2->Lk; }
+    attn_families(a, S.P, f1, f2);
     a.scale = 1.0f / sqrtf((float)d);
     a.pimg[0] = pw.att_img; a.pimg[1] = pw.att_img + pw.side_C; a.p_split = PM; a.p_nct = nC; a.p_dp = d; a.pbnd = pw.att_bnd;
     a.qimg[0] = pw.qkv_img; a.qimg[1] = pw.qkv_img + pw.side_C;
@@ -246,38 +233,38 @@ static int fusion_layer_planes(const P2Ctx& X, const dr_fusion_layer_weights& W,
     if (rc) return rc;
     // ---- z = LayerNorm(linear(h) + b + x)   (transformer.py:188-196)
     reset();
-    for_sides(xs, [&](int side) {
+    S.for_sides(xs, [&](int side) {
         PgProblem& p = add();
-        p.A0 = at(pw.att_img, pw.side_C, side); p.bnd0 = pw.att_bnd + r0(side); p.nc0 = nC;
-        p.W = L.lin; p.nblk = 1; p.rows = nrows(side); p.C = C; p.k_alg = C; p.mode = PG_LN; p.bias = W.lin_b;
+        p.A0 = S.at(pw.att_img, pw.side_C, side); p.bnd0 = pw.att_bnd + S.r0(side); p.nc0 = nC;
+        p.W = L.lin; p.nblk = 1; p.rows = S.rows(side); p.C = C; p.k_alg = C; p.mode = PG_LN; p.bias = W.lin_b;
         p.gamma = W.norm1_w; p.beta = W.norm1_b; p.lnB = L.lnB1;
-        p.resid = xin.f32 + (size_t)r0(side) * C; p.ldr = C; p.ln_postadd = 1;
-        p.out = pw.z.f32 + (size_t)r0(side) * C; p.ldo = C;
-        p.pimg = at(pw.z.img, pw.side_C, side); p.p_nct = nC; p.pbnd = pw.z.bnd + r0(side);
+        p.resid = xin.f32 + (size_t)S.r0(side) * C; p.ldr = C; p.ln_postadd = 1;
+        p.out = pw.z.f32 + (size_t)S.r0(side) * C; p.ldo = C;
+        p.pimg = S.at(pw.z.img, pw.side_C, side); p.p_nct = nC; p.pbnd = pw.z.bnd + S.r0(side);
     });
     rc = launch_pgemm(g, st);
     if (rc) return rc;
     // ---- hidden = relu(expand(z) + b)   (transformer.py:262-266)
     reset();
-    for_sides(xs, [&](int side) {
+    S.for_sides(xs, [&](int side) {
         PgProblem& p = add();
-        p.A0 = at(pw.z.img, pw.side_C, side); p.bnd0 = pw.z.bnd + r0(side); p.nc0 = nC;
-        p.W = L.expand; p.nblk = 2; p.rows = nrows(side); p.C = C; p.k_alg = C; p.mode = PG_PLANES; p.relu = 1; p.scale = 1.f;
+        p.A0 = S.at(pw.z.img, pw.side_C, side); p.bnd0 = pw.z.bnd + S.r0(side); p.nc0 = nC;
+        p.W = L.expand; p.nblk = 2; p.rows = S.rows(side); p.C = C; p.k_alg = C; p.mode = PG_PLANES; p.relu = 1; p.scale = 1.f;
         p.bias = W.expand_b; p.bias_max = L.exp_bmax;
-        p.pimg = at(pw.hid_img, pw.side_hid, side); p.p_nct = 2 * nC; p.pbnd = pw.hid_bnd + r0(side);
+        p.pimg = S.at(pw.hid_img, pw.side_hid, side); p.p_nct = 2 * nC; p.pbnd = pw.hid_bnd + S.r0(side);
     });
     rc = launch_pgemm(g, st);
     if (rc) return rc;
     // ---- out = LayerNorm(z + squeeze(hidden) + b)   (transformer.py:267-271)
     reset();
-    for_sides(xs, [&](int side) {
+    S.for_sides(xs, [&](int side) {
         PgProblem& p = add();
-        p.A0 = at(pw.hid_img, pw.side_hid, side); p.bnd0 = pw.hid_bnd + r0(side); p.nc0 = 2 * nC;
-        p.W = L.squeeze; p.nblk = 1; p.rows = nrows(side); p.C = C; p.k_alg = 2 * C; p.mode = PG_LN; p.bias = W.squeeze_b;
+        p.A0 = S.at(pw.hid_img, pw.side_hid, side); p.bnd0 = pw.hid_bnd + S.r0(side); p.nc0 = 2 * nC;
+        p.W = L.squeeze; p.nblk = 1; p.rows = S.rows(side); p.C = C; p.k_alg = 2 * C; p.mode = PG_LN; p.bias = W.squeeze_b;
         p.gamma = W.norm2_w; p.beta = W.norm2_b; p.lnB = L.lnB2;
-        p.resid = pw.z.f32 + (size_t)r0(side) * C; p.ldr = C; p.ln_postadd = 1;
-        p.out = out.f32 + (size_t)r0(side) * C; p.ldo = C;
-        p.pimg = at(out.img, pw.side_C, side); p.p_nct = nC; p.pbnd = out.bnd + r0(side);
+        p.resid = pw.z.f32 + (size_t)S.r0(side) * C; p.ldr = C; p.ln_postadd = 1;
+        p.out = out.f32 + (size_t)S.r0(side) * C; p.ldo = C;
+        p.pimg = S.at(out.img, pw.side_C, side); p.p_nct = nC; p.pbnd = out.bnd + S.r0(side);
     });
     return launch_pgemm(g, st);
 }
@@ -327,6 +314,7 @@ int dr_denoise_loop_2d3d(const dr_loop2d3d_config* cfg, const dr_fusion_weights*
     F2Ws L;
     F2Ws::carve(c, L, *cfg, P, N, M);
     DR_HIP_CHECK(hipMemsetAsync(L.status, 0, 16, st));          // the status of THIS call (dr_denoise_loop_status)
+    const Sides S(P, M, N);             // image patches, then point nodes
     const int C = cfg->C, H = cfg->H, PM = P * M, PN = P * N, T = PM + PN;
     const size_t NM = (size_t)P * N * M;
     const int strict = (cfg->flags & DR_LOOP_STRICT_F64) ? DR_SK_STRICT : 0;
@@ -353,19 +341,12 @@ int dr_denoise_loop_2d3d(const dr_loop2d3d_config* cfg, const dr_fusion_weights*
     // and the image half of layer 0 (a self layer: image tokens attend image tokens only -- step-invariant)
     Prepack2 pp;
     const bool want_feat = cfg->steps == 0;
-    if (L.pl.on) {
-        void* buf = const_cast<void*>(w->prepacked);
-        if (!buf) {
-            buf = L.pl.own_pack;
-            rc = Prepack2::fill(buf, *cfg, *w, st);
-            if (rc) return rc;
-        }
-        Prepack2::carve(buf, *cfg, &pp);
-        rc = launch_planes_from_f32(L.tok0, C, PM, C, L.pl.tok0.img, L.pl.tok0.bnd, st);
-        if (rc) return rc;
-        const P2Ctx X{&pp, &L.pl, C, H, P, N, M, (cfg->flags & DR_LOOP_ATTN_F16) ? 1 : 0};
-        const Family self_i{0, M, 0, M};
-        rc = fusion_layer_planes(X, w->layers[0], 0, L.pl.tok0, SIDE_IMG, L.pl.tok0, SIDE_IMG, L.pl.l0, self_i, nullptr, st);
+    const Planes2& pw = L.pl;
+    const P2Ctx X{&pp, &pw, S, C, H, (cfg->flags & DR_LOOP_ATTN_F16) ? 1 : 0};
+    if (pw.on) {
+        rc = packed_or_own(*cfg, *w, pw.own_pack, pp, st);
+        if (rc == DR_OK) rc = side_planes_from_f32(S, SIDE_A, pw.tok0, C, pw.side_C, st);
+        if (rc == DR_OK) rc = fusion_layer_planes(X, w->layers[0], 0, pw.tok0, SIDE_A, pw.tok0, SIDE_A, pw.l0, S.self_a(), nullptr, st);
         if (rc) return rc;
     }
 
@@ -375,56 +356,42 @@ int dr_denoise_loop_2d3d(const dr_loop2d3d_config* cfg, const dr_fusion_weights*
         if (r) return r;
         r = gemm1(L.emb3, 64, w->pcd_emb_w, w->pcd_emb_b, L.tok0 + (size_t)PM * C, C, PN, C, 64, EPI_NONE, 1.f, L.proj + (size_t)PM * C, st);
         if (r) return r;
-        if (L.pl.on) {
-            const Planes2& pw = L.pl;
-            const P2Ctx X{&pp, &pw, C, H, P, N, M, (cfg->flags & DR_LOOP_ATTN_F16) ? 1 : 0};
-            const Family self_i{0, M, 0, M}, self_p{PM, N, PM, N}, cross_i{0, M, PM, N}, cross_p{PM, N, 0, M};
+        if (pw.on) {
             // the point tokens of this step -> their part of the token image (row maxima as bounds)
-            r = launch_planes_from_f32(L.tok0 + (size_t)PM * C, C, PN, C, pw.tok0.img + pw.side_C, pw.tok0.bnd + PM, st);
+            r = side_planes_from_f32(S, SIDE_B, pw.tok0, C, pw.side_C, st);
             if (r) return r;
-            // layer 0 (self): the image half is step-invariant and sits in pw.l0 already (l0_image_half below); the point half joins it there
-            r = fusion_layer_planes(X, w->layers[0], 0, pw.tok0, SIDE_PCD, pw.tok0, SIDE_PCD, pw.l0, self_p, nullptr, st);
+            // layer 0 (self): the image half is step-invariant and sits in pw.l0 already (evaluated once per call, above); the point half joins it there
+            r = fusion_layer_planes(X, w->layers[0], 0, pw.tok0, SIDE_B, pw.tok0, SIDE_B, pw.l0, S.self_b(), nullptr, st);
             if (r) return r;
             const Tok* cur = &pw.l0;
-            const Tok* bufs[2] = {&pw.ta, &pw.tb};
-            int which = 0;
-            for (int l = 1; l < cfg->n_layers; ++l) {
-                const Tok* nxt = bufs[which];
-                if (l % 2 == 0) {
-                    r = fusion_layer_planes(X, w->layers[l], l, *cur, SIDE_BOTH2, *cur, SIDE_BOTH2, *nxt, self_i, &self_p, st);
-                    if (r) return r;
-                } else {        // image <- points, then points <- UPDATED image (fusion_module.py:101-102)
-                    r = fusion_layer_planes(X, w->layers[l], l, *cur, SIDE_IMG, *cur, SIDE_PCD, *nxt, cross_i, nullptr, st);
-                    if (r) return r;
-                    r = fusion_layer_planes(X, w->layers[l], l, *cur, SIDE_PCD, *nxt, SIDE_IMG, *nxt, cross_p, nullptr, st);
-                    if (r) return r;
-                }
-                cur = nxt;
-                which ^= 1;
-            }
+            r = layer_schedule(S, 1, cfg->n_layers, cur, &pw.ta, &pw.tb,
+                               [&](int l, int xs, const Tok* x, int ys, const Tok* y, const Tok* out, const Family& f1, const Family* f2) {
+                return fusion_layer_planes(X, w->layers[l], l, *x, xs, *y, ys, *out, f1, f2, st);
+            });
+            if (r) return r;
             // out_proj (+ bias) -> image (+ fp32 rows when the caller wants the features), then the matching head's src_proj on both
             // sides (Q1) / sqrt(C) -> fp32 rows for the similarity
             PgBatch g;
             memset(&g, 0, sizeof(g));
-            for (int side = 1; side <= 2; ++side) {
+            S.for_sides(SIDE_BOTH, [&](int side) {
                 PgProblem& p = g.p[g.n++];
-                const int r0 = side == SIDE_PCD ? PM : 0;
-                p.A0 = cur->img + (side == SIDE_PCD ? pw.side_C : 0); p.bnd0 = cur->bnd + r0; p.nc0 = C / 16;
-                p.W = pp.out; p.nblk = 1; p.rows = side == SIDE_PCD ? PN : PM; p.C = C; p.k_alg = C; p.mode = PG_PLANES; p.scale = 1.f;
+                const int r0 = S.r0(side);
+                p.A0 = S.at(cur->img, pw.side_C, side); p.bnd0 = cur->bnd + r0; p.nc0 = C / 16;
+                p.W = pp.out; p.nblk = 1; p.rows = S.rows(side); p.C = C; p.k_alg = C; p.mode = PG_PLANES; p.scale = 1.f;
                 p.bias = w->out_b; p.bias_max = pp.out_bmax;
-                p.pimg = pw.feat_img + (side == SIDE_PCD ? pw.side_C : 0); p.p_nct = C / 16; p.pbnd = pw.feat_bnd + r0;
+                p.pimg = S.at(pw.feat_img, pw.side_C, side); p.p_nct = C / 16; p.pbnd = pw.feat_bnd + r0;
                 if (want_feat) { p.out = L.feat + (size_t)r0 * C; p.ldo = C; }
-            }
+            });
             r = launch_pgemm(g, st);
             if (r) return r;
             memset(&g, 0, sizeof(g));
-            for (int side = 1; side <= 2; ++side) {
+            S.for_sides(SIDE_BOTH, [&](int side) {
                 PgProblem& p = g.p[g.n++];
-                const int r0 = side == SIDE_PCD ? PM : 0;
-                p.A0 = pw.feat_img + (side == SIDE_PCD ? pw.side_C : 0); p.bnd0 = pw.feat_bnd + r0; p.nc0 = C / 16;
-                p.W = pp.head; p.nblk = 1; p.rows = side == SIDE_PCD ? PN : PM; p.C = C; p.k_alg = C; p.mode = PG_F32;
+                const int r0 = S.r0(side);
+                p.A0 = S.at(pw.feat_img, pw.side_C, side); p.bnd0 = pw.feat_bnd + r0; p.nc0 = C / 16;
+                p.W = pp.head; p.nblk = 1; p.rows = S.rows(side); p.C = C; p.k_alg = C; p.mode = PG_F32;
                 p.out = L.z + (size_t)r0 * C; p.ldo = C; p.scale = 1.0f / sqrtf((float)C);
-            }
+            });
             r = launch_pgemm(g, st);
             if (r) return r;
             r = gemm1(L.z + (size_t)PM * C, C, L.z, nullptr, L.sim, M, N, M, C, EPI_NONE, 1.f, nullptr, st, nullptr, nullptr, 0, P, (long long)N * C,
@@ -434,22 +401,11 @@ int dr_denoise_loop_2d3d(const dr_loop2d3d_config* cfg, const dr_fusion_weights*
                                 L.skws_bytes, st, L.status);
         }
         const float* cur = L.tok0;
-        float* bufs[2] = {L.ta, L.tb};
-        int which = 0;
-        for (int l = 0; l < cfg->n_layers; ++l) {
-            float* nxt = bufs[which];
-            if (l % 2 == 0) {   // self: image tokens and point tokens, same weights, one launch family each
-                r = fusion_layer(w->layers[l], C, H, P, cur, 0, T, M, cur, 0, T, M, 2, PM, N, PM, N, L, nxt, st);
-                if (r) return r;
-            } else {            // cross: image <- points, then points <- UPDATED image (fusion_module.py:101-102)
-                r = fusion_layer(w->layers[l], C, H, P, cur, 0, PM, M, cur, PM, PN, N, 1, 0, 0, 0, 0, L, nxt, st);
-                if (r) return r;
-                r = fusion_layer(w->layers[l], C, H, P, cur, PM, PN, N, nxt, 0, PM, M, 1, 0, 0, 0, 0, L, nxt, st);
-                if (r) return r;
-            }
-            cur = nxt;
-            which ^= 1;
-        }
+        r = layer_schedule(S, 0, cfg->n_layers, cur, L.ta, L.tb,
+                           [&](int l, int xs, const float* x, int ys, const float* y, float* out, const Family& f1, const Family* f2) {
+            return fusion_layer(w->layers[l], C, H, P, x, S.r0(xs), S.rows(xs), y, S.r0(ys), S.rows(ys), f1, f2, L, out, st);
+        });
+        if (r) return r;
         r = gemm1(cur, C, w->out_w, w->out_b, L.feat, C, T, C, C, EPI_NONE, 1.f, nullptr, st);
         if (r) return r;
         // matching head: src_proj on both sides (Q1), / sqrt(C), sim[p] = pcd_p img_p^T  (EXP/matching.py:100-125)

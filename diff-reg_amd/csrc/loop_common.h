@@ -1,7 +1,7 @@
 // loop_common.h -- host helpers shared by the two denoise loops (loop.hip, loop2d3d.hip), the single-op entries (api.hip) and the training
-// entry points: the carving of caller memory, the plane path's small types and its on / off rule, a one-problem GEMM launch, and
-// reverse_sampling(), the ONE driver of the reverse-diffusion steps -- both loops honour the dr_loop_trace / teacher-forcing contract
-// through it.
+// entry points: the carving of caller memory, the two-sided token view (Sides) and the ONE layer schedule of both denoisers, the plane
+// path's small types, its packed-weight plumbing and its on / off rule, a one-problem GEMM launch, and reverse_sampling(), the ONE driver of
+// the reverse-diffusion steps -- both loops honour the dr_loop_trace / teacher-forcing contract through it.
 #pragma once
 #include <math.h>
 #include <string.h>
@@ -30,6 +30,101 @@ struct Tok { float* f32; char* img; float* bnd; };
 struct Family {   // P segments: queries rows q0 + p*Lq (+Lq) attend keys rows k0 + p*Lk (+Lk)
     int q0, Lq, k0, Lk;
 };
+// the one or two families of an attention launch
+static inline void attn_families(AttnArgs& a, int P, const Family& f1, const Family* f2) {
+    a.nseg = P; a.q0 = f1.q0; a.qstride = f1.Lq; a.Lq = f1.Lq; a.k0 = f1.k0; a.kstride = f1.Lk; a.Lk = f1.Lk;
+    if (f2) { a.nseg2 = P; a.q0b = f2->q0; a.qstrideb = f2->Lq; a.Lqb = f2->Lq; a.k0b = f2->k0; a.kstrideb = f2->Lk; a.Lkb = f2->Lk; }
+}
+
+// The two token sides of a call: all rows of side A (pair p at p * La), then all rows of side B (pair p at rows_a + p * Lb).  Which side is
+// which is the loop's business (the header comment of loop.hip / loop2d3d.hip says).  A `side` argument is SIDE_A or SIDE_B (r0 takes SIDE_BOTH too:
+// the whole token range starts at row 0); a mask is any of the three, or 0.
+enum { SIDE_A = 1, SIDE_B = 2, SIDE_BOTH = 3 };
+struct Sides {
+    int P, La, Lb, rows_a, rows_b;           // pairs; rows per pair of each side; rows of each side (side B starts at row rows_a)
+    Sides() = default;
+    Sides(int P_, int La_, int Lb_) : P(P_), La(La_), Lb(Lb_), rows_a(P_ * La_), rows_b(P_ * Lb_) {}
+    int r0(int side) const { return side == SIDE_B ? rows_a : 0; }
+    int rows(int mask) const { return (mask & SIDE_A ? rows_a : 0) + (mask & SIDE_B ? rows_b : 0); }
+    int per_pair(int side) const { return side == SIDE_B ? Lb : La; }
+    int grp_first(int side) const { return side == SIDE_B ? P : 0; }        // first of the side's P groups in a [2 P] per-group array
+    // the side's part of a two-sided plane image whose side B starts `side_off` bytes in
+    template <class T> T* at(T* img, size_t side_off, int side) const { return img + (side == SIDE_B ? side_off : 0); }
+    template <class F> void for_sides(int mask, F&& fn) const { for (int side = SIDE_A; side <= SIDE_B; ++side) if (mask & side) fn(side); }
+    // the attention families: a side attends itself / side A attends side B / side B attends side A
+    Family self_a() const { return {0, La, 0, La}; }
+    Family self_b() const { return {rows_a, Lb, rows_a, Lb}; }
+    Family cross_a() const { return {0, La, rows_a, Lb}; }
+    Family cross_b() const { return {rows_a, Lb, 0, La}; }
+};
+
+// The layer schedule of both denoisers (pipeline.py:142, transformero.py:170-186; fusion_module.py:96-102): even layers are self layers on both
+// sides; odd layers are cross layers -- side A attends side B, then side B attends the UPDATED side A (quirk Q11).  Walks layers
+// [l_begin, n_layers) from the tokens in `cur`, writing buf0 and buf1 in turn, and leaves the last written buffer in `cur`.
+// call(l, xs, x_tok, ys, y_tok, out_tok, f1, f2) evaluates layer l: the rows of side(s) xs of x_tok attend those of side(s) ys of y_tok.
+template <class H, class B, class Call>
+static int layer_schedule(const Sides& S, int l_begin, int n_layers, H& cur, B buf0, B buf1, Call&& call) {
+    const Family self_a = S.self_a(), self_b = S.self_b(), cross_a = S.cross_a(), cross_b = S.cross_b();
+    B bufs[2] = {buf0, buf1};
+    for (int l = l_begin, which = 0; l < n_layers; ++l, which ^= 1) {
+        B nxt = bufs[which];
+        int rc;
+        if (l % 2 == 0) {
+            rc = call(l, SIDE_BOTH, cur, SIDE_BOTH, cur, nxt, self_a, &self_b);
+        } else {
+            rc = call(l, SIDE_A, cur, SIDE_B, cur, nxt, cross_a, nullptr);
+            if (rc == DR_OK) rc = call(l, SIDE_B, cur, SIDE_A, H(nxt), nxt, cross_b, nullptr);
+        }
+        if (rc) return rc;
+        cur = nxt;
+    }
+    return DR_OK;
+}
+
+// what a plane-path layer call needs besides its tokens (Pack / Ws: the loop's packed weights and plane buffers; the rotary tables and the
+// token mask stay null in the 2D-3D loop)
+template <class Pack, class Ws> struct PlaneCtx {
+    const Pack* pp; const Ws* pw; Sides S;
+    int C, H, attn_f16;                      // attn_f16: DR_LOOP_ATTN_F16
+    const float *cosT, *sinT; const uint8_t* tokmask;
+};
+// bound of the keys' source rows per group (pair x side) for the sides in `mask`: bnd [T] -> grp_x [2 P]
+static inline int side_group_max(const Sides& S, int mask, const float* bnd, float* grp_x, hipStream_t st) {
+    int rc = DR_OK;
+    S.for_sides(mask, [&](int side) { if (rc == DR_OK) rc = launch_group_max(bnd + S.r0(side), S.P, S.per_pair(side), grp_x + S.grp_first(side), st); });
+    return rc;
+}
+// the fp32 rows of one side of a token buffer -> that side's part of its plane image, row maxima as bounds
+static inline int side_planes_from_f32(const Sides& S, int side, const Tok& t, int C, size_t side_C, hipStream_t st) {
+    return launch_planes_from_f32(t.f32 + (size_t)S.r0(side) * C, C, S.rows(side), C, S.at(t.img, side_C, side), t.bnd + S.r0(side), st);
+}
+
+// ---- packed weights of the plane path --------------------------------------------------------------------------------------------------
+// room for one packed weight of nblk blocks x nct k-chunks (wide: in the wide-wave kernel's layout); viewed through *v where the carve is real
+static inline void take_weight(Carver& c, int C, int nblk, int nct, PgW* v, bool wide = false) {
+    char* p = c.take<char>(wide ? pgemm16w_weight_bytes(nblk, nct) : pgemm_weight_bytes(C, nblk, nct));
+    if (!v || !p) return;
+    if (wide) pgemm16w_weight_view(p, nblk, nct, v);
+    else pgemm_weight_view(p, C, nblk, nct, v);
+}
+// packs one block of a weight in the layout of its view
+static inline int pack_weight_block(const float* Wm, int Cc, int K, int plen, int ppad, const PgW& v, int nb, hipStream_t st, int olen = 0, int opad = 0) {
+    return v.sub == 2 ? pgemm16w_pack_weights_block(Wm, Cc, K, plen, ppad, v, nb, st, olen, opad)
+                      : pgemm_pack_weights_block(Wm, Cc, K, plen, ppad, v, nb, st, olen, opad);
+}
+// the views of a call's packed weights: the caller's buffer, or the workspace's own, packed now (Pack: Prepack / Prepack2)
+template <class Pack, class Cfg, class W>
+static int packed_or_own(const Cfg& cfg, const W& w, void* own_pack, Pack& pp, hipStream_t st) {
+    void* buf = const_cast<void*>(w.prepacked);
+    if (!buf) {
+        buf = own_pack;
+        const int rc = Pack::fill(buf, cfg, w, st);
+        if (rc) return rc;
+    }
+    Pack::carve(buf, cfg, &pp);
+    return DR_OK;
+}
+
 // blocks b0.. of a packed weight.  (The 2D-3D loop had a copy without the wide-wave branch: its weights are never packed in that layout,
 // PgW::sub == 0, where the two bodies are the same function.)
 static inline PgW pgw_blocks(const PgW& v, int b0, int C) {
