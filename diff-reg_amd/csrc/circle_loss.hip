@@ -227,11 +227,9 @@ CircleArgs circle_args(const dr_circle_loss_params* p) {
 // similarity, overlaps, logits, row / column statistics, loss and gradient coefficients
 int circle_forward(int M, int N, int C, const float* img, const float* pcd, int K, const int64_t* ii, const int64_t* jj, const float* omin,
                    const float* omax, const CircleArgs& a, float* loss, CircleWs& w, hipStream_t st) {
-    GemmBatch g;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], img, C, nullptr, 0, C, pcd, w.S, N, M, N, C, EPI_NONE, nullptr);
-    g.n = 1;
-    int rc = launch_gemm(g, st);
+    Gemms G;
+    G.add(img, C, pcd, w.S, N, M, N, C);
+    int rc = G.launch(st);
     if (rc) return rc;
     const size_t MN = (size_t)M * N;
     DR_HIP_CHECK(hipMemsetAsync(w.Omin, 0, MN * sizeof(float), st));
@@ -318,12 +316,10 @@ int dr_circle_loss_backward_f32(int M, int N, int C, const float* img, const flo
     hipLaunchKernelGGL(circle_grad_kernel, dim3((N4 + 31) / 32, (M4 + 31) / 32), dim3(256), 0, st, M, N, M4, N4, w.S, w.Omin, w.Omax, w.A, w.Bn, a,
                        w.la_r, w.lb_r, w.la_c, w.lb_c, w.cr, w.cc, grad_loss, w.G, w.GT);
     DR_LAUNCH_CHECK();
-    GemmBatch g;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], w.G, N4, nullptr, 0, N4, w.Tpcd, grad_img, C, M, C, N4, EPI_NONE, nullptr);    // G pcd
-    gemm_problem(g.p[1], w.GT, M4, nullptr, 0, M4, w.Timg, grad_pcd, C, N, C, M4, EPI_NONE, nullptr);   // G^T img
-    g.n = 2;
-    return launch_gemm(g, st);
+    Gemms G;
+    G.add(w.G, N4, w.Tpcd, grad_img, C, M, C, N4);      // G pcd
+    G.add(w.GT, M4, w.Timg, grad_pcd, C, N, C, M4);     // G^T img
+    return G.launch(st);
 }
 
 }  // extern "C"

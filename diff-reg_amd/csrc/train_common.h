@@ -1,6 +1,6 @@
 // train_common.h -- host helpers shared by the training entry points (train_layer.hip, train_fusion.hip, circle_loss.hip): a batched
 // transposition (the GEMM contracts along contiguous k: x W for a gradient w.r.t. the input and g^T x for a weight gradient need the transposed
-// operand), a two-operand add and a GemmProblem filler (the carving of caller memory into 256-byte aligned arrays: Carver of loop_common.h).
+// operand), a two-operand add and a builder of GEMM launches (the carving of caller memory into 256-byte aligned arrays: Carver of loop_common.h).
 #pragma once
 #include <string.h>
 #include "loop_common.h"
@@ -63,12 +63,35 @@ __global__ __launch_bounds__(256) void add2_kernel(long long n4, const float4* _
 
 inline int up4(int x) { return (x + 3) & ~3; }
 
-inline void gemm_problem(GemmProblem& p, const float* A, int lda, const float* A2, int lda2, int K1, const float* W, float* out, int ldo, int rows,
-                         int ncols, int K, int epi, const float* addend) {
-    memset(&p, 0, sizeof(p));
-    p.A = A; p.lda = lda; p.A2 = A2; p.lda2 = lda2; p.K1 = K1; p.W = W; p.out = out; p.ldo = ldo; p.rows = rows; p.ncols = ncols; p.K = K;
-    p.epi = epi; p.scale = 1.f; p.addend = addend;
-}
+// up to 4 GEMMs in one launch (launch_gemm): add() fills the next GemmProblem (everything zero but the operands named here and scale = 1) and
+// returns it -- the caller sets `bias` or the rotary tables on the reference
+struct Gemms {
+    GemmBatch g;
+    bool overflow;                                                        // an add() beyond the batch's 4 slots: launch() then fails (add() filled a spare problem)
+    GemmProblem spare;
+    static constexpr int CAP = (int)(sizeof(GemmBatch::p) / sizeof(GemmProblem));
+    Gemms() { memset(&g, 0, sizeof(g)); overflow = false; }
+    // out[rows, ncols] = epi([A | A2] W^T) + addend: A holds the first K1 of the K contraction entries of a row, A2 the others
+    GemmProblem& add(const float* A, int lda, const float* A2, int lda2, int K1, const float* W, float* out, int ldo, int rows, int ncols, int K,
+                     int epi = EPI_NONE, const float* addend = nullptr) {
+        if (g.n >= CAP) overflow = true;
+        GemmProblem& p = overflow ? spare : g.p[g.n++];
+        memset(&p, 0, sizeof(p));
+        p.A = A; p.lda = lda; p.A2 = A2; p.lda2 = lda2; p.K1 = K1; p.W = W; p.out = out; p.ldo = ldo; p.rows = rows; p.ncols = ncols; p.K = K;
+        p.epi = epi; p.scale = 1.f; p.addend = addend;
+        return p;
+    }
+    GemmProblem& add(const float* A, int lda, const float* W, float* out, int ldo, int rows, int ncols, int K, int epi = EPI_NONE,
+                     const float* addend = nullptr) {
+        return add(A, lda, nullptr, 0, K, W, out, ldo, rows, ncols, K, epi, addend);
+    }
+    int launch(hipStream_t st) {
+        if (overflow) return DR_EINVAL;
+        const int rc = launch_gemm(g, st);
+        memset(&g, 0, sizeof(g));
+        return rc;
+    }
+};
 
 }  // namespace
 }  // namespace dr

@@ -146,6 +146,33 @@ struct FSaved {
     }
 };
 
+// the backward's workspace (floats): activation gradients, the transposed weights ([Wk^T | Wv^T] side by side), the transposed activations and
+// gradients (token count padded to a multiple of 4: the GEMM's k extent), the column partials by blocks of FB_RB rows (LN2 and LN1: gamma, beta
+// and the preceding linear's bias, one after the other), the attention backward's own workspace
+struct FBwdWs {
+    float *g_f, *g_e, *g_z, *g_a, *g_o, *g_q, *g_k, *g_v;
+    float *TWs, *TWe, *TWl, *TWq, *TWkv;
+    float *T_e, *T_z, *T_o, *T_x, *T_y, *T_gf, *T_ge, *T_ga, *T_gq, *T_gk, *T_gv;
+    float *p_ln2, *p_exp, *p_ln1, *p_q, *p_k, *p_v;
+    float* att_ws;
+    size_t att_wsb;
+    static size_t carve(void* buf, FBwdWs& s, int B, int H, int L, int S, size_t C) {
+        const size_t R = (size_t)B * L, Q = (size_t)B * S, R4 = up4((int)R), Q4 = up4((int)Q), C2 = 2 * C, nR = nblk((int)R), nQ = nblk((int)Q);
+        Carver c(buf);
+        s.g_f = c.take<float>(R * C); s.g_e = c.take<float>(R * C2); s.g_z = c.take<float>(R * C); s.g_a = c.take<float>(R * C); s.g_o = c.take<float>(R * C);
+        s.g_q = c.take<float>(R * C); s.g_k = c.take<float>(Q * C); s.g_v = c.take<float>(Q * C);
+        s.TWs = c.take<float>(C2 * C); s.TWe = c.take<float>(C2 * C); s.TWl = c.take<float>(C * C); s.TWq = c.take<float>(C * C); s.TWkv = c.take<float>(C2 * C);
+        s.T_e = c.take<float>(C2 * R4); s.T_z = c.take<float>(C * R4); s.T_o = c.take<float>(C * R4); s.T_x = c.take<float>(C * R4); s.T_y = c.take<float>(C * Q4);
+        s.T_gf = c.take<float>(C * R4); s.T_ge = c.take<float>(C2 * R4); s.T_ga = c.take<float>(C * R4); s.T_gq = c.take<float>(C * R4);
+        s.T_gk = c.take<float>(C * Q4); s.T_gv = c.take<float>(C * Q4);
+        s.p_ln2 = c.take<float>(nR * C * 3); s.p_exp = c.take<float>(nR * C2); s.p_ln1 = c.take<float>(nR * C * 3); s.p_q = c.take<float>(nR * C);
+        s.p_k = c.take<float>(nQ * C); s.p_v = c.take<float>(nQ * C);
+        s.att_wsb = dr_attention_backward_workspace_bytes(B, H, L);
+        s.att_ws = c.take<float>(s.att_wsb / sizeof(float) + 64);
+        return c.off + 256;
+    }
+};
+
 bool fusion_args_ok(int C, int H, int B, int L, int S) {
     return B >= 1 && L >= 1 && S >= 1 && H >= 1 && C >= 4 && C <= 1024 && C % H == 0 && (C / H) % 4 == 0 && C / H <= 160 && C % 4 == 0;
 }
@@ -171,14 +198,11 @@ int dr_fusion_layer_train_forward_f32(const dr_fusion_layer_weights* w, int C, i
     const int R = B * L, Q = B * S, d = C / H, C2 = 2 * C;
     FSaved sv;
     FSaved::carve(saved, sv, R, Q, C);
-    GemmBatch g;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], x, C, nullptr, 0, C, w->q_w, sv.q, C, R, C, C, EPI_NONE, nullptr);
-    gemm_problem(g.p[1], y, C, nullptr, 0, C, w->k_w, sv.k, C, Q, C, C, EPI_NONE, nullptr);
-    gemm_problem(g.p[2], y, C, nullptr, 0, C, w->v_w, sv.v, C, Q, C, C, EPI_NONE, nullptr);
-    g.p[0].bias = w->q_b; g.p[1].bias = w->k_b; g.p[2].bias = w->v_b;
-    g.n = 3;
-    int rc = launch_gemm(g, st);
+    Gemms G;
+    G.add(x, C, w->q_w, sv.q, C, R, C, C).bias = w->q_b;
+    G.add(y, C, w->k_w, sv.k, C, Q, C, C).bias = w->k_b;
+    G.add(y, C, w->v_w, sv.v, C, Q, C, C).bias = w->v_b;
+    int rc = G.launch(st);
     if (rc) return rc;
     const uint8_t* qm = nullptr;
     if (y_mask) {
@@ -187,37 +211,20 @@ int dr_fusion_layer_train_forward_f32(const dr_fusion_layer_weights* w, int C, i
     }
     rc = dr_attention_f32(B, H, L, S, d, sv.q, sv.k, sv.v, C, qm, y_mask, 1.0f / sqrtf((float)d), sv.o, stream);
     if (rc) return rc;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], sv.o, C, nullptr, 0, C, w->lin_w, sv.a, C, R, C, C, EPI_NONE, x);                  // linear(o) + x
-    g.p[0].bias = w->lin_b;
-    g.n = 1;
-    if ((rc = launch_gemm(g, st))) return rc;
+    G.add(sv.o, C, w->lin_w, sv.a, C, R, C, C, EPI_NONE, x).bias = w->lin_b;                               // linear(o) + x
+    if ((rc = G.launch(st))) return rc;
     if ((rc = dr_layernorm_f32(R, C, sv.a, w->norm1_w, w->norm1_b, 1e-5f, sv.z, sv.st1, stream))) return rc;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], sv.z, C, nullptr, 0, C, w->expand_w, sv.e, C2, R, C2, C, EPI_RELU, nullptr);       // relu(expand(z))
-    g.p[0].bias = w->expand_b;
-    g.n = 1;
-    if ((rc = launch_gemm(g, st))) return rc;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], sv.e, C2, nullptr, 0, C2, w->squeeze_w, sv.f, C, R, C, C2, EPI_NONE, sv.z);        // squeeze(e) + z
-    g.p[0].bias = w->squeeze_b;
-    g.n = 1;
-    if ((rc = launch_gemm(g, st))) return rc;
+    G.add(sv.z, C, w->expand_w, sv.e, C2, R, C2, C, EPI_RELU).bias = w->expand_b;                          // relu(expand(z))
+    if ((rc = G.launch(st))) return rc;
+    G.add(sv.e, C2, w->squeeze_w, sv.f, C, R, C, C2, EPI_NONE, sv.z).bias = w->squeeze_b;                   // squeeze(e) + z
+    if ((rc = G.launch(st))) return rc;
     return dr_layernorm_f32(R, C, sv.f, w->norm2_w, w->norm2_b, 1e-5f, out, sv.st2, stream);
 }
 
 size_t dr_fusion_layer_backward_workspace_bytes(int B, int H, int L, int S, int C) {
     if (B < 1 || L < 1 || S < 1 || C < 4 || H < 1) return 0;
-    const size_t R = (size_t)B * L, Q = (size_t)B * S, R4 = up4((int)R), Q4 = up4((int)Q), C2 = 2 * (size_t)C;
-    const size_t nR = nblk((int)R), nQ = nblk((int)Q);
-    Carver c(nullptr);
-    c.take<float>(R * C); c.take<float>(R * C2); c.take<float>(R * C); c.take<float>(R * C); c.take<float>(R * C); c.take<float>(R * C); c.take<float>(Q * C); c.take<float>(Q * C);  // g_f .. g_v
-    c.take<float>(C2 * C); c.take<float>(C2 * C); c.take<float>((size_t)C * C); c.take<float>((size_t)C * C); c.take<float>(C2 * C);                          // transposed weights
-    c.take<float>(C2 * R4); c.take<float>(C * R4); c.take<float>(C * R4); c.take<float>(C * R4); c.take<float>(C * Q4);                                       // e^T z^T o^T x^T y^T
-    c.take<float>(C * R4); c.take<float>(C2 * R4); c.take<float>(C * R4); c.take<float>(C * R4); c.take<float>(C * Q4); c.take<float>(C * Q4);                       // gradients^T
-    c.take<float>(nR * C * 3); c.take<float>(nR * C2); c.take<float>(nR * C * 3); c.take<float>(nR * C); c.take<float>(nQ * C); c.take<float>(nQ * C);             // column partials
-    c.take<float>(dr_attention_backward_workspace_bytes(B, H, L) / sizeof(float) + 64);
-    return c.off + 256;
+    FBwdWs ws;
+    return FBwdWs::carve(nullptr, ws, B, H, L, S, C);
 }
 
 int dr_fusion_layer_backward_f32(const dr_fusion_layer_weights* w, int C, int H, int B, int L, int S, const float* x, const float* y,
@@ -229,88 +236,67 @@ int dr_fusion_layer_backward_f32(const dr_fusion_layer_weights* w, int C, int H,
     const int R = B * L, Q = B * S, d = C / H, R4 = up4(R), Q4 = up4(Q), C2 = 2 * C, nR = nblk(R), nQ = nblk(Q);
     FSaved sv;
     FSaved::carve(const_cast<void*>(saved), sv, R, Q, C);
-    Carver c(workspace);
-    float *g_f = c.take<float>((size_t)R * C), *g_e = c.take<float>((size_t)R * C2), *g_z = c.take<float>((size_t)R * C), *g_a = c.take<float>((size_t)R * C),
-          *g_o = c.take<float>((size_t)R * C), *g_q = c.take<float>((size_t)R * C), *g_k = c.take<float>((size_t)Q * C), *g_v = c.take<float>((size_t)Q * C);
-    float *TWs = c.take<float>((size_t)C2 * C), *TWe = c.take<float>((size_t)C2 * C), *TWl = c.take<float>((size_t)C * C), *TWq = c.take<float>((size_t)C * C),
-          *TWkv = c.take<float>((size_t)C2 * C);
-    float *T_e = c.take<float>((size_t)C2 * R4), *T_z = c.take<float>((size_t)C * R4), *T_o = c.take<float>((size_t)C * R4), *T_x = c.take<float>((size_t)C * R4),
-          *T_y = c.take<float>((size_t)C * Q4);
-    float *T_gf = c.take<float>((size_t)C * R4), *T_ge = c.take<float>((size_t)C2 * R4), *T_ga = c.take<float>((size_t)C * R4), *T_gq = c.take<float>((size_t)C * R4),
-          *T_gk = c.take<float>((size_t)C * Q4), *T_gv = c.take<float>((size_t)C * Q4);
-    float *p_ln2 = c.take<float>((size_t)nR * C * 3), *p_exp = c.take<float>((size_t)nR * C2), *p_ln1 = c.take<float>((size_t)nR * C * 3), *p_q = c.take<float>((size_t)nR * C),
-          *p_k = c.take<float>((size_t)nQ * C), *p_v = c.take<float>((size_t)nQ * C);
-    const size_t att_wsb = dr_attention_backward_workspace_bytes(B, H, L);
-    float* att_ws = c.take<float>(att_wsb / sizeof(float) + 64);
+    FBwdWs ws;
+    FBwdWs::carve(workspace, ws, B, H, L, S, C);
     const size_t pRC = (size_t)nR * C;
     int rc;
     // ---- everything that only needs the forward's tensors is transposed first, in one launch
     Transposer T;
-    T.add(w->squeeze_w, C, C2, C2, TWs, C);            // Ws [C, 2C] -> [2C, C]
-    T.add(w->expand_w, C2, C, C, TWe, C2);             // We [2C, C] -> [C, 2C]
-    T.add(w->lin_w, C, C, C, TWl, C);
-    T.add(w->q_w, C, C, C, TWq, C);
-    T.add(w->k_w, C, C, C, TWkv, C2, C);               // [Wk^T | Wv^T]: row j = (Wk[:, j], Wv[:, j])
-    T.add(w->v_w, C, C, C, TWkv + C, C2, C);
-    T.add(sv.e, R, C2, C2, T_e, R4);
-    T.add(sv.z, R, C, C, T_z, R4);
-    T.add(sv.o, R, C, C, T_o, R4);
-    T.add(x, R, C, C, T_x, R4);
-    if (y == x && Q == R) T_y = T_x;                   // a self-attention call: y^T is x^T
-    else T.add(y, Q, C, C, T_y, Q4);
+    T.add(w->squeeze_w, C, C2, C2, ws.TWs, C);         // Ws [C, 2C] -> [2C, C]
+    T.add(w->expand_w, C2, C, C, ws.TWe, C2);          // We [2C, C] -> [C, 2C]
+    T.add(w->lin_w, C, C, C, ws.TWl, C);
+    T.add(w->q_w, C, C, C, ws.TWq, C);
+    T.add(w->k_w, C, C, C, ws.TWkv, C2, C);            // [Wk^T | Wv^T]: row j = (Wk[:, j], Wv[:, j])
+    T.add(w->v_w, C, C, C, ws.TWkv + C, C2, C);
+    T.add(sv.e, R, C2, C2, ws.T_e, R4);
+    T.add(sv.z, R, C, C, ws.T_z, R4);
+    T.add(sv.o, R, C, C, ws.T_o, R4);
+    T.add(x, R, C, C, ws.T_x, R4);
+    if (y == x && Q == R) ws.T_y = ws.T_x;             // a self-attention call: y^T is x^T
+    else T.add(y, Q, C, C, ws.T_y, Q4);
     if ((rc = T.launch(st))) return rc;
     // ---- LN2 -> squeeze -> ReLU -> expand
-    if ((rc = launch_postln_bwd(R, C, sv.f, w->norm2_w, sv.st2, grad_out, nullptr, g_f, p_ln2, p_ln2 + pRC, p_ln2 + 2 * pRC, st))) return rc;
-    GemmBatch g;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], g_f, C, nullptr, 0, C, TWs, g_e, C2, R, C2, C, EPI_NONE, nullptr);                  // g_f Ws
-    g.n = 1;
-    if ((rc = launch_gemm(g, st))) return rc;
+    if ((rc = launch_postln_bwd(R, C, sv.f, w->norm2_w, sv.st2, grad_out, nullptr, ws.g_f, ws.p_ln2, ws.p_ln2 + pRC, ws.p_ln2 + 2 * pRC, st))) return rc;
+    Gemms G;
+    G.add(ws.g_f, C, ws.TWs, ws.g_e, C2, R, C2, C);                                        // g_f Ws
+    if ((rc = G.launch(st))) return rc;
     ColSums cs;
-    cs.add(g_e, R, C2, p_exp, sv.e, g_e);                                                                       // ReLU backward + expand's bias
+    cs.add(ws.g_e, R, C2, ws.p_exp, sv.e, ws.g_e);                                                              // ReLU backward + expand's bias
     if ((rc = cs.launch(st))) return rc;
-    T.add(g_f, R, C, C, T_gf, R4);
-    T.add(g_e, R, C2, C2, T_ge, R4);
+    T.add(ws.g_f, R, C, C, ws.T_gf, R4);
+    T.add(ws.g_e, R, C2, C2, ws.T_ge, R4);
     if ((rc = T.launch(st))) return rc;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], g_e, C2, nullptr, 0, C2, TWe, g_z, C, R, C, C2, EPI_NONE, nullptr);                 // g_e We
-    gemm_problem(g.p[1], T_gf, R4, nullptr, 0, R4, T_e, gw->squeeze_w, C2, C, C2, R4, EPI_NONE, nullptr);    // g_f^T e
-    gemm_problem(g.p[2], T_ge, R4, nullptr, 0, R4, T_z, gw->expand_w, C, C2, C, R4, EPI_NONE, nullptr);      // g_e^T z
-    g.n = 3;
-    if ((rc = launch_gemm(g, st))) return rc;
+    G.add(ws.g_e, C2, ws.TWe, ws.g_z, C, R, C, C2);                                        // g_e We
+    G.add(ws.T_gf, R4, ws.T_e, gw->squeeze_w, C2, C, C2, R4);                              // g_f^T e
+    G.add(ws.T_ge, R4, ws.T_z, gw->expand_w, C, C2, C, R4);                                // g_e^T z
+    if ((rc = G.launch(st))) return rc;
     // ---- LN1 (its upstream: the feed-forward branch + the residual g_f) -> linear
-    if ((rc = launch_postln_bwd(R, C, sv.a, w->norm1_w, sv.st1, g_z, g_f, g_a, p_ln1, p_ln1 + pRC, p_ln1 + 2 * pRC, st))) return rc;
-    T.add(g_a, R, C, C, T_ga, R4);
+    if ((rc = launch_postln_bwd(R, C, sv.a, w->norm1_w, sv.st1, ws.g_z, ws.g_f, ws.g_a, ws.p_ln1, ws.p_ln1 + pRC, ws.p_ln1 + 2 * pRC, st))) return rc;
+    T.add(ws.g_a, R, C, C, ws.T_ga, R4);
     if ((rc = T.launch(st))) return rc;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], g_a, C, nullptr, 0, C, TWl, g_o, C, R, C, C, EPI_NONE, nullptr);
-    gemm_problem(g.p[1], T_ga, R4, nullptr, 0, R4, T_o, gw->lin_w, C, C, C, R4, EPI_NONE, nullptr);
-    g.n = 2;
-    if ((rc = launch_gemm(g, st))) return rc;
+    G.add(ws.g_a, C, ws.TWl, ws.g_o, C, R, C, C);
+    G.add(ws.T_ga, R4, ws.T_o, gw->lin_w, C, C, C, R4);
+    if ((rc = G.launch(st))) return rc;
     // ---- attention -> q | k | v projections
     const uint8_t* qm = y_mask ? sv.ones : nullptr;
-    rc = dr_attention_backward_f32(B, H, L, S, d, sv.q, sv.k, sv.v, sv.o, g_o, C, qm, y_mask, 1.0f / sqrtf((float)d), g_q, g_k, g_v, att_ws, att_wsb,
-                                   stream);
+    rc = dr_attention_backward_f32(B, H, L, S, d, sv.q, sv.k, sv.v, sv.o, ws.g_o, C, qm, y_mask, 1.0f / sqrtf((float)d), ws.g_q, ws.g_k, ws.g_v, ws.att_ws,
+                                   ws.att_wsb, stream);
     if (rc) return rc;
-    cs.add(g_q, R, C, p_q);
-    cs.add(g_k, Q, C, p_k);
-    cs.add(g_v, Q, C, p_v);
+    cs.add(ws.g_q, R, C, ws.p_q);
+    cs.add(ws.g_k, Q, C, ws.p_k);
+    cs.add(ws.g_v, Q, C, ws.p_v);
     if ((rc = cs.launch(st))) return rc;
-    T.add(g_q, R, C, C, T_gq, R4);
-    T.add(g_k, Q, C, C, T_gk, Q4);
-    T.add(g_v, Q, C, C, T_gv, Q4);
+    T.add(ws.g_q, R, C, C, ws.T_gq, R4);
+    T.add(ws.g_k, Q, C, C, ws.T_gk, Q4);
+    T.add(ws.g_v, Q, C, C, ws.T_gv, Q4);
     if ((rc = T.launch(st))) return rc;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], g_q, C, nullptr, 0, C, TWq, grad_x, C, R, C, C, EPI_NONE, g_a);                      // g_q Wq + the residual
-    gemm_problem(g.p[1], g_k, C, g_v, C, C, TWkv, grad_y, C, Q, C, C2, EPI_NONE, nullptr);                    // g_k Wk + g_v Wv
-    gemm_problem(g.p[2], T_gq, R4, nullptr, 0, R4, T_x, gw->q_w, C, C, C, R4, EPI_NONE, nullptr);
-    gemm_problem(g.p[3], T_gk, Q4, nullptr, 0, Q4, T_y, gw->k_w, C, C, C, Q4, EPI_NONE, nullptr);
-    g.n = 4;
-    if ((rc = launch_gemm(g, st))) return rc;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], T_gv, Q4, nullptr, 0, Q4, T_y, gw->v_w, C, C, C, Q4, EPI_NONE, nullptr);
-    g.n = 1;
-    if ((rc = launch_gemm(g, st))) return rc;
+    G.add(ws.g_q, C, ws.TWq, grad_x, C, R, C, C, EPI_NONE, ws.g_a);                        // g_q Wq + the residual
+    G.add(ws.g_k, C, ws.g_v, C, C, ws.TWkv, grad_y, C, Q, C, C2);                          // g_k Wk + g_v Wv
+    G.add(ws.T_gq, R4, ws.T_x, gw->q_w, C, C, C, R4);
+    G.add(ws.T_gk, Q4, ws.T_y, gw->k_w, C, C, C, Q4);
+    if ((rc = G.launch(st))) return rc;
+    G.add(ws.T_gv, Q4, ws.T_y, gw->v_w, C, C, C, Q4);
+    if ((rc = G.launch(st))) return rc;
     // ---- the ten vector gradients from their partials
     FinBatch fb;
     memset(&fb, 0, sizeof(fb));
@@ -320,9 +306,9 @@ int dr_fusion_layer_backward_f32(const dr_fusion_layer_weights* w, int C, int H,
         t.part = part; t.out = out; t.nblk = nb; t.n = n; t.tile0 = tiles;
         tiles += (n + 255) / 256;
     };
-    fin(p_q, nR, C, gw->q_b); fin(p_k, nQ, C, gw->k_b); fin(p_v, nQ, C, gw->v_b);
-    fin(p_ln1 + 2 * pRC, nR, C, gw->lin_b); fin(p_ln1, nR, C, gw->norm1_w); fin(p_ln1 + pRC, nR, C, gw->norm1_b);
-    fin(p_exp, nR, C2, gw->expand_b); fin(p_ln2 + 2 * pRC, nR, C, gw->squeeze_b); fin(p_ln2, nR, C, gw->norm2_w); fin(p_ln2 + pRC, nR, C, gw->norm2_b);
+    fin(ws.p_q, nR, C, gw->q_b); fin(ws.p_k, nQ, C, gw->k_b); fin(ws.p_v, nQ, C, gw->v_b);
+    fin(ws.p_ln1 + 2 * pRC, nR, C, gw->lin_b); fin(ws.p_ln1, nR, C, gw->norm1_w); fin(ws.p_ln1 + pRC, nR, C, gw->norm1_b);
+    fin(ws.p_exp, nR, C2, gw->expand_b); fin(ws.p_ln2 + 2 * pRC, nR, C, gw->squeeze_b); fin(ws.p_ln2, nR, C, gw->norm2_w); fin(ws.p_ln2 + pRC, nR, C, gw->norm2_b);
     hipLaunchKernelGGL(colsum_final_kernel, dim3(tiles), dim3(256), 0, st, fb);
     DR_LAUNCH_CHECK();
     return DR_OK;

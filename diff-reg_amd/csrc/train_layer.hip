@@ -23,6 +23,31 @@ struct Saved {
     }
 };
 
+// the backward's workspace (floats): activation gradients, the transposed weights ([Wk^T | Wv^T] side by side), the transposed activations and
+// gradients (token count padded to a multiple of 4: the GEMM's k extent), the LayerNorm and attention backwards' own workspaces
+struct BwdWs {
+    float *g_fpre, *g_h, *g_x1, *g_m, *g_mpre, *g_o, *g_qw, *g_kw, *g_vw, *g_qpre, *g_kpre;
+    float *TW2, *TW0, *TWm, *TWq, *TWkv;
+    float *T_gf, *T_h, *T_gh, *T_cat, *T_gm, *T_o, *T_gq, *T_gk, *T_gv, *T_y;
+    float *ln_ws, *att_ws;
+    size_t att_wsb;
+    static size_t carve(void* buf, BwdWs& s, int B, int H, int L, int S, size_t C) {
+        const size_t R = (size_t)B * L, Q = (size_t)B * S, R4 = up4((int)R), Q4 = up4((int)Q), C2 = 2 * C;
+        Carver c(buf);
+        s.g_fpre = c.take<float>(R * C); s.g_h = c.take<float>(R * C2); s.g_x1 = c.take<float>(R * C); s.g_m = c.take<float>(R * C);
+        s.g_mpre = c.take<float>(R * C); s.g_o = c.take<float>(R * C);
+        s.g_qw = c.take<float>(R * C); s.g_kw = c.take<float>(Q * C); s.g_vw = c.take<float>(Q * C); s.g_qpre = c.take<float>(R * C); s.g_kpre = c.take<float>(Q * C);
+        s.TW2 = c.take<float>(C2 * C); s.TW0 = c.take<float>(C2 * C2); s.TWm = c.take<float>(C * C); s.TWq = c.take<float>(C * C); s.TWkv = c.take<float>(C * C2);
+        s.T_gf = c.take<float>(C * R4); s.T_h = c.take<float>(C2 * R4); s.T_gh = c.take<float>(C2 * R4); s.T_cat = c.take<float>(C2 * R4);
+        s.T_gm = c.take<float>(C * R4); s.T_o = c.take<float>(C * R4); s.T_gq = c.take<float>(C * R4);
+        s.T_gk = c.take<float>(C * Q4); s.T_gv = c.take<float>(C * Q4); s.T_y = c.take<float>(C * Q4);
+        s.ln_ws = c.take<float>(dr_layernorm_backward_workspace_bytes((int)C) / sizeof(float));
+        s.att_wsb = dr_attention_backward_workspace_bytes(B, H, L);
+        s.att_ws = c.take<float>(s.att_wsb / sizeof(float) + 64);
+        return c.off + 256;
+    }
+};
+
 }  // namespace
 }  // namespace dr
 
@@ -46,35 +71,27 @@ int dr_attention_layer_train_forward_f32(const dr_layer_weights* w, int C, int H
     const int R = B * L, Q = B * S, d = C / H;
     Saved sv;
     Saved::carve(saved, sv, R, Q, C);
-    GemmBatch g;
-    memset(&g, 0, sizeof(g));
+    Gemms G;
     // q | k | v: one launch; the rotary code in the GEMM's epilogue (transformero.py:61-70)
-    gemm_problem(g.p[0], x, C, nullptr, 0, C, w->q_proj, sv.qw, C, R, C, C, EPI_ROTARY, nullptr);
-    g.p[0].cosT = cos_x; g.p[0].sinT = sin_x; g.p[0].rot_C = C;
-    gemm_problem(g.p[1], y, C, nullptr, 0, C, w->k_proj, sv.kw, C, Q, C, C, EPI_ROTARY, nullptr);
-    g.p[1].cosT = cos_y; g.p[1].sinT = sin_y; g.p[1].rot_C = C;
-    gemm_problem(g.p[2], y, C, nullptr, 0, C, w->v_proj, sv.vw, C, Q, C, C, EPI_NONE, nullptr);
-    g.n = 3;
-    int rc = launch_gemm(g, st);
+    GemmProblem& pq = G.add(x, C, w->q_proj, sv.qw, C, R, C, C, EPI_ROTARY);
+    pq.cosT = cos_x; pq.sinT = sin_x; pq.rot_C = C;
+    GemmProblem& pk = G.add(y, C, w->k_proj, sv.kw, C, Q, C, C, EPI_ROTARY);
+    pk.cosT = cos_y; pk.sinT = sin_y; pk.rot_C = C;
+    G.add(y, C, w->v_proj, sv.vw, C, Q, C, C);
+    int rc = G.launch(st);
     if (rc) return rc;
     rc = dr_attention_f32(B, H, L, S, d, sv.qw, sv.kw, sv.vw, C, x_mask, y_mask, 1.0f / sqrtf((float)d), sv.o, stream);
     if (rc) return rc;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], sv.o, C, nullptr, 0, C, w->merge, sv.m_pre, C, R, C, C, EPI_NONE, nullptr);
-    g.n = 1;
-    rc = launch_gemm(g, st);
+    G.add(sv.o, C, w->merge, sv.m_pre, C, R, C, C);
+    rc = G.launch(st);
     if (rc) return rc;
     rc = dr_layernorm_f32(R, C, sv.m_pre, w->norm1_w, w->norm1_b, 1e-5f, sv.m, sv.st1, stream);
     if (rc) return rc;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], x, C, sv.m, C, C, w->mlp0, sv.h, 2 * C, R, 2 * C, 2 * C, EPI_RELU, nullptr);      // mlp.0(cat[x, message]) + ReLU
-    g.n = 1;
-    rc = launch_gemm(g, st);
+    G.add(x, C, sv.m, C, C, w->mlp0, sv.h, 2 * C, R, 2 * C, 2 * C, EPI_RELU);      // mlp.0(cat[x, message]) + ReLU
+    rc = G.launch(st);
     if (rc) return rc;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], sv.h, 2 * C, nullptr, 0, 2 * C, w->mlp2, sv.f_pre, C, R, C, 2 * C, EPI_NONE, nullptr);
-    g.n = 1;
-    rc = launch_gemm(g, st);
+    G.add(sv.h, 2 * C, w->mlp2, sv.f_pre, C, R, C, 2 * C);
+    rc = G.launch(st);
     if (rc) return rc;
     // out = x + norm2(.)  (norm2's output is not needed again: it lands in `out` and the residual is added in place)
     rc = dr_layernorm_f32(R, C, sv.f_pre, w->norm2_w, w->norm2_b, 1e-5f, out, sv.st2, stream);
@@ -87,16 +104,8 @@ int dr_attention_layer_train_forward_f32(const dr_layer_weights* w, int C, int H
 
 size_t dr_attention_layer_backward_workspace_bytes(int B, int H, int L, int S, int C) {
     if (B < 1 || L < 1 || S < 1 || C < 4 || H < 1) return 0;
-    const size_t R = (size_t)B * L, Q = (size_t)B * S, R4 = up4((int)R), Q4 = up4((int)Q);
-    Carver c(nullptr);
-    c.take<float>(R * C); c.take<float>(R * 2 * C); c.take<float>(R * C); c.take<float>(R * C); c.take<float>(R * C); c.take<float>(R * C);   // g_fpre, g_h, g_x1, g_m, g_mpre, g_o
-    c.take<float>(R * C); c.take<float>(Q * C); c.take<float>(Q * C); c.take<float>(R * C); c.take<float>(Q * C);                      // g_qw, g_kw, g_vw, g_qpre, g_kpre
-    c.take<float>((size_t)2 * C * C); c.take<float>((size_t)4 * C * C); c.take<float>((size_t)C * C); c.take<float>((size_t)C * C); c.take<float>((size_t)2 * C * C);   // W2^T, W0^T, Wm^T, Wq^T, [Wk^T | Wv^T]
-    c.take<float>(C * R4); c.take<float>(2 * C * R4); c.take<float>(2 * C * R4); c.take<float>(2 * C * R4); c.take<float>(C * R4); c.take<float>(C * R4); c.take<float>(C * R4);   // transposed activations
-    c.take<float>(C * Q4); c.take<float>(C * Q4); c.take<float>(C * Q4);
-    c.take<float>(dr_layernorm_backward_workspace_bytes(C) / sizeof(float));
-    c.take<float>(dr_attention_backward_workspace_bytes(B, H, L) / sizeof(float) + 64);
-    return c.off + 256;
+    BwdWs ws;
+    return BwdWs::carve(nullptr, ws, B, H, L, S, C);
 }
 
 int dr_attention_layer_backward_f32(const dr_layer_weights* w, int C, int H, int B, int L, int S, const float* x, const float* y,
@@ -112,98 +121,77 @@ int dr_attention_layer_backward_f32(const dr_layer_weights* w, int C, int H, int
     const int R = B * L, Q = B * S, d = C / H, R4 = up4(R), Q4 = up4(Q), C2 = 2 * C;
     Saved sv;
     Saved::carve(const_cast<void*>(saved), sv, R, Q, C);
-    Carver c(workspace);
-    float *g_fpre = c.take<float>((size_t)R * C), *g_h = c.take<float>((size_t)R * C2), *g_x1 = c.take<float>((size_t)R * C), *g_m = c.take<float>((size_t)R * C),
-          *g_mpre = c.take<float>((size_t)R * C), *g_o = c.take<float>((size_t)R * C);
-    float *g_qw = c.take<float>((size_t)R * C), *g_kw = c.take<float>((size_t)Q * C), *g_vw = c.take<float>((size_t)Q * C), *g_qpre = c.take<float>((size_t)R * C),
-          *g_kpre = c.take<float>((size_t)Q * C);
-    float *TW2 = c.take<float>((size_t)C2 * C), *TW0 = c.take<float>((size_t)C2 * C2), *TWm = c.take<float>((size_t)C * C), *TWq = c.take<float>((size_t)C * C),
-          *TWkv = c.take<float>((size_t)C * C2);
-    float *T_gf = c.take<float>((size_t)C * R4), *T_h = c.take<float>((size_t)C2 * R4), *T_gh = c.take<float>((size_t)C2 * R4), *T_cat = c.take<float>((size_t)C2 * R4),
-          *T_gm = c.take<float>((size_t)C * R4), *T_o = c.take<float>((size_t)C * R4), *T_gq = c.take<float>((size_t)C * R4);
-    float *T_gk = c.take<float>((size_t)C * Q4), *T_gv = c.take<float>((size_t)C * Q4), *T_y = c.take<float>((size_t)C * Q4);
-    float* ln_ws = c.take<float>(dr_layernorm_backward_workspace_bytes(C) / sizeof(float));
-    const size_t att_wsb = dr_attention_backward_workspace_bytes(B, H, L);
-    float* att_ws = c.take<float>(att_wsb / sizeof(float) + 64);
+    BwdWs ws;
+    BwdWs::carve(workspace, ws, B, H, L, S, C);
     int rc;
     // ---- everything that only needs the forward's tensors is transposed first, in one launch
     Transposer T;
-    T.add(w->mlp2, C, C2, C2, TW2, C);                 // W2 [C, 2C]  -> [2C, C]
-    T.add(w->mlp0, C2, C2, C2, TW0, C2);               // W0 [2C, 2C] -> its transpose
-    T.add(w->merge, C, C, C, TWm, C);
-    T.add(w->q_proj, C, C, C, TWq, C);
-    T.add(w->k_proj, C, C, C, TWkv, C2, C);            // [Wk^T | Wv^T]: row j = (Wk[:, j], Wv[:, j])
-    T.add(w->v_proj, C, C, C, TWkv + C, C2, C);
-    T.add(sv.h, R, C2, C2, T_h, R4);
-    T.add(x, R, C, C, T_cat, R4);                      // cat[x, m]^T = [x^T ; m^T]
-    T.add(sv.m, R, C, C, T_cat + (size_t)C * R4, R4);
-    T.add(sv.o, R, C, C, T_o, R4);
+    T.add(w->mlp2, C, C2, C2, ws.TW2, C);              // W2 [C, 2C]  -> [2C, C]
+    T.add(w->mlp0, C2, C2, C2, ws.TW0, C2);            // W0 [2C, 2C] -> its transpose
+    T.add(w->merge, C, C, C, ws.TWm, C);
+    T.add(w->q_proj, C, C, C, ws.TWq, C);
+    T.add(w->k_proj, C, C, C, ws.TWkv, C2, C);         // [Wk^T | Wv^T]: row j = (Wk[:, j], Wv[:, j])
+    T.add(w->v_proj, C, C, C, ws.TWkv + C, C2, C);
+    T.add(sv.h, R, C2, C2, ws.T_h, R4);
+    T.add(x, R, C, C, ws.T_cat, R4);                   // cat[x, m]^T = [x^T ; m^T]
+    T.add(sv.m, R, C, C, ws.T_cat + (size_t)C * R4, R4);
+    T.add(sv.o, R, C, C, ws.T_o, R4);
     // self-attention calls (y is x): y^T is x^T, already the first C rows of cat^T
     const bool y_is_x = y == x && Q == R;
-    if (y_is_x) T_y = T_cat;
-    else T.add(y, Q, C, C, T_y, Q4);
+    if (y_is_x) ws.T_y = ws.T_cat;
+    else T.add(y, Q, C, C, ws.T_y, Q4);
     rc = T.launch(st);
     if (rc) return rc;
     // ---- norm2 -> mlp.2 -> ReLU -> mlp.0
-    rc = dr_layernorm_backward_f32(R, C, sv.f_pre, w->norm2_w, sv.st2, grad_out, g_fpre, gw->norm2_w, gw->norm2_b, ln_ws, stream);
+    rc = dr_layernorm_backward_f32(R, C, sv.f_pre, w->norm2_w, sv.st2, grad_out, ws.g_fpre, gw->norm2_w, gw->norm2_b, ws.ln_ws, stream);
     if (rc) return rc;
-    GemmBatch g;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], g_fpre, C, nullptr, 0, C, TW2, g_h, C2, R, C2, C, EPI_NONE, nullptr);                 // g W2
-    g.n = 1;
-    rc = launch_gemm(g, st);
+    Gemms G;
+    G.add(ws.g_fpre, C, ws.TW2, ws.g_h, C2, R, C2, C);                                     // g W2
+    rc = G.launch(st);
     if (rc) return rc;
-    rc = dr_relu_backward_f32((long long)R * C2, sv.h, g_h, g_h, stream);
+    rc = dr_relu_backward_f32((long long)R * C2, sv.h, ws.g_h, ws.g_h, stream);
     if (rc) return rc;
-    T.add(g_fpre, R, C, C, T_gf, R4);
-    T.add(g_h, R, C2, C2, T_gh, R4);
+    T.add(ws.g_fpre, R, C, C, ws.T_gf, R4);
+    T.add(ws.g_h, R, C2, C2, ws.T_gh, R4);
     rc = T.launch(st);
     if (rc) return rc;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], g_h, C2, nullptr, 0, C2, TW0, g_x1, C, R, C, C2, EPI_NONE, grad_out);                  // grad_out + (g_h W0)[:, :C]   (the residual + cat's x half)
-    gemm_problem(g.p[1], g_h, C2, nullptr, 0, C2, TW0 + (size_t)C * C2, g_m, C, R, C, C2, EPI_NONE, nullptr);  // (g_h W0)[:, C:]  -> norm1's output
-    gemm_problem(g.p[2], T_gf, R4, nullptr, 0, R4, T_h, gw->mlp2, C2, C, C2, R4, EPI_NONE, nullptr);           // g^T h
-    gemm_problem(g.p[3], T_gh, R4, nullptr, 0, R4, T_cat, gw->mlp0, C2, C2, C2, R4, EPI_NONE, nullptr);        // g_h^T cat[x, m]
-    g.n = 4;
-    rc = launch_gemm(g, st);
+    G.add(ws.g_h, C2, ws.TW0, ws.g_x1, C, R, C, C2, EPI_NONE, grad_out);                   // grad_out + (g_h W0)[:, :C]   (the residual + cat's x half)
+    G.add(ws.g_h, C2, ws.TW0 + (size_t)C * C2, ws.g_m, C, R, C, C2);                       // (g_h W0)[:, C:]  -> norm1's output
+    G.add(ws.T_gf, R4, ws.T_h, gw->mlp2, C2, C, C2, R4);                                      // g^T h
+    G.add(ws.T_gh, R4, ws.T_cat, gw->mlp0, C2, C2, C2, R4);                                   // g_h^T cat[x, m]
+    rc = G.launch(st);
     if (rc) return rc;
     // ---- norm1 -> merge
-    rc = dr_layernorm_backward_f32(R, C, sv.m_pre, w->norm1_w, sv.st1, g_m, g_mpre, gw->norm1_w, gw->norm1_b, ln_ws, stream);
+    rc = dr_layernorm_backward_f32(R, C, sv.m_pre, w->norm1_w, sv.st1, ws.g_m, ws.g_mpre, gw->norm1_w, gw->norm1_b, ws.ln_ws, stream);
     if (rc) return rc;
-    T.add(g_mpre, R, C, C, T_gm, R4);
+    T.add(ws.g_mpre, R, C, C, ws.T_gm, R4);
     rc = T.launch(st);
     if (rc) return rc;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], g_mpre, C, nullptr, 0, C, TWm, g_o, C, R, C, C, EPI_NONE, nullptr);
-    gemm_problem(g.p[1], T_gm, R4, nullptr, 0, R4, T_o, gw->merge, C, C, C, R4, EPI_NONE, nullptr);
-    g.n = 2;
-    rc = launch_gemm(g, st);
+    G.add(ws.g_mpre, C, ws.TWm, ws.g_o, C, R, C, C);
+    G.add(ws.T_gm, R4, ws.T_o, gw->merge, C, C, C, R4);
+    rc = G.launch(st);
     if (rc) return rc;
     // ---- attention, rotary code, projections
-    rc = dr_attention_backward_f32(B, H, L, S, d, sv.qw, sv.kw, sv.vw, sv.o, g_o, C, x_mask, y_mask, 1.0f / sqrtf((float)d), g_qw, g_kw, g_vw, att_ws,
-                                   att_wsb, stream);
+    rc = dr_attention_backward_f32(B, H, L, S, d, sv.qw, sv.kw, sv.vw, sv.o, ws.g_o, C, x_mask, y_mask, 1.0f / sqrtf((float)d), ws.g_qw, ws.g_kw, ws.g_vw,
+                                   ws.att_ws, ws.att_wsb, stream);
     if (rc) return rc;
-    rc = dr_rotary_f32(R, C, g_qw, cos_x, sin_x, 1, 1.f, g_qpre, stream);
+    rc = dr_rotary_f32(R, C, ws.g_qw, cos_x, sin_x, 1, 1.f, ws.g_qpre, stream);
     if (rc) return rc;
-    rc = dr_rotary_f32(Q, C, g_kw, cos_y, sin_y, 1, 1.f, g_kpre, stream);
+    rc = dr_rotary_f32(Q, C, ws.g_kw, cos_y, sin_y, 1, 1.f, ws.g_kpre, stream);
     if (rc) return rc;
-    T.add(g_qpre, R, C, C, T_gq, R4);
-    T.add(g_kpre, Q, C, C, T_gk, Q4);
-    T.add(g_vw, Q, C, C, T_gv, Q4);
+    T.add(ws.g_qpre, R, C, C, ws.T_gq, R4);
+    T.add(ws.g_kpre, Q, C, C, ws.T_gk, Q4);
+    T.add(ws.g_vw, Q, C, C, ws.T_gv, Q4);
     rc = T.launch(st);
     if (rc) return rc;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], g_qpre, C, nullptr, 0, C, TWq, grad_x, C, R, C, C, EPI_NONE, g_x1);                    // + the residual / mlp part
-    gemm_problem(g.p[1], g_kpre, C, g_vw, C, C, TWkv, grad_y, C, Q, C, C2, EPI_NONE, nullptr);                  // g_k Wk + g_v Wv
-    g.n = 2;
-    rc = launch_gemm(g, st);
+    G.add(ws.g_qpre, C, ws.TWq, grad_x, C, R, C, C, EPI_NONE, ws.g_x1);                    // + the residual / mlp part
+    G.add(ws.g_kpre, C, ws.g_vw, C, C, ws.TWkv, grad_y, C, Q, C, C2);                      // g_k Wk + g_v Wv
+    rc = G.launch(st);
     if (rc) return rc;
-    memset(&g, 0, sizeof(g));
-    gemm_problem(g.p[0], T_gq, R4, nullptr, 0, R4, T_cat, gw->q_proj, C, C, C, R4, EPI_NONE, nullptr);          // g_q^T x   (x^T = the first C rows of cat^T)
-    gemm_problem(g.p[1], T_gk, Q4, nullptr, 0, Q4, T_y, gw->k_proj, C, C, C, Q4, EPI_NONE, nullptr);
-    gemm_problem(g.p[2], T_gv, Q4, nullptr, 0, Q4, T_y, gw->v_proj, C, C, C, Q4, EPI_NONE, nullptr);
-    g.n = 3;
-    return launch_gemm(g, st);
+    G.add(ws.T_gq, R4, ws.T_cat, gw->q_proj, C, C, C, R4);                                    // g_q^T x   (x^T = the first C rows of cat^T)
+    G.add(ws.T_gk, Q4, ws.T_y, gw->k_proj, C, C, C, Q4);
+    G.add(ws.T_gv, Q4, ws.T_y, gw->v_proj, C, C, C, Q4);
+    return G.launch(st);
 }
 
 }  // extern "C"

@@ -48,52 +48,6 @@ class _FocalLoss(torch.autograd.Function):
         return lib.focal_loss_backward(conf, conf_gt, *ctx.hp) * grad_loss, None, None, None, None, None, None
 
 
-class _MatchingHead(torch.autograd.Function):
-    """Matching.forward, sinkhorn branch, disentangled rotary code (3D/models/matching.py:164-216): src_proj on both sides (quirk Q1), rotary,
-    / sqrt(C), similarity, mask, Sinkhorn read-out.  Backward: dr_sinkhorn_backward_f32, then the similarity / rotary / projection transposes
-    on the library's GEMM (dr_linear_f32) and dr_rotary_f32."""
-
-    @staticmethod
-    def forward(ctx, src_feats, tgt_feats, weight, bin_score, cs, ss, ct, st, src_mask, tgt_mask, iters):
-        B, N, C = src_feats.shape
-        M = tgt_feats.shape[1]
-        sf, tf, W = src_feats.detach().float().contiguous(), tgt_feats.detach().float().contiguous(), weight.detach().float().contiguous()
-        cs, ss, ct, st = (t_.detach().float().contiguous() for t_ in (cs, ss, ct, st))
-        spre, tpre = lib.linear(sf.reshape(B * N, C), W), lib.linear(tf.reshape(B * M, C), W)
-        a = lib.rotary(spre, cs, ss, scale=1.0 / C ** 0.5).view(B, N, C)
-        b = lib.rotary(tpre, ct, st, scale=1.0 / C ** 0.5).view(B, M, C)
-        sim = lib.bmm_nt(a, b)
-        if src_mask is not None:
-            sim = sim.masked_fill(~(src_mask[:, :, None] & tgt_mask[:, None, :]), float("-inf"))
-        conf = lib.sinkhorn(sim, bin_score.detach().float().reshape(1), iters, src_mask, tgt_mask)
-        ctx.save_for_backward(sf, tf, W, a, b, sim, bin_score.detach(), cs, ss, ct, st, spre, tpre)
-        ctx.iters, ctx.masks = iters, (src_mask, tgt_mask)
-        return conf
-
-    @staticmethod
-    def backward(ctx, grad_conf):
-        sf, tf, W, a, b, sim, bin_score, cs, ss, ct, st, spre, tpre = ctx.saved_tensors
-        sm, tm = ctx.masks
-        B, N, C = sf.shape
-        M = tf.shape[1]
-        if sm is None:
-            sm = torch.ones(B, N, dtype=torch.bool, device=sf.device)
-            tm = torch.ones(B, M, dtype=torch.bool, device=sf.device)
-        gs, ga = lib.sinkhorn_backward(sim, bin_score, ctx.iters, sm, tm, grad_conf)                  # d loss / d sim  [B,N,M]
-        tr = lambda x: x.transpose(-1, -2).contiguous()
-        g_a = lib.bmm_nt(gs, tr(b))                                                                   # gs b    [B,N,C]
-        g_b = lib.bmm_nt(tr(gs), tr(a))                                                               # gs^T a  [B,M,C]
-        g_sp = lib.rotary(g_a.reshape(B * N, C), cs, ss, inverse=True, scale=1.0 / C ** 0.5)          # back through / sqrt(C) and the rotary code
-        g_tp = lib.rotary(g_b.reshape(B * M, C), ct, st, inverse=True, scale=1.0 / C ** 0.5)
-        Wt = tr(W)
-        g_src = lib.linear(g_sp, Wt).view(B, N, C)                                                     # g W
-        g_tgt = lib.linear(g_tp, Wt).view(B, M, C)
-        pad4 = lambda x: torch.nn.functional.pad(x, (0, (-x.shape[1]) % 4))                            # (the GEMM wants K % 4 == 0)
-        g_W = lib.linear(pad4(tr(g_sp)), pad4(tr(sf.reshape(B * N, C)))) + lib.linear(pad4(tr(g_tp)), pad4(tr(tf.reshape(B * M, C))))   # g^T x, both sides
-        gcs = gss = gct = gst = None        # (position codes: constants, as in the reference)
-        return g_src, g_tgt, g_W, ga.reshape(bin_score.shape).to(bin_score.dtype), gcs, gss, gct, gst, None, None, None
-
-
 class _ScatterRows(torch.autograd.Function):
     """dst[dst_index[i]] = src[src_index[i]] into a zero tensor of n_dst rows (Pipeline.split_feats, 3D/models/pipeline.py:350-379); backward: the
     same kernel with the index lists swapped (the lists are injective: every destination row has one source)"""
@@ -144,81 +98,33 @@ class _GeometryAttentionLayer(torch.autograd.Function):
     """GeometryAttentionLayer.forward (3D/models/transformero.py:43-96, rotary code) and its backward: the attention itself is FUSED both ways
     (forward = the inference kernels, dr_attention_f32; backward = dr_attention_backward_f32, flash-style: per-query log-sum-exp + delta, then dQ by
     query blocks and dK | dV by key blocks on the f32-input MFMA -- no [B,H,L,S] matrix exists in either direction); LayerNorm / ReLU / rotary
-    backward kernels (csrc/train.hip); every projection and its weight gradient on dr_linear_f32."""
+    backward kernels (csrc/train.hip); every projection and its weight gradient on the library's GEMM."""
 
     #: True (default): forward and backward are ONE library call each (dr_attention_layer_train_forward_f32 / dr_attention_layer_backward_f32:
     #: the same kernels launched from C++ -- a step is ~1 900 launches, and driving them from Python cost more host time than the kernels run).
-    #: False: the per-op form below (one library call per kernel), kept as the readable statement of the backward and for A/B tests.
+    #: False: geometry_attention_layer takes the per-op form instead (_GeometryAttentionLayerG: one library call per kernel), for A/B tests.
     fused = True
 
     @staticmethod
     def forward(ctx, x, source, cx, sx, cy, sy, x_mask, source_mask, H, Wq, Wk, Wv, Wm, W0, W2, g1, b1, g2, b2):
-        B, L, C = x.shape
-        S = source.shape[1]
-        d = C // H
+        C = x.shape[2]
         det = lambda t: t.detach().float().contiguous()
-        if _GeometryAttentionLayer.fused:
-            x3, s3 = det(x), det(source)
-            wts = [det(t) for t in (Wq, Wk, Wv, Wm, W0, W2, g1, b1, g2, b2)]
-            tabs = [det(t) for t in (cx, sx, cy, sy)]
-            out, saved = lib.attention_layer_train_forward(wts, C, H, x3, s3, *tabs, x_mask, source_mask)
-            ctx.save_for_backward(x3, s3, saved, *tabs, *wts)
-            ctx.dims = (B, L, S, C, H, d, 1.0 / d ** 0.5)
-            ctx.masks = (x_mask, source_mask)
-            ctx.is_fused = True
-            return out
-        ctx.is_fused = False
-        x2, s2 = det(x).reshape(B * L, C), det(source).reshape(B * S, C)
-        Wq, Wk, Wv, Wm, W0, W2, g1, b1, g2, b2 = map(det, (Wq, Wk, Wv, Wm, W0, W2, g1, b1, g2, b2))
-        cx, sx, cy, sy = map(det, (cx, sx, cy, sy))
-        qpre, kpre = lib.linear(x2, Wq), lib.linear(s2, Wk)
-        qw, kw = lib.rotary(qpre, cx, sx), lib.rotary(kpre, cy, sy)
-        vw = lib.linear(s2, Wv)
-        # fused attention in the token layout (head h in columns h d ..): no [B,H,L,S] matrix, no head permutes
-        o2 = lib.attention(qw.view(B, L, C), kw.view(B, S, C), vw.view(B, S, C), H, x_mask, source_mask).view(B * L, C)
-        scale = 1.0 / d ** 0.5
-        m_pre = lib.linear(o2, Wm)
-        m, st1 = lib.layernorm(m_pre, g1, b1)
-        cat = torch.cat([x2, m], 1)
-        h = lib.linear(cat, W0, epilogue=1)
-        f_pre = lib.linear(h, W2)
-        f, st2 = lib.layernorm(f_pre, g2, b2)
-        ctx.save_for_backward(x2, s2, cx, sx, cy, sy, Wq, Wk, Wv, Wm, W0, W2, g1, g2, qw, kw, vw, o2, m_pre, st1, cat, h, f_pre, st2)
-        ctx.dims = (B, L, S, C, H, d, scale)
+        x3, s3 = det(x), det(source)
+        wts = [det(t) for t in (Wq, Wk, Wv, Wm, W0, W2, g1, b1, g2, b2)]
+        tabs = [det(t) for t in (cx, sx, cy, sy)]
+        out, saved = lib.attention_layer_train_forward(wts, C, H, x3, s3, *tabs, x_mask, source_mask)
+        ctx.save_for_backward(x3, s3, saved, *tabs, *wts)
+        ctx.dims = (C, H)
         ctx.masks = (x_mask, source_mask)
-        return (x2 + f).view(B, L, C)
+        return out
 
     @staticmethod
     def backward(ctx, ge):
-        if ctx.is_fused:
-            x3, s3, saved, cx, sx, cy, sy, *wts = ctx.saved_tensors
-            B, L, S, C, H, d, scale = ctx.dims
-            xm, sm_ = ctx.masks
-            gx, gs, gw = lib.attention_layer_backward(wts, C, H, x3, s3, cx, sx, cy, sy, xm, sm_, saved, ge.contiguous().float())
-            return (gx, gs, None, None, None, None, None, None, None, *gw)
-        (x2, s2, cx, sx, cy, sy, Wq, Wk, Wv, Wm, W0, W2, g1, g2, qw, kw, vw, o2, m_pre, st1, cat, h, f_pre, st2) = ctx.saved_tensors
-        B, L, S, C, H, d, scale = ctx.dims
-        tr = lambda t: t.transpose(-1, -2).contiguous()
-        ge = ge.contiguous().float().reshape(B * L, C)
-        g_fpre, gg2, gb2 = lib.layernorm_backward(f_pre, g2, st2, ge)
-        g_h = lib.relu_backward(h, _mm(g_fpre, tr(W2)))
-        gW2 = _mm(tr(g_fpre), tr(h))
-        g_cat = _mm(g_h, tr(W0))
-        gW0 = _mm(tr(g_h), tr(cat))
-        g_x = ge + g_cat[:, :C]
-        g_mpre, gg1, gb1 = lib.layernorm_backward(m_pre, g1, st1, g_cat[:, C:].contiguous())
-        g_o2 = _mm(g_mpre, tr(Wm))
-        gWm = _mm(tr(g_mpre), tr(o2))
+        x3, s3, saved, cx, sx, cy, sy, *wts = ctx.saved_tensors
+        C, H = ctx.dims
         xm, sm_ = ctx.masks
-        g_qw, g_kw, g_vw = lib.attention_backward(qw.view(B, L, C), kw.view(B, S, C), vw.view(B, S, C), o2.view(B, L, C), g_o2.view(B, L, C), H, xm, sm_)
-        g_qw, g_kw, g_vw = g_qw.view(B * L, C), g_kw.view(B * S, C), g_vw.view(B * S, C)
-        g_qpre = lib.rotary(g_qw, cx, sx, inverse=True)
-        g_kpre = lib.rotary(g_kw, cy, sy, inverse=True)
-        gcx = gsx = gcy = gsy = None        # (position codes are constants of the graph: the reference detaches them, position_encoding.py:83-84)
-        g_x = g_x + _mm(g_qpre, tr(Wq))
-        g_s = _mm(g_kpre, tr(Wk)) + _mm(g_vw, tr(Wv))
-        gWq, gWk, gWv = _mm(tr(g_qpre), tr(x2)), _mm(tr(g_kpre), tr(s2)), _mm(tr(g_vw), tr(s2))
-        return (g_x.view(B, L, C), g_s.view(B, S, C), gcx, gsx, gcy, gsy, None, None, None, gWq, gWk, gWv, gWm, gW0, gW2, gg1, gb1, gg2, gb2)
+        gx, gs, gw = lib.attention_layer_backward(wts, C, H, x3, s3, cx, sx, cy, sy, xm, sm_, saved, ge.contiguous().float())
+        return (gx, gs, None, None, None, None, None, None, None, *gw)
 
 
 _TABLES = {}        # id(position-code tensor) -> (weak reference to it, its version counter, (cos, sin)): dropped when the tensor dies
@@ -245,6 +151,8 @@ def geometry_attention_layer(layer, x, source, x_pe, source_pe, x_mask=None, sou
     position codes are constants of the graph, as in the reference: position_encoding.py:83-84 detaches them)"""
     cx, sx = _tables(x_pe)
     cy, sy = _tables(source_pe)
+    if not _GeometryAttentionLayer.fused:
+        return _GeometryAttentionLayerG.apply(x, source, None, None, cx, sx, cy, sy, x_mask, source_mask, layer.nhead, *_layer_params(layer))
     return _GeometryAttentionLayer.apply(x, source, cx, sx, cy, sy, x_mask, source_mask, layer.nhead, *_layer_params(layer))
 
 
@@ -302,8 +210,9 @@ def motion_l1(s_pcd, R_pred, t_pred, R_gt, t_gt, overlap_mask, flow=None):
 
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 # The configuration branches no shipped yaml selects (pe_type 'sinusoidal', entangled = True, match_type 'dual_softmax'), differentiable: the
-# per-kernel form of the layer / head above with the position code entering where that branch puts it.  Same kernels, one library call each;
-# gradients pinned to the reference's autograd by tests/test_train_branches_gpu.py (oracle/make_golden_train_branches.py).
+# per-kernel form of the layer / head with the position code entering where that branch puts it (the shipped forms are two of its cases).
+# Same kernels, one library call each; gradients pinned to the reference's autograd by tests/test_train_branches_gpu.py
+# (oracle/make_golden_train_branches.py).
 # ---------------------------------------------------------------------------------------------------------------------------------------------
 class _Rotary(torch.autograd.Function):
     """embed_rotary (position_encoding.py:25-35) on [B,N,C] features with half tables: the entangled rotary form rotates the features ONCE in front of
@@ -325,7 +234,8 @@ class _Rotary(torch.autograd.Function):
 class _GeometryAttentionLayerG(torch.autograd.Function):
     """GeometryAttentionLayer.forward in the forms of transformero.py:50-57 / 246-252: q = W_q (x + x_add), k = W_k (source + s_add), v = W_v source
     (x_add / s_add: the sinusoidal code, or None), the rotary code on q and k only when tables are given (None: the entangled forms call the layers
-    without a code).  The per-kernel backward of _GeometryAttentionLayer with those inputs."""
+    without a code).  With tables and no x_add / s_add it is the shipped form, one library call per kernel: what _GeometryAttentionLayer's two
+    fused calls launch from C++, kept as the readable statement of the backward and for A/B tests."""
 
     @staticmethod
     def forward(ctx, x, source, x_add, s_add, cx, sx, cy, sy, x_mask, source_mask, H, Wq, Wk, Wv, Wm, W0, W2, g1, b1, g2, b2):
@@ -471,9 +381,7 @@ def matching_head_form(m, src_feats, tgt_feats, src_pe, tgt_pe, src_mask, tgt_ma
     W = m.src_proj.weight
     if m.entangled:
         return _MatchingHeadG.apply(src_feats, tgt_feats, W, bin_score, "none", None, None, None, None, src_mask, tgt_mask, readout, iters, temperature)
-    if pe_type == "rotary":
-        if readout == "sinkhorn":
-            return matching_head(src_feats, tgt_feats, W, bin_score, src_pe, tgt_pe, src_mask, tgt_mask, iters)          # the shipped form
+    if pe_type == "rotary":                                         # (with the Sinkhorn read-out: the shipped form, matching_head)
         cs, ss = _tables(src_pe)
         ct, st = _tables(tgt_pe)
         return _MatchingHeadG.apply(src_feats, tgt_feats, W, bin_score, "rotary", cs, ss, ct, st, src_mask, tgt_mask, readout, iters, temperature)
@@ -558,7 +466,7 @@ def matching_head(src_feats, tgt_feats, weight, bin_score, src_pe, tgt_pe, src_m
     """differentiable Matching.forward (sinkhorn, rotary): src_pe / tgt_pe = position codes [B,N,C,2] or (cos, sin) half-table pairs"""
     cs, ss = _tables(src_pe)
     ct, st = _tables(tgt_pe)
-    return _MatchingHead.apply(src_feats, tgt_feats, weight, bin_score, cs, ss, ct, st, src_mask, tgt_mask, int(iters))
+    return _MatchingHeadG.apply(src_feats, tgt_feats, weight, bin_score, "rotary", cs, ss, ct, st, src_mask, tgt_mask, "sinkhorn", int(iters), 1.0)
 
 
 def sinkhorn_conf(scores, bin_score, iters, src_mask=None, tgt_mask=None):

@@ -10,15 +10,7 @@ library's GEMM.  Gradients reach all 55 parameter tensors the reference trains i
 import torch
 
 from . import lib
-
-
-def _mm(a, b):
-    """a [R,K] @ b [N,K]^T on dr_linear_f32 (K padded to a multiple of 4: the kernel's vector width)"""
-    a, b = a.contiguous(), b.contiguous()
-    pad = (-a.shape[1]) % 4
-    if pad:
-        a, b = torch.nn.functional.pad(a, (0, pad)), torch.nn.functional.pad(b, (0, pad))
-    return lib.linear(a, b)
+from .autograd import _mm
 
 
 _tr = lambda t: t.transpose(0, 1).contiguous()
