@@ -1,7 +1,21 @@
 // sinkhorn.hip -- batched Sinkhorn normalisation with dustbins for gfx950.
 //
 // Replaces log_optimal_transport + exp + slice of the reference (3D/models/matching.py:61-93 and
-// its three call sites, see include/diffreg_hip.h).  Two kernels:
+// its three call sites, see include/diffreg_hip.h).  Five forms of one iteration (the register form with its plain-tile, non-temporal and persistent kernels); sk_plan() (the host side at the end of the
+// file) picks one per call, in this order:
+//
+//  register        N, M <= 256, conf output, not strict:   sk_reg_kernel, or for plain tiles (unmasked, no min-shift, 16-byte
+//                  accessible) of exactly 256 x 256 / 128 x 128 sk_fast_kernel; float -> float launches of >= SK_NT_MIN_TILES
+//                  256 x 256 tiles (4 x as many 128 x 128 ones) its non-temporal form, the 256 x 256 ones the persistent
+//                  sk_fast_persist_kernel.  No workspace.  The only form of the fp16 entry.
+//  stream          min-shift inside the call, or M > 2 048:  sk_stream_kernel, one workgroup per tile, E in the workspace.
+//  co-resident     conf output, not strict, and the launch resident beside SK_COOP_SHARE - 1 others:  sk_coop_kernel in ONE
+//                  launch, a wave keeps one row in registers -- or two rows (M <= 768) if only that is resident.
+//  batch           the same, 768 < M <= 2 048, at most 32 workgroups per tile and one per CU:  sk_coop_kernel with 8 rows per wave.
+//  grid            everything else (large batches, log output, strict float64):  sk_grid_kernel + sk_grid_reduce_kernel, one
+//                  launch per phase, 8 / 16 / 32 columns per lane for M <= 512 / 1 024 / 2 048.
+// Double input takes float sums unless DR_SK_STRICT, and float or double output (DR_SK_OUT_F32); float and half input keep their type.
+// The workspace of every form but the first is sized by the stream form (E) or the grid form (E + its per-tile vectors).
 //
 //  sk_reg_kernel     one workgroup per tile, the whole tile (<= 256 x 256) lives in VGPRs as
 //                    row-max-shifted exponentials E_ij = exp(Z_ij - rho_i) in [0,1].  The log-domain
@@ -1500,59 +1514,12 @@ __global__ __launch_bounds__(64 * RW) void sk_coop_kernel(SkArgs A) {
     }
 }
 
-// rows per wave of the co-resident form for a batch: 1 if the launch is then resident beside a second one, else 2 (tiles of up to 768
-// columns: two rows of 3 float4s per lane are 123-125 registers, inside the 128 of two workgroups per CU; 4 float4s are 139), else 0 = not this form
-static size_t coop_lds_bytes(int vpl) { return ((size_t)SK_COOP_RW * (vpl * 256 + 4) + 8 * SK_COOP_RW + 8) * sizeof(float); }
-// resident workgroups per CU of the instantiation (VPL, RPW) as the occupancy API reports them for its registers and LDS, the least
-// over the four (input, output) type pairs, capped by the 2 that 512-thread workgroups of <= 128 registers allow; 0 = not built
-static int coop_blocks_per_cu(int vpl, int rpw) {
-    static int cache[9][3];                                       // 0 = not asked yet, -1 = not built / query failed
-    if (vpl < 1 || vpl > 8 || rpw < 1 || rpw > 2 || (rpw == 2 && vpl > 3)) return 0;
-    int& c = cache[vpl][rpw];
-    if (c == 0) {
-        int least = 2;
-        bool ok = true;
-        auto ask = [&](const void* fn) {
-            int nb = 0;
-            const size_t lds = coop_lds_bytes(vpl);
-            if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) ok = false;
-            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * SK_COOP_RW, lds) != hipSuccess) ok = false;
-            least = nb < least ? nb : least;
-        };
-#define SK_COOP_ASK(V, R)                                                         \
-    ask((const void*)sk_coop_kernel<float, float, V, SK_COOP_RW, R>);             \
-    ask((const void*)sk_coop_kernel<double, float, V, SK_COOP_RW, R>);            \
-    ask((const void*)sk_coop_kernel<double, double, V, SK_COOP_RW, R>);
-        switch (vpl * 4 + rpw) {
-            case 1 * 4 + 1: SK_COOP_ASK(1, 1) break;
-            case 1 * 4 + 2: SK_COOP_ASK(1, 2) break;
-            case 2 * 4 + 1: SK_COOP_ASK(2, 1) break;
-            case 2 * 4 + 2: SK_COOP_ASK(2, 2) break;
-            case 3 * 4 + 1: SK_COOP_ASK(3, 1) break;
-            case 3 * 4 + 2: SK_COOP_ASK(3, 2) break;
-            case 4 * 4 + 1: SK_COOP_ASK(4, 1) break;
-            case 5 * 4 + 1: SK_COOP_ASK(5, 1) break;
-            case 6 * 4 + 1: SK_COOP_ASK(6, 1) break;
-            case 7 * 4 + 1: SK_COOP_ASK(7, 1) break;
-            case 8 * 4 + 1: SK_COOP_ASK(8, 1) break;
-            default: ok = false;
-        }
-#undef SK_COOP_ASK
-        c = (ok && least > 0) ? least : -1;
-    }
-    return c > 0 ? c : 0;
-}
-static int coop_rows_per_wave(int B, int N, int M, int flags) {
-    if (flags & (DR_SK_MINSHIFT | DR_SK_STRICT | DR_SK_OUT_LOG)) return 0;
-    if (M > 2048 || !env_knob("DR_SK_COOP", 1)) return 0;
-    const int n_cu = device_cu_count();
-    const int vpl = (M + 255) / 256;
-    // residency as the runtime reports it for the instantiation that would run, shared with SK_COOP_SHARE - 1 other launches
-    if ((long)B * sk_coop_g(N) <= (long)coop_blocks_per_cu(vpl, 1) * n_cu / SK_COOP_SHARE) return 1;
-    if (M <= 768 && env_knob("DR_SK_COOP", 1) != 2 &&
-        (long)B * ((N + 2 * SK_COOP_RW - 1) / (2 * SK_COOP_RW)) <= (long)coop_blocks_per_cu(vpl, 2) * n_cu / SK_COOP_SHARE) return 2;
-    return 0;
-}
+// ---------------------------------------------------------------------------------------------
+// Host side.  sk_plan() decides ONCE per call which form runs, with which parameters and how much workspace it needs; the size query,
+// the dispatcher and the launchers all read that plan.  sk_with_types() is the one place that turns (input type, out32, strict64) into
+// template arguments, and SK_COOP_INSTANCES the one list of co-resident instantiations the occupancy query and the launch expand from
+// (the batch form keeps its own launcher and its two instantiations).
+// ---------------------------------------------------------------------------------------------
 // The BATCH form of the co-resident kernel (round 5; cfg5's 8 x 1024 x 2048 per call): the register files of the chip hold the exponentials of
 // the whole batch.  A wave keeps EIGHT rows (256 registers of E at 2 048 columns), a workgroup is 4 waves -- one per SIMD, one workgroup per CU
 // at ~330 registers -- so 32 rows per CU and 8 192 rows on the chip: 8 tiles of 1 024 rows exactly.  One launch instead of 2 iters + 1, E never
@@ -1566,14 +1533,118 @@ static size_t coop_batch_lds_bytes(int vpl) { return ((size_t)SK_BATCH_RW * (vpl
 // (two instantiations per type pair: 4 or 8 float4 groups per lane and row.  A 6-group one -- 1 025 .. 1 536 columns -- faulted on the device
 //  for M < 1 536 in the first hardware run and was dropped unexplained: such tiles take the 8-group kernel with idle lanes)
 static int coop_batch_vpl(int M) { return M <= 1024 ? 4 : 8; }
-static bool coop_batch_path(int B, int N, int M, int flags) {
-    if (flags & (DR_SK_MINSHIFT | DR_SK_STRICT | DR_SK_OUT_LOG)) return false;
-    if (M > 2048 || M <= 768 || !env_knob("DR_SK_COOP", 1) || !env_knob("DR_SK_BATCH", 1)) return false;
-    const int n_cu = device_cu_count();
-    const long G = (N + SK_BATCH_RW * SK_BATCH_RPW - 1) / (SK_BATCH_RW * SK_BATCH_RPW);
-    return G <= 32 && (long)B * G <= n_cu;
+
+// every (VPL, RPW) instantiation of the co-resident form proper: float4 groups per lane and row, rows per wave.  Two rows per wave up to 768
+// columns (two rows of 3 float4s per lane are 123-125 registers, inside the 128 of two workgroups per CU; 4 float4s are 139)
+#define SK_COOP_INSTANCES(X) X(1, 1) X(1, 2) X(2, 1) X(2, 2) X(3, 1) X(3, 2) X(4, 1) X(5, 1) X(6, 1) X(7, 1) X(8, 1)
+static_assert(SK_COOP_RW * 2 < 32, "an instantiation of >= 32 rows per workgroup takes the half-wave reduction: it then needs the G <= 32 guard of the batch form");
+static size_t coop_lds_bytes(int vpl) { return ((size_t)SK_COOP_RW * (vpl * 256 + 4) + 8 * SK_COOP_RW + 8) * sizeof(float); }
+
+typedef void (*SkKernel)(SkArgs);
+template <typename TIn, typename TOut>
+static SkKernel coop_kernel(int vpl, int rpw) {                   // nullptr = not built
+#define SK_COOP_PICK(V, R) if (vpl == V && rpw == R) return sk_coop_kernel<TIn, TOut, V, SK_COOP_RW, R>;
+    SK_COOP_INSTANCES(SK_COOP_PICK)
+#undef SK_COOP_PICK
+    return nullptr;
 }
-static bool coop_path(int B, int N, int M, int flags) { return coop_rows_per_wave(B, N, M, flags) != 0 || coop_batch_path(B, N, M, flags); }
+
+// resident workgroups per CU of the instantiation (VPL, RPW) as the occupancy API reports them for its registers and LDS, the least
+// over the three (input, output) type pairs, capped by the 2 that 512-thread workgroups of <= 128 registers allow; 0 = not built
+static int coop_blocks_per_cu(int vpl, int rpw) {
+    static int cache[9][3];                                       // 0 = not asked yet, -1 = not built / query failed
+    if (vpl < 1 || vpl > 8 || rpw < 1 || rpw > 2) return 0;
+    int& c = cache[vpl][rpw];
+    if (c == 0) {
+        int least = 2;
+        bool ok = true;
+        const size_t lds = coop_lds_bytes(vpl);
+        for (SkKernel k : {coop_kernel<float, float>(vpl, rpw), coop_kernel<double, float>(vpl, rpw), coop_kernel<double, double>(vpl, rpw)}) {
+            int nb = 0;
+            const void* fn = (const void*)k;
+            if (!k) { ok = false; break; }
+            if (lds > 64 * 1024 && hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds) != hipSuccess) ok = false;
+            if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, fn, 64 * SK_COOP_RW, lds) != hipSuccess) ok = false;
+            least = nb < least ? nb : least;
+        }
+        c = (ok && least > 0) ? least : -1;
+    }
+    return c > 0 ? c : 0;
+}
+
+enum SkForm { SK_REG, SK_COOP, SK_BATCH, SK_GRID, SK_STREAM };
+struct SkPlan {
+    SkForm form;
+    bool out32, strict64;     // float output (always, for float / half input); double accumulation (double input with DR_SK_STRICT)
+    int cpl;                  // columns per lane: SK_REG 2 | 4 (the width of its vector accesses), SK_GRID 8 | 16 | 32
+    int rpw, vpl, G;          // SK_COOP / SK_BATCH: the instantiation (rows per wave, float4 groups per lane and row) and its workgroups per tile
+    int grid_G;               // row blocks per tile of the grid form: what it launches, and what sizes the workspace of every form but SK_REG / SK_STREAM
+};
+// the workspace: E per tile (SK_STREAM), plus the per-tile vectors of the grid form; the co-resident forms' exchange area, B sk_coop_tile_floats(N, M)
+// floats ~ a quarter of E, fits inside the grid form's.  Sized for the largest iteration count the library is used with (16), so that the size
+// query does not depend on it
+static size_t sk_workspace_bytes(const SkPlan& p, int B, int N, int M, int iters) {
+    const size_t esz = p.strict64 ? 8 : 4;
+    if (p.form == SK_REG) return 0;
+    if (p.form == SK_STREAM) return (size_t)B * N * M * esz;
+    return (size_t)B * sk_grid_tile_elems<float>(N, M, p.grid_G, iters > 16 ? iters : 16) * esz;
+}
+
+static int sk_grid_blocks(int B, int N) {
+    // enough workgroups for the chip, at least 8 rows (two per wave) per block, at most 128 blocks (the column
+    // partials are G x M values per tile)
+    const int target = env_knob("DR_SK_GRID_WGS", 512), cap = env_knob("DR_SK_GRID_CAP", 128);   // (512 = two workgroups per CU: 8 x 1024 x 2048 takes 203 us against 222 at 768 and 292 at 1536, profiles/r04_sinkhorn_grid_vec.txt)
+    int G = (target + B - 1) / B;
+    if (G > cap) G = cap;
+    if (G > (N + 7) / 8) G = (N + 7) / 8;
+    return G < 1 ? 1 : G;
+}
+
+// The selection rule (see the head of the file).  on_device = false is the size query: it does not ask the device which co-resident
+// instantiation would be resident, because those forms live inside the grid form's workspace -- it plans SK_GRID for them.
+static SkPlan sk_plan(int B, int N, int M, int in_bytes, int flags, bool on_device) {
+    SkPlan p = {};
+    p.out32 = in_bytes != 8 || (flags & DR_SK_OUT_F32);
+    p.strict64 = in_bytes == 8 && (flags & DR_SK_STRICT);
+    if (!(flags & (DR_SK_STRICT | DR_SK_OUT_LOG)) && N <= 256 && M <= 256) {
+        p.form = SK_REG; p.cpl = (N <= 128 && M <= 128) ? 2 : 4;
+        return p;
+    }
+    if ((flags & DR_SK_MINSHIFT) || M > 64 * 32) { p.form = SK_STREAM; return p; }
+    p.form = SK_GRID; p.grid_G = sk_grid_blocks(B, N);
+    p.cpl = M <= 64 * 8 ? 8 : (M <= 64 * 16 ? 16 : 32);
+    // (half input has no form beyond the register one: its entry refuses the call, and nothing is asked of the device for it)
+    const int coop = (!on_device || in_bytes == 2 || (flags & (DR_SK_STRICT | DR_SK_OUT_LOG))) ? 0 : env_knob("DR_SK_COOP", 1);
+    if (!coop) return p;
+    // co-resident: residency as the runtime reports it for the instantiation that would run, shared with SK_COOP_SHARE - 1 other launches;
+    // one row per wave if the launch is then resident beside a second one, else two
+    const int n_cu = device_cu_count();
+    const int vpl = (M + 255) / 256;
+    for (int rpw = 1; rpw <= ((M <= 768 && coop != 2) ? 2 : 1); ++rpw) {
+        const int G = (N + SK_COOP_RW * rpw - 1) / (SK_COOP_RW * rpw);
+        if ((long)B * G <= (long)coop_blocks_per_cu(vpl, rpw) * n_cu / SK_COOP_SHARE) {
+            p.form = SK_COOP; p.rpw = rpw; p.vpl = vpl; p.G = G;
+            return p;
+        }
+    }
+    // batch form: one workgroup per CU, a tile's workgroups at most the 32 partials its half-wave reduction reads
+    const int G = (N + SK_BATCH_RW * SK_BATCH_RPW - 1) / (SK_BATCH_RW * SK_BATCH_RPW);
+    if (M > 768 && env_knob("DR_SK_BATCH", 1) && G <= 32 && (long)B * G <= n_cu) {
+        p.form = SK_BATCH; p.rpw = SK_BATCH_RPW; p.vpl = coop_batch_vpl(M); p.G = G;
+    }
+    return p;
+}
+
+// (accumulate, output) types of a plan as template arguments: f(SkType<TAcc>, SkType<TOut>).  Only the combinations that can occur are
+// instantiated: half -> half and float -> float with float sums; double -> float | double with float sums, or double ones when strict
+template <typename T> struct SkType { typedef T type; };
+template <typename TIn, typename F>
+static int sk_with_types(const SkPlan& p, F&& f) {
+    if constexpr (std::is_same<TIn, _Float16>::value) return f(SkType<float>(), SkType<_Float16>());
+    else if constexpr (std::is_same<TIn, float>::value) return f(SkType<float>(), SkType<float>());
+    else if (p.strict64) return p.out32 ? f(SkType<double>(), SkType<float>()) : f(SkType<double>(), SkType<double>());
+    else return p.out32 ? f(SkType<float>(), SkType<float>()) : f(SkType<float>(), SkType<double>());
+}
 
 // flags + status of every tile start at zero: they sit behind the G partials and the column sums of the launch's G inside each tile's workspace
 // slice.  ONE launch for the batch (a hipMemsetAsync per tile was 8 x 4.8 us in front of every Sinkhorn of an 8-pair call: 183 memset nodes, 0.9 ms
@@ -1611,52 +1682,25 @@ static int launch_coop_batch(const SkArgs& a, hipStream_t st) {
     return DR_OK;
 }
 
+// SK_COOP: one launch of the plan's instantiation, G workgroups of SK_COOP_RW waves per tile
 template <typename TIn, typename TOut>
-static int launch_coop(const SkArgs& a, hipStream_t st) {
-    const int rpw = coop_rows_per_wave(a.B, a.N, a.M, a.flags);
-    if (!rpw) return DR_EINVAL;
-    const int G = (a.N + SK_COOP_RW * rpw - 1) / (SK_COOP_RW * rpw), vpl = (a.M + 255) / 256;
-    static_assert(SK_COOP_RW * 2 < 32, "an instantiation of >= 32 rows per workgroup takes the half-wave reduction: it then needs the G <= 32 guard of the batch form");
-    const int zrc = coop_zero_flags(a, G, st);
+static int launch_coop(const SkArgs& a, const SkPlan& p, hipStream_t st) {
+    const SkKernel k = coop_kernel<TIn, TOut>(p.vpl, p.rpw);
+    if (!k) return DR_ENOSUP;
+    const int zrc = coop_zero_flags(a, p.G, st);
     if (zrc) return zrc;
-    const dim3 grid(G, a.B), blk(64 * SK_COOP_RW);
-#define SK_COOP_LAUNCH(V, R)                                                                                                 \
-    {                                                                                                                        \
-        const size_t lds = coop_lds_bytes(V);                                                                                \
-        if (lds > 64 * 1024) DR_HIP_CHECK(hipFuncSetAttribute((const void*)sk_coop_kernel<TIn, TOut, V, SK_COOP_RW, R>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds)); \
-        hipLaunchKernelGGL((sk_coop_kernel<TIn, TOut, V, SK_COOP_RW, R>), grid, blk, lds, st, a);                            \
-    }
-#define SK_COOP_CASE(V) case V: SK_COOP_LAUNCH(V, 1) break;
-#define SK_COOP_CASE2(V) case V: if (rpw == 2) SK_COOP_LAUNCH(V, 2) else SK_COOP_LAUNCH(V, 1) break;
-    switch (vpl) {
-        SK_COOP_CASE2(1) SK_COOP_CASE2(2) SK_COOP_CASE2(3) SK_COOP_CASE(4) SK_COOP_CASE(5) SK_COOP_CASE(6) SK_COOP_CASE(7) SK_COOP_CASE(8)
-        default: return DR_ENOSUP;
-    }
-#undef SK_COOP_CASE
-#undef SK_COOP_CASE2
-#undef SK_COOP_LAUNCH
+    const size_t lds = coop_lds_bytes(p.vpl);
+    if (lds > 64 * 1024) DR_HIP_CHECK(hipFuncSetAttribute((const void*)k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+    hipLaunchKernelGGL(k, dim3(p.G, a.B), dim3(64 * SK_COOP_RW), lds, st, a);
     DR_LAUNCH_CHECK();
     return DR_OK;
 }
 
-static int sk_grid_blocks(int B, int N) {
-    // enough workgroups for the chip, at least 8 rows (two per wave) per block, at most 128 blocks (the column
-    // partials are G x M values per tile)
-    const int target = env_knob("DR_SK_GRID_WGS", 512), cap = env_knob("DR_SK_GRID_CAP", 128);   // (512 = two workgroups per CU: 8 x 1024 x 2048 takes 203 us against 222 at 768 and 292 at 1536, profiles/r04_sinkhorn_grid_vec.txt)
-    int G = (target + B - 1) / B;
-    if (G > cap) G = cap;
-    if (G > (N + 7) / 8) G = (N + 7) / 8;
-    return G < 1 ? 1 : G;
-}
-
-static bool grid_path(int N, int M, int flags) { return !(flags & DR_SK_MINSHIFT) && M <= 64 * 32; }
-
 template <typename TIn, typename T, typename TOut>
-static int launch_grid(const SkArgs& a, hipStream_t st) {
-    const int G = sk_grid_blocks(a.B, a.N);
-    if (a.M <= 64 * 8) return launch_grid_cpl<TIn, T, TOut, 8>(a, G, st);
-    if (a.M <= 64 * 16) return launch_grid_cpl<TIn, T, TOut, 16>(a, G, st);
-    return launch_grid_cpl<TIn, T, TOut, 32>(a, G, st);
+static int launch_grid(const SkArgs& a, const SkPlan& p, hipStream_t st) {
+    if (p.cpl == 8) return launch_grid_cpl<TIn, T, TOut, 8>(a, p.grid_G, st);
+    if (p.cpl == 16) return launch_grid_cpl<TIn, T, TOut, 16>(a, p.grid_G, st);
+    return launch_grid_cpl<TIn, T, TOut, 32>(a, p.grid_G, st);
 }
 
 static size_t stream_lds_bytes(int N, int M, size_t esz) { return ((size_t)3 * N + M + 2 + 1024 + 32) * esz + 16; }
@@ -1673,113 +1717,80 @@ static int launch_stream(const SkArgs& a, hipStream_t st) {
     return DR_OK;
 }
 
-template <typename TIn, typename TOut, bool VEC>
-static int launch_reg2(const SkArgs& a, hipStream_t st) {
-    if (a.N <= 128 && a.M <= 128) {
-        hipLaunchKernelGGL((sk_reg_kernel<TIn, TOut, 8, 2, VEC>), dim3(a.B), dim3(512), 0, st, a);
+// SK_REG.  Plain (unmasked, 16-byte accessible) 256 x 256 and 128 x 128 tiles take sk_fast_kernel; float -> float batches of at least
+// SK_NT_MIN_TILES 256 x 256 tiles (4 x as many 128 x 128 ones) its non-temporal form (float64 tiles measured slower with nt), the 256 x 256
+// ones the persistent kernel unless DR_SK_PERSIST_GRID = 0; every other tile sk_reg_kernel
+template <typename TIn, typename TOut>
+static int launch_reg(SkArgs a, const SkPlan& p, hipStream_t st) {
+    constexpr bool f32 = std::is_same<TIn, float>::value && std::is_same<TOut, float>::value;
+    const size_t in_al = p.cpl * sizeof(TIn) > 16 ? 16 : p.cpl * sizeof(TIn), out_al = p.cpl * sizeof(TOut) > 16 ? 16 : p.cpl * sizeof(TOut);
+    a.vec_in = (a.M % p.cpl == 0) && ((uintptr_t)a.scores % in_al == 0);
+    a.vec_out = (a.M % p.cpl == 0) && ((uintptr_t)a.out % out_al == 0);
+    const bool vec = a.vec_in && a.vec_out;
+    const bool plain = vec && !a.src_mask && !a.tgt_mask && !(a.flags & DR_SK_MINSHIFT);
+    SkKernel k;
+    int nw = 16;                                                  // waves per workgroup: 16 rows each
+    if (plain && a.N == 256 && a.M == 256) {
+        k = sk_fast_kernel<TIn, TOut, 16, 4, false>;
+        if constexpr (f32) if (a.B >= SK_NT_MIN_TILES) {
+            k = sk_fast_kernel<TIn, TOut, 16, 4, true>;
+            if (!a.shift && sk_persist_grid() > 0) {
+                static bool attr_done = false;
+                if (!attr_done) {
+                    DR_HIP_CHECK(hipFuncSetAttribute((const void*)sk_fast_persist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                                     (int)SKP_LDS));
+                    attr_done = true;
+                }
+                const int G = a.B < sk_persist_grid() ? a.B : sk_persist_grid();
+                hipLaunchKernelGGL(sk_fast_persist_kernel, dim3(G), dim3(1024), SKP_LDS, st, a);
+                DR_LAUNCH_CHECK();
+                return DR_OK;
+            }
+        }
+    } else if (plain && a.N == 128 && a.M == 128) {
+        k = sk_fast_kernel<TIn, TOut, 8, 2, false>; nw = 8;
+        if constexpr (f32) if (a.B >= 4 * SK_NT_MIN_TILES) k = sk_fast_kernel<TIn, TOut, 8, 2, true>;
+    } else if (a.N <= 128 && a.M <= 128) {
+        k = vec ? sk_reg_kernel<TIn, TOut, 8, 2, true> : sk_reg_kernel<TIn, TOut, 8, 2, false>; nw = 8;
     } else if (a.N <= 128) {
-        hipLaunchKernelGGL((sk_reg_kernel<TIn, TOut, 8, 4, VEC>), dim3(a.B), dim3(512), 0, st, a);
+        k = vec ? sk_reg_kernel<TIn, TOut, 8, 4, true> : sk_reg_kernel<TIn, TOut, 8, 4, false>; nw = 8;
     } else {
-        hipLaunchKernelGGL((sk_reg_kernel<TIn, TOut, 16, 4, VEC>), dim3(a.B), dim3(1024), 0, st, a);
+        k = vec ? sk_reg_kernel<TIn, TOut, 16, 4, true> : sk_reg_kernel<TIn, TOut, 16, 4, false>;
     }
+    hipLaunchKernelGGL(k, dim3(a.B), dim3(64 * nw), 0, st, a);
     DR_LAUNCH_CHECK();
     return DR_OK;
 }
-template <typename TIn, typename TOut>
-static int launch_reg(const SkArgs& a, hipStream_t st) {
-    const bool plain = a.vec_in && a.vec_out && !a.src_mask && !a.tgt_mask && !(a.flags & DR_SK_MINSHIFT);
-    if (plain && a.N == 256 && a.M == 256) {
-        if (a.B >= SK_NT_MIN_TILES && std::is_same<TIn, float>::value && std::is_same<TOut, float>::value && !a.shift &&
-            sk_persist_grid() > 0) {
-            static bool attr_done = false;
-            if (!attr_done) {
-                DR_HIP_CHECK(hipFuncSetAttribute((const void*)sk_fast_persist_kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                                 (int)SKP_LDS));
-                attr_done = true;
-            }
-            const int G = a.B < sk_persist_grid() ? a.B : sk_persist_grid();
-            hipLaunchKernelGGL(sk_fast_persist_kernel, dim3(G), dim3(1024), SKP_LDS, st, a);
-        } else if (a.B >= SK_NT_MIN_TILES && sizeof(TIn) == 4 && sizeof(TOut) == 4)   // (float64 tiles measured slower with nt)
-            hipLaunchKernelGGL((sk_fast_kernel<TIn, TOut, 16, 4, true>), dim3(a.B), dim3(1024), 0, st, a);
-        else hipLaunchKernelGGL((sk_fast_kernel<TIn, TOut, 16, 4, false>), dim3(a.B), dim3(1024), 0, st, a);
-        DR_LAUNCH_CHECK();
-        return DR_OK;
-    }
-    if (plain && a.N == 128 && a.M == 128) {
-        if (a.B >= 4 * SK_NT_MIN_TILES && sizeof(TIn) == 4 && sizeof(TOut) == 4)
-            hipLaunchKernelGGL((sk_fast_kernel<TIn, TOut, 8, 2, true>), dim3(a.B), dim3(512), 0, st, a);
-        else hipLaunchKernelGGL((sk_fast_kernel<TIn, TOut, 8, 2, false>), dim3(a.B), dim3(512), 0, st, a);
-        DR_LAUNCH_CHECK();
-        return DR_OK;
-    }
-    if (a.vec_in && a.vec_out) return launch_reg2<TIn, TOut, true>(a, st);
-    return launch_reg2<TIn, TOut, false>(a, st);
-}
 
-static bool reg_path(int N, int M, int flags) {
-    return !(flags & (DR_SK_STRICT | DR_SK_OUT_LOG)) && N <= 256 && M <= 256;
-}
-
-// workspace of the non-register paths: E per tile (stream kernel), plus the per-tile vectors of the grid form
-// (sized for the largest iteration count the library is used with, so that the size does not depend on it)
-static size_t sk_workspace_need(int B, int N, int M, int esz, int flags, int iters) {
-    if (!grid_path(N, M, flags)) return (size_t)B * N * M * esz;
-    // (the co-resident form's exchange area, B sk_coop_tile_floats(N, M) floats ~ a quarter of E, fits inside the grid form's workspace)
-    const int G = sk_grid_blocks(B, N);
-    return (size_t)B * sk_grid_tile_elems<float>(N, M, G, iters > 16 ? iters : 16) * esz;
-}
-
+// the one entry behind sinkhorn_f32 / _f64 / _f16: argument checks, plan, workspace check, launch
 template <typename TIn>
 static int sinkhorn_dispatch(int B, int N, int M, const TIn* scores, const double* shift, const uint8_t* src_mask,
                              const uint8_t* tgt_mask, const float* bin_score, int iters, int flags, void* out, void* ws,
-                             size_t ws_bytes, void* stream, unsigned* call_status = nullptr) {
+                             size_t ws_bytes, hipStream_t st, unsigned* call_status) {
+    constexpr bool f16 = std::is_same<TIn, _Float16>::value;
     if (B < 0 || N < 1 || M < 1 || iters < 1 || !scores || !bin_score || !out) return DR_EINVAL;
     if (B == 0) return DR_OK;
-    constexpr bool in64 = sizeof(TIn) == 8;
-    const bool out32 = !in64 || (flags & DR_SK_OUT_F32);
+    const SkPlan p = sk_plan(B, N, M, (int)sizeof(TIn), flags, true);
+    if (f16 && p.form != SK_REG) return DR_ENOSUP;                 // fp16 tiles: the register-resident kernels only
     SkArgs a;
     a.scores = scores; a.src_mask = src_mask; a.tgt_mask = tgt_mask; a.bin_score = bin_score;
     a.out = out; a.ws = ws; a.shift = shift; a.B = B; a.N = N; a.M = M; a.iters = iters; a.flags = flags;
+    a.vec_in = a.vec_out = 0;                                      // (the register forms set them at their launch)
     a.spin_limit = g_sk_spin_limit; a.call_status = call_status;
-    hipStream_t st = (hipStream_t)stream;
     // algorithmic bytes: read the score tile once, write the conf tile once
-    ProfScope ps(PK_SINKHORN, (double)B * N * M * (sizeof(TIn) + (out32 ? 4.0 : 8.0)), st);
-    if (reg_path(N, M, flags)) {
-        const int cpl = (N <= 128 && M <= 128) ? 2 : 4;
-        const size_t in_al = cpl * sizeof(TIn) > 16 ? 16 : cpl * sizeof(TIn);
-        const size_t osz = out32 ? 4 : 8;
-        const size_t out_al = cpl * osz > 16 ? 16 : cpl * osz;
-        a.vec_in = (M % cpl == 0) && ((uintptr_t)scores % in_al == 0);
-        a.vec_out = (M % cpl == 0) && ((uintptr_t)out % out_al == 0);
-        if (out32) return launch_reg<TIn, float>(a, st);
-        return launch_reg<TIn, double>(a, st);
-    }
-    const bool strict64 = in64 && (flags & DR_SK_STRICT);
-    const size_t need = sk_workspace_need(B, N, M, strict64 ? 8 : 4, flags, iters);
-    if (!ws || ws_bytes < need) return DR_EWORKSPACE;
-    a.vec_in = a.vec_out = 0;
-    if (coop_rows_per_wave(B, N, M, flags) != 0) {
-        if (out32) return launch_coop<TIn, float>(a, st);
-        return launch_coop<TIn, double>(a, st);
-    }
-    if (coop_batch_path(B, N, M, flags)) {
-        if (out32) return launch_coop_batch<TIn, float>(a, st);
-        return launch_coop_batch<TIn, double>(a, st);
-    }
-    if (grid_path(N, M, flags)) {
-        if (strict64) {
-            if (out32) return launch_grid<TIn, double, float>(a, st);
-            return launch_grid<TIn, double, double>(a, st);
+    ProfScope ps(PK_SINKHORN, (double)B * N * M * (sizeof(TIn) + (f16 ? 2.0 : p.out32 ? 4.0 : 8.0)), st);
+    if (p.form != SK_REG && (!ws || ws_bytes < sk_workspace_bytes(p, B, N, M, iters))) return DR_EWORKSPACE;
+    return sk_with_types<TIn>(p, [&](auto acc, auto o) {
+        using T = typename decltype(acc)::type;
+        using TOut = typename decltype(o)::type;
+        if constexpr (!std::is_same<TOut, _Float16>::value) {
+            if (p.form == SK_COOP) return launch_coop<TIn, TOut>(a, p, st);
+            if (p.form == SK_BATCH) return launch_coop_batch<TIn, TOut>(a, st);
+            if (p.form == SK_GRID) return launch_grid<TIn, T, TOut>(a, p, st);
+            if (p.form == SK_STREAM) return launch_stream<TIn, T, TOut>(a, st);
         }
-        if (out32) return launch_grid<TIn, float, float>(a, st);
-        return launch_grid<TIn, float, double>(a, st);
-    }
-    if (strict64) {
-        if (out32) return launch_stream<TIn, double, float>(a, st);
-        return launch_stream<TIn, double, double>(a, st);
-    }
-    if (out32) return launch_stream<TIn, float, float>(a, st);
-    return launch_stream<TIn, float, double>(a, st);
+        return launch_reg<TIn, TOut>(a, p, st);
+    });
 }
 
 int sinkhorn_f32(int B, int N, int M, const float* scores, const uint8_t* sm, const uint8_t* tm, const float* bin_score,
@@ -1790,34 +1801,10 @@ int sinkhorn_f64(int B, int N, int M, const double* scores, const double* shift,
                  const float* bin_score, int iters, int flags, void* out, void* ws, size_t ws_bytes, hipStream_t st, unsigned* call_status) {
     return sinkhorn_dispatch<double>(B, N, M, scores, shift, sm, tm, bin_score, iters, flags, out, ws, ws_bytes, st, call_status);
 }
-
-// fp16 tiles in, fp16 confidences out: the register-resident kernel only (tiles up to 256 x 256: BASELINE cfg1 / cfg2)
+// fp16 tiles in, fp16 confidences out (tiles up to 256 x 256: BASELINE cfg1 / cfg2), no workspace
 int sinkhorn_f16(int B, int N, int M, const void* scores, const uint8_t* sm, const uint8_t* tm, const float* bin_score, int iters, int flags,
                  void* out, hipStream_t st) {
-    if (B < 0 || N < 1 || M < 1 || iters < 1 || !scores || !bin_score || !out) return DR_EINVAL;
-    if (B == 0) return DR_OK;
-    if (!reg_path(N, M, flags)) return DR_ENOSUP;
-    SkArgs a;
-    a.scores = scores; a.src_mask = sm; a.tgt_mask = tm; a.bin_score = bin_score;
-    a.out = out; a.ws = nullptr; a.shift = nullptr; a.B = B; a.N = N; a.M = M; a.iters = iters; a.flags = flags;
-    a.spin_limit = g_sk_spin_limit; a.call_status = nullptr;
-    ProfScope ps(PK_SINKHORN, (double)B * N * M * 4.0, st);
-    const int cpl = (N <= 128 && M <= 128) ? 2 : 4;
-    a.vec_in = (M % cpl == 0) && ((uintptr_t)scores % (2 * cpl) == 0);
-    a.vec_out = (M % cpl == 0) && ((uintptr_t)out % (2 * cpl) == 0);
-    const bool plain = a.vec_in && a.vec_out && !sm && !tm && !(flags & DR_SK_MINSHIFT);
-    if (plain && N == 256 && M == 256) {              // the headline's tile: the per-tile fast kernel (16 waves x 16 rows, 4 columns per lane)
-        hipLaunchKernelGGL((sk_fast_kernel<_Float16, _Float16, 16, 4, false>), dim3(B), dim3(1024), 0, st, a);
-        DR_LAUNCH_CHECK();
-        return DR_OK;
-    }
-    if (plain && N == 128 && M == 128) {
-        hipLaunchKernelGGL((sk_fast_kernel<_Float16, _Float16, 8, 2, false>), dim3(B), dim3(512), 0, st, a);
-        DR_LAUNCH_CHECK();
-        return DR_OK;
-    }
-    if (a.vec_in && a.vec_out) return launch_reg2<_Float16, _Float16, true>(a, st);
-    return launch_reg2<_Float16, _Float16, false>(a, st);
+    return sinkhorn_dispatch<_Float16>(B, N, M, (const _Float16*)scores, nullptr, sm, tm, bin_score, iters, flags, out, nullptr, 0, st, nullptr);
 }
 
 // waits for the stream, reads (and clears) the sticky flag
@@ -1867,16 +1854,14 @@ void dr_debug_sinkhorn_spin_limit(unsigned polls) { dr::g_sk_spin_limit = polls 
 
 size_t dr_sinkhorn_workspace_bytes(int B, int N, int M, int elem_bytes, int flags) {
     if (B <= 0 || N <= 0 || M <= 0) return 0;
-    if (dr::reg_path(N, M, flags)) return 0;
-    const bool strict64 = elem_bytes == 8 && (flags & DR_SK_STRICT);
-    return dr::sk_workspace_need(B, N, M, strict64 ? 8 : 4, flags, 16);
+    return dr::sk_workspace_bytes(dr::sk_plan(B, N, M, elem_bytes, flags, false), B, N, M, 16);
 }
 
 int dr_sinkhorn_f32(int B, int N, int M, const float* scores, const uint8_t* src_mask, const uint8_t* tgt_mask,
                     const float* bin_score, int iters, int flags, float* out, void* workspace, size_t workspace_bytes,
                     void* stream) {
-    return dr::sinkhorn_dispatch<float>(B, N, M, scores, nullptr, src_mask, tgt_mask, bin_score, iters, flags, out, workspace,
-                                        workspace_bytes, stream);
+    return dr::sinkhorn_f32(B, N, M, scores, src_mask, tgt_mask, bin_score, iters, flags, out, workspace, workspace_bytes,
+                            (hipStream_t)stream, nullptr);
 }
 
 int dr_sinkhorn_f16(int B, int N, int M, const void* scores, const uint8_t* src_mask, const uint8_t* tgt_mask, const float* bin_score,
@@ -1887,8 +1872,8 @@ int dr_sinkhorn_f16(int B, int N, int M, const void* scores, const uint8_t* src_
 int dr_sinkhorn_f64(int B, int N, int M, const double* scores, const uint8_t* src_mask, const uint8_t* tgt_mask,
                     const float* bin_score, int iters, int flags, void* out, void* workspace, size_t workspace_bytes,
                     void* stream) {
-    return dr::sinkhorn_dispatch<double>(B, N, M, scores, nullptr, src_mask, tgt_mask, bin_score, iters, flags, out, workspace,
-                                         workspace_bytes, stream);
+    return dr::sinkhorn_f64(B, N, M, scores, nullptr, src_mask, tgt_mask, bin_score, iters, flags, out, workspace, workspace_bytes,
+                            (hipStream_t)stream, nullptr);
 }
 
 }  // extern "C"

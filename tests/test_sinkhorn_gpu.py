@@ -314,3 +314,52 @@ def test_two_concurrent_batch_form_launches_make_progress():
         for o in outs[s]:
             assert torch.equal(o, alone[s])
     assert dt < 0.5, dt                                            # (12 launches of ~0.1 ms; one time-out alone is seconds)
+
+
+WS_CASES = [  # (B, N, M, dtype, flags): one per form and per decision of the launch plan that sizes or checks the workspace
+    (2, 300, 400, "f32", {}), (2, 300, 400, "f64", dict(out_f32=True)), (2, 300, 400, "f64", {}),                   # co-resident, one row per wave
+    (8, 512, 512, "f32", {}), (8, 512, 768, "f32", {}), (8, 512, 769, "f32", {}),                                       # two rows per wave; 769: batch form
+    (16, 512, 800, "f32", {}), (16, 512, 1100, "f32", {}), (8, 1024, 1280, "f64", {}), (None, 32, 1100, "f32", {}),     # batch 4 / 8 groups; B = CU count + 1
+    (40, 512, 512, "f32", {}), (40, 300, 1000, "f32", {}), (40, 300, 1100, "f64", dict(out_f32=True)), (40, 300, 1001, "f32", {}),   # grid: 8 / 16 / 32 columns per lane, scalar
+    (1, 40, 300, "f32", dict(log_output=True)), (1, 300, 400, "f64", dict(strict=True)),                               # grid: log output, strict float64
+    (2, 300, 400, "f32", dict(minshift=True)), (2, 300, 400, "f64", dict(minshift=True, strict=True)), (2, 24, 2100, "f32", {}),   # stream
+    (2, 96, 80, "f32", {}), (1, 256, 256, "f64", {}), (2, 5, 7, "f64", dict(out_f32=True)), (3, 64, 250, "f32", dict(minshift=True)),   # register: no workspace
+]
+
+
+@pytest.mark.parametrize("B,N,M,dt,kw", WS_CASES)
+def test_workspace_query_is_what_dispatch_needs(B, N, M, dt, kw):
+    """dr_sinkhorn_workspace_bytes and the dispatcher size the workspace from the same rule: a call with exactly the queried bytes (between guard
+    bands) succeeds and fills the output, one byte fewer is DR_EWORKSPACE before anything is launched (the output keeps its fill); tiles of the
+    register path ask for 0 bytes and accept a null workspace."""
+    from diffreg_hip import lib
+    from tests.helpers import guarded
+    lib.ensure_init()
+    r = lib.raw()
+    f64 = dt == "f64"
+    if B is None:                                                  # one workgroup per tile, one tile more than the device has CUs: the grid form
+        B = torch.cuda.get_device_properties(0).multi_processor_count + 1
+    flags = (lib.SK_OUT_LOG if kw.get("log_output") else 0) | (lib.SK_MINSHIFT if kw.get("minshift") else 0) | \
+            (lib.SK_OUT_F32 if kw.get("out_f32") else 0) | (lib.SK_STRICT if kw.get("strict") else 0)
+    g = torch.Generator().manual_seed(N * 1000 + M)
+    x = (torch.randn(B, N, M, generator=g) * 3).to(torch.float64 if f64 else torch.float32).to(DEV)
+    odt = torch.float64 if f64 and not kw.get("out_f32") else torch.float32
+    out = torch.full((B, N + 1, M + 1) if kw.get("log_output") else (B, N, M), float("nan"), dtype=odt, device=DEV)
+    bs = torch.tensor([1.0], device=DEV)
+    fn = r.dr_sinkhorn_f64 if f64 else r.dr_sinkhorn_f32
+    call = lambda ws, nbytes: fn(B, N, M, lib.ptr(x), None, None, lib.ptr(bs), 3, flags, lib.ptr(out), ws, nbytes, lib.stream_of(x))
+    need = r.dr_sinkhorn_workspace_bytes(B, N, M, 8 if f64 else 4, flags)
+    if N <= 256 and M <= 256:
+        assert need == 0
+        assert call(None, 0) == 0
+    else:
+        assert need > 0
+        ws, check = guarded((need,), torch.uint8, DEV)
+        assert call(lib.ptr(ws), need - 1) == -4                    # DR_EWORKSPACE
+        assert call(None, need) == -4
+        torch.cuda.synchronize()
+        assert bool(torch.isnan(out).all())                        # nothing ran
+        assert call(lib.ptr(ws), need) == 0
+        check()
+    lib.device_status(DEV)
+    assert not bool(torch.isnan(out).any())
