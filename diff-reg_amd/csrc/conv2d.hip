@@ -11,6 +11,12 @@
 // in the zero padding, the pixel beyond the image or kk beyond K: the slot is then zero without touching memory.  Every address comes from
 // conv_index.h.  Cin % 4 != 0 (the 7 x 7 stem at Cin = 1) takes a direct VALU kernel.  No atomics, one fixed accumulation order per output
 // element: two runs are bit-equal.  Nothing synchronises, nothing allocates.
+//
+// The backward, under the same rules and with every output element written:
+//   dr_conv2d_rows_backward_data_f32     the same MFMA kernel over a second slot map (BwdMap: m = input pixel, kk = (tap, co)); direct for Cout % 4 != 0
+//   dr_conv2d_rows_backward_weight_f32   dW[co][kk] = sum_m G[m][co] A[m][kk] over slabs of output pixels (a function of the shape alone): float32
+//                                        partial sums per slab, added in ascending order in double; grad_bias likewise; direct for Cin % 4 != 0
+//   dr_resize_rows_backward_f32          the gather of resize_index.h, shared with dr_resize_tokens_backward_f32
 #include "kernels.h"
 #include "conv_index.h"
 #include "resize_index.h"
@@ -31,6 +37,27 @@ struct ConvArgs {
 
 constexpr int CV_BKC = 32, CV_LDT = CV_BKC + 4, CV_C4 = CV_BKC / 4, CV_NT = 256;
 
+// The slot map of the implicit GEMM  out[m][n] = sum_kk A[m][kk] B[n][kk]: what m, n and kk mean and where their elements live (conv_index.h).
+// FwdMap: m = output pixel, n = output channel, kk = (tap, ci); A = x, B = the packed weight, out = the convolution.
+// BwdMap: the roles turned (dr_conv2d_rows_backward_data_f32): m = input pixel, n = input channel, kk = (tap, co); A = grad_out read through
+// conv_bwd_a_offset, B = the weight packed [Cin, k k Cout], out = grad_x.  One kernel, one main loop, two instantiations.
+struct FwdMap {
+    static __device__ __host__ int rows(const ConvGeom& g) { return g.Ho * g.Wo; }
+    static __device__ __host__ int cols(const ConvGeom& g) { return g.Cout; }
+    static __device__ __host__ int depth(const ConvGeom& g) { return g.K; }
+    static __device__ long long a(const ConvGeom& g, int m, int kk, int ld) { return conv_a_offset(g, m, kk, ld); }
+    static __device__ long long b(const ConvGeom& g, int n, int kk) { return conv_w_offset(g, n, kk); }
+    static __device__ long long o(const ConvGeom& g, int m, int n, int ld) { return conv_o_offset(g, m, n, ld); }
+};
+struct BwdMap {
+    static __device__ __host__ int rows(const ConvGeom& g) { return g.Hi * g.Wi; }
+    static __device__ __host__ int cols(const ConvGeom& g) { return g.Cin; }
+    static __device__ __host__ int depth(const ConvGeom& g) { return conv_bwd_k(g); }
+    static __device__ long long a(const ConvGeom& g, int m, int kk, int ld) { return conv_bwd_a_offset(g, m, kk, ld); }
+    static __device__ long long b(const ConvGeom& g, int n, int kk) { return conv_bwd_w_offset(g, n, kk); }
+    static __device__ long long o(const ConvGeom& g, int m, int n, int ld) { return conv_bwd_o_offset(g, m, n, ld); }
+};
+
 // 2 x 2 waves, each TM x TN MFMA tiles of 32 x 32: a workgroup owns 64 TM output pixels x 64 TN output channels.  NBUF = 2: double-buffered LDS,
 // one barrier per chunk; NBUF = 1: one buffer, two barriers, half the LDS (the large tile: more workgroups per CU hide the second barrier).
 // VEC = false: the scalar-load arm for base pointers or leading dimensions that are not 16-byte multiples.
@@ -39,7 +66,7 @@ constexpr int CV_BKC = 32, CV_LDT = CV_BKC + 4, CV_C4 = CV_BKC / 4, CV_NT = 256;
 // ulp of the result (measured: 4.7e-7 of max|out| at K = 144, 2-3e-6 at K = 1 152 .. 4 608); windows of m terms leave sqrt(m) from the chains
 // plus one rounding per window.  FG = 1 (8 terms) for short sums, where a reference that rounds once leaves no room; FG = 4 (one k-chunk)
 // for long ones, where the adds would otherwise rival the MFMAs.  The order is fixed either way: two runs are bit-equal.
-template <int TM, int TN, int NBUF, int FG, bool VEC>
+template <class MAP, int TM, int TN, int NBUF, int FG, bool VEC>
 __global__ __launch_bounds__(CV_NT) __attribute__((amdgpu_waves_per_eu(2))) void conv2d_mfma_kernel(ConvArgs P) {
     constexpr int BM = 64 * TM, BN = 64 * TN, STAGE = (BM + BN) * CV_LDT;
     constexpr int A_SLOTS = BM * CV_C4 / CV_NT, B_SLOTS = BN * CV_C4 / CV_NT;
@@ -49,12 +76,12 @@ __global__ __launch_bounds__(CV_NT) __attribute__((amdgpu_waves_per_eu(2))) void
     const float* __restrict__ px = P.x;
     const float* __restrict__ pw = P.w;
     const int ldx = P.ldx;
-    const int tiles_n = (g.Cout + BN - 1) / BN;
+    const int tiles_n = (MAP::cols(g) + BN - 1) / BN;
     const int tm = blockIdx.x / tiles_n, tn = blockIdx.x % tiles_n;
     const int row0 = tm * BM, col0 = tn * BN;
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int wn = w & 1, wm = w >> 1;
-    const int nchunks = (g.K + CV_BKC - 1) / CV_BKC;
+    const int nchunks = (MAP::depth(g) + CV_BKC - 1) / CV_BKC;
 
     auto fetch = [&](const float* __restrict__ base, long long off) -> float4 {
         if (off < 0) return make_float4(0.f, 0.f, 0.f, 0.f);                 // no load is issued for this slot
@@ -66,12 +93,12 @@ __global__ __launch_bounds__(CV_NT) __attribute__((amdgpu_waves_per_eu(2))) void
 #pragma unroll
         for (int s = 0; s < A_SLOTS; ++s) {
             const int slot = t + s * CV_NT;
-            ra[s] = fetch(px, conv_a_offset(g, row0 + slot / CV_C4, ch * CV_BKC + 4 * (slot % CV_C4), ldx));
+            ra[s] = fetch(px, MAP::a(g, row0 + slot / CV_C4, ch * CV_BKC + 4 * (slot % CV_C4), ldx));
         }
 #pragma unroll
         for (int s = 0; s < B_SLOTS; ++s) {
             const int slot = t + s * CV_NT;
-            rb[s] = fetch(pw, conv_w_offset(g, col0 + slot / CV_C4, ch * CV_BKC + 4 * (slot % CV_C4)));
+            rb[s] = fetch(pw, MAP::b(g, col0 + slot / CV_C4, ch * CV_BKC + 4 * (slot % CV_C4)));
         }
     };
     auto store_chunk = [&](int ch) {
@@ -137,16 +164,16 @@ __global__ __launch_bounds__(CV_NT) __attribute__((amdgpu_waves_per_eu(2))) void
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int col = col0 + (wn * TN + j) * 32 + l31;
-        const float bv = (P.bias && col < g.Cout) ? P.bias[col] : 0.f;
+        const float bv = (P.bias && col < MAP::cols(g)) ? P.bias[col] : 0.f;
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = row0 + (wm * TM + i) * 32 + (r & 3) + 8 * (r >> 2) + 4 * h;
-                const long long oo = conv_o_offset(g, row, col, P.ldo);
+                const long long oo = MAP::o(g, row, col, P.ldo);
                 if (oo >= 0) {
                     float v = tot[i][j][r] + bv;
-                    if (P.addend) v += P.addend[conv_o_offset(g, row, col, P.lda)];
+                    if (P.addend) v += P.addend[MAP::o(g, row, col, P.lda)];
                     P.out[oo] = v;
                 }
             }
@@ -211,21 +238,231 @@ __global__ __launch_bounds__(256) void resize_rows_kernel(int C, int Hs, int Ws,
     out[(size_t)p * ldo + c] = v;
 }
 
-template <int TM, int TN, int NBUF, int FG>
-static int launch_conv_mfma(const ConvArgs& A, bool vec, hipStream_t st) {
-    const long long tiles = (long long)((A.g.Ho * A.g.Wo + 64 * TM - 1) / (64 * TM)) * ((A.g.Cout + 64 * TN - 1) / (64 * TN));
-    ProfScope ps(PK_GEMM, 2.0 * A.g.Ho * A.g.Wo * A.g.Cout * A.g.K, st);
-    if (vec) hipLaunchKernelGGL((conv2d_mfma_kernel<TM, TN, NBUF, FG, true>), dim3((unsigned)tiles), dim3(CV_NT), 0, st, A);
-    else hipLaunchKernelGGL((conv2d_mfma_kernel<TM, TN, NBUF, FG, false>), dim3((unsigned)tiles), dim3(CV_NT), 0, st, A);
-    DR_LAUNCH_CHECK();
-    return DR_OK;
-}
-
 // 128 x 128 tiles (half the operand traffic per multiply-add) once there are two of them per compute unit of an MI355X, 64 x 64 tiles below:
 // a fixed count, so the same problem takes the same kernel, and sums in the same order, on every device
 constexpr long long CV_LARGE_TILES = 512;
 // sums of up to this many terms add their partial sums every 8 terms, longer ones every 32 (see the kernel)
 constexpr int CV_SHORT_K = 1024;
+
+template <class MAP, int TM, int TN, int NBUF, int FG>
+static int launch_conv_mfma(const ConvArgs& A, bool vec, hipStream_t st) {
+    const long long tiles = (long long)((MAP::rows(A.g) + 64 * TM - 1) / (64 * TM)) * ((MAP::cols(A.g) + 64 * TN - 1) / (64 * TN));
+    ProfScope ps(PK_GEMM, 2.0 * MAP::rows(A.g) * MAP::cols(A.g) * MAP::depth(A.g), st);
+    if (vec) hipLaunchKernelGGL((conv2d_mfma_kernel<MAP, TM, TN, NBUF, FG, true>), dim3((unsigned)tiles), dim3(CV_NT), 0, st, A);
+    else hipLaunchKernelGGL((conv2d_mfma_kernel<MAP, TM, TN, NBUF, FG, false>), dim3((unsigned)tiles), dim3(CV_NT), 0, st, A);
+    DR_LAUNCH_CHECK();
+    return DR_OK;
+}
+
+// the tile and window choice of both implicit GEMMs: rows x cols x depth of the map
+template <class MAP>
+static int dispatch_conv_mfma(const ConvArgs& A, bool vec, hipStream_t st) {
+    const long long large = (long long)((MAP::rows(A.g) + 127) / 128) * ((MAP::cols(A.g) + 127) / 128);
+    if (MAP::depth(A.g) <= CV_SHORT_K) return launch_conv_mfma<MAP, 1, 1, 2, 1>(A, vec, st);     // (the large tile has no registers for a window per group)
+    return large >= CV_LARGE_TILES ? launch_conv_mfma<MAP, 2, 2, 1, 4>(A, vec, st) : launch_conv_mfma<MAP, 1, 1, 2, 4>(A, vec, st);
+}
+
+
+// ---- the backward ---------------------------------------------------------------------------------------------------------------------
+
+// Data gradient, direct form for Cout % 4 != 0: a thread owns one (input pixel, input channel), lanes along the channel; the sum runs over
+// (ky, kx, co) ascending in double and is rounded once.  Taps without an output pixel are skipped.
+__global__ __launch_bounds__(256) void conv2d_dgrad_direct_kernel(ConvArgs P) {
+    const ConvGeom g = P.g;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int m = (int)(e / g.Cin), ci = (int)(e - (long long)m * g.Cin);
+    const long long oo = conv_bwd_o_offset(g, m, ci, P.ldo);
+    if (oo < 0) return;
+    double acc = 0.0;
+    for (int tap = 0; tap < g.k * g.k; ++tap) {
+        const long long ao = conv_bwd_a_offset(g, m, tap * g.Cout, P.ldx);
+        if (ao < 0) continue;
+        for (int co = 0; co < g.Cout; ++co) acc = fma((double)P.x[ao + co], (double)P.w[conv_bwd_w_offset(g, ci, tap * g.Cout + co)], acc);
+    }
+    float v = (float)acc;
+    if (P.addend) v += P.addend[conv_bwd_o_offset(g, m, ci, P.lda)];
+    P.out[oo] = v;
+}
+
+struct WgradArgs {
+    ConvGeom g;
+    ConvSlabs sl;
+    const float* x;        // [Hi Wi, ldx]
+    const float* go;       // grad_out [Ho Wo, ldg]
+    float* part;           // [S, Cout, K] float32 partial sums
+    double* bpart;         // [S, Cout] double partial sums of grad_bias
+    float* gw;             // [Cout, K] or nullptr
+    float* gb;             // [Cout] or nullptr
+    int ldx, ldg;
+};
+
+// Weight gradient  dW[co][kk] = sum_m G[m][co] A[m][kk]  on v_mfma_f32_32x32x2_f32.  A workgroup owns one (64 output channels, 64 positions kk,
+// slab of output pixels); 2 x 2 waves of one 32 x 32 tile.  Both operands have the REDUCTION index m as their row, so a chunk of CV_WG_CHUNK = 32
+// pixels is staged as [m][64 co] and [m][64 kk] and the lanes that read one k-step of the MFMA (lane half h takes pixel 2 e + h, lane & 31 the
+// channel / position) touch consecutive words: no transpose.  The A slots are the forward's: one (output pixel, 4-channel group of a tap) per
+// 16-byte load through conv_a_offset, or nothing for a tap in the padding.  The row stride 96 puts the two lane halves 32 banks apart.
+// Accumulation: the MFMA chain runs over windows of 8 pixels from zero, each window is added to a float32 total (the forward's FG = 1 rule);
+// the total of the slab is written to the workspace and wgrad_reduce_kernel adds the slabs in ascending order in double.
+constexpr int WG_BT = 64, WG_LDW = WG_BT + 32, WG_Q = WG_BT / 4, WG_SLOTS = CV_WG_CHUNK * WG_Q / CV_NT, WG_STAGE = 2 * CV_WG_CHUNK * WG_LDW;
+template <bool VEC>
+__global__ __launch_bounds__(CV_NT) void conv2d_wgrad_mfma_kernel(WgradArgs P) {
+    __shared__ __attribute__((aligned(16))) float smem[2 * WG_STAGE];
+    const ConvGeom g = P.g;
+    const ConvSlabs sl = P.sl;
+    const float* __restrict__ px = P.x;
+    const float* __restrict__ pg = P.go;
+    const int ldx = P.ldx, ldg = P.ldg;
+    const int tiles_k = (g.K + WG_BT - 1) / WG_BT, tiles_c = (g.Cout + WG_BT - 1) / WG_BT;
+    const int tk = blockIdx.x % tiles_k, tc = (blockIdx.x / tiles_k) % tiles_c, slab = blockIdx.x / (tiles_k * tiles_c);
+    const int co0 = tc * WG_BT, kk0 = tk * WG_BT;
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int wn = w & 1, wm = w >> 1;
+    const int nchunks = sl.L / CV_WG_CHUNK;
+
+    float4 ra[WG_SLOTS], rg[WG_SLOTS];
+    auto load_chunk = [&](int ch) {
+#pragma unroll
+        for (int s = 0; s < WG_SLOTS; ++s) {
+            const int slot = t + s * CV_NT;
+            const int m = conv_slab_pixel(g, sl, slab, ch * CV_WG_CHUNK + slot / WG_Q), c4 = 4 * (slot % WG_Q);
+            const long long ao = m < 0 ? -1 : conv_a_offset(g, m, kk0 + c4, ldx);
+            if (ao < 0) ra[s] = make_float4(0.f, 0.f, 0.f, 0.f);
+            else if (VEC) ra[s] = *reinterpret_cast<const float4*>(px + ao);
+            else ra[s] = make_float4(px[ao], px[ao + 1], px[ao + 2], px[ao + 3]);
+            if (VEC) {                                                               // Cout % 4 == 0: the group is inside the row whenever its first element is
+                const long long o = m < 0 ? -1 : conv_o_offset(g, m, co0 + c4, ldg);
+                rg[s] = o < 0 ? make_float4(0.f, 0.f, 0.f, 0.f) : *reinterpret_cast<const float4*>(pg + o);
+            } else {
+                float v[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const long long o = m < 0 ? -1 : conv_o_offset(g, m, co0 + c4 + e, ldg);
+                    v[e] = o < 0 ? 0.f : pg[o];
+                }
+                rg[s] = make_float4(v[0], v[1], v[2], v[3]);
+            }
+        }
+    };
+    auto store_chunk = [&](int ch) {
+        float* Gs = smem + (ch & 1) * WG_STAGE;
+        float* As = Gs + CV_WG_CHUNK * WG_LDW;
+#pragma unroll
+        for (int s = 0; s < WG_SLOTS; ++s) {
+            const int slot = t + s * CV_NT;
+            *reinterpret_cast<float4*>(Gs + (slot / WG_Q) * WG_LDW + 4 * (slot % WG_Q)) = rg[s];
+            *reinterpret_cast<float4*>(As + (slot / WG_Q) * WG_LDW + 4 * (slot % WG_Q)) = ra[s];
+        }
+    };
+
+    f32x16 acc, tot;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) tot[r] = 0.f, acc[r] = 0.f;
+    const f32x16 zero = tot;
+    const int h = lane >> 5, l31 = lane & 31;
+    load_chunk(0);
+    store_chunk(0);
+    __syncthreads();
+    for (int ch = 0; ch < nchunks; ++ch) {
+        if (ch + 1 < nchunks) load_chunk(ch + 1);
+        const float* Gs = smem + (ch & 1) * WG_STAGE + h * WG_LDW + wm * 32 + l31;
+        const float* As = smem + (ch & 1) * WG_STAGE + CV_WG_CHUNK * WG_LDW + h * WG_LDW + wn * 32 + l31;
+#pragma unroll
+        for (int e = 0; e < CV_WG_CHUNK / 2; ++e) {
+            const float a = Gs[2 * e * WG_LDW], b = As[2 * e * WG_LDW];
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b, (e % 4 == 0) ? zero : acc, 0, 0, 0);      // a window of 8 pixels starts from zero
+            if (e % 4 == 3) tot += acc;
+        }
+        if (ch + 1 < nchunks) store_chunk(ch + 1);           // the other buffer: its readers passed the barrier below one chunk ago
+        __syncthreads();
+    }
+    // C/D layout of the 32x32 MFMA: col = lane & 31 (the position kk), row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5) (the output channel)
+#pragma unroll
+    for (int r = 0; r < 16; ++r) {
+        const long long o = conv_wg_part_offset(g, sl, slab, co0 + wm * 32 + (r & 3) + 8 * (r >> 2) + 4 * h, kk0 + wn * 32 + l31);
+        if (o >= 0) P.part[o] = tot[r];
+    }
+}
+
+// Weight gradient, direct form for Cin % 4 != 0 (the stem: K = 49): a thread owns one (output channel, position kk) of one slab and sums the
+// slab's pixels in ascending order in double; the same partials, the same second pass.
+__global__ __launch_bounds__(256) void conv2d_wgrad_direct_kernel(WgradArgs P) {
+    const ConvGeom g = P.g;
+    const ConvSlabs sl = P.sl;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x;
+    const int slab = blockIdx.y, co = (int)(e / g.K), kk = (int)(e - (long long)co * g.K);
+    const long long po = conv_wg_part_offset(g, sl, slab, co, kk);
+    if (po < 0) return;
+    double acc = 0.0;
+    for (int j = 0; j < sl.L; ++j) {
+        const int m = conv_slab_pixel(g, sl, slab, j);
+        if (m < 0) break;
+        const long long ao = conv_a_offset(g, m, kk, P.ldx);
+        if (ao >= 0) acc = fma((double)P.go[conv_o_offset(g, m, co, P.ldg)], (double)P.x[ao], acc);
+    }
+    P.part[po] = (float)acc;
+}
+
+// grad_bias partials: the column sums of grad_out over one slab.  Lanes along the channel; the four waves take the slab's pixels j = wave, wave + 4,
+// ... in ascending order in double and are then added in wave order.
+__global__ __launch_bounds__(256) void conv2d_bias_partial_kernel(WgradArgs P) {
+    __shared__ double red[4][64];
+    const ConvGeom g = P.g;
+    const ConvSlabs sl = P.sl;
+    const int slab = blockIdx.y, lane = threadIdx.x & 63, wv = threadIdx.x >> 6, co = blockIdx.x * 64 + lane;
+    double acc = 0.0;
+    for (int j = wv; j < sl.L; j += 4) {
+        const int m = conv_slab_pixel(g, sl, slab, j);
+        const long long o = m < 0 ? -1 : conv_o_offset(g, m, co, P.ldg);
+        if (o >= 0) acc += (double)P.go[o];
+    }
+    red[wv][lane] = acc;
+    __syncthreads();
+    if (wv == 0 && co < g.Cout) P.bpart[(size_t)slab * g.Cout + co] = ((red[0][lane] + red[1][lane]) + red[2][lane]) + red[3][lane];
+}
+
+// the second pass: element e < Cout K of grad_w, then element e - Cout K of grad_bias; slabs in ascending order in double, rounded once
+__global__ __launch_bounds__(256) void conv2d_wgrad_reduce_kernel(WgradArgs P) {
+    const ConvGeom g = P.g;
+    const long long e = (long long)blockIdx.x * 256 + threadIdx.x, nw = (long long)g.Cout * g.K;
+    if (e < nw) {
+        if (!P.gw) return;
+        const int co = (int)(e / g.K), kk = (int)(e - (long long)co * g.K);
+        double acc = 0.0;
+        for (int s = 0; s < P.sl.S; ++s) acc += (double)P.part[conv_wg_part_offset(g, P.sl, s, co, kk)];
+        P.gw[conv_w_offset(g, co, kk)] = (float)acc;
+    } else if (e < nw + g.Cout && P.gb) {
+        const int co = (int)(e - nw);
+        double acc = 0.0;
+        for (int s = 0; s < P.sl.S; ++s) acc += P.bpart[(size_t)s * g.Cout + co];
+        P.gb[co] = (float)acc;
+    }
+}
+
+// grad_in[s][c] = the sum over the destination pixels whose footprint holds source texel s (resize_gather: the statement shared with
+// dr_resize_tokens_backward_f32): lanes along the channel
+__global__ __launch_bounds__(256) void resize_rows_backward_kernel(int C, int Hs, int Ws, int Hd, int Wd, const float* __restrict__ g, int ldg,
+                                                                   float* __restrict__ grad_in, int ldgi) {
+    const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (e >= (size_t)Hs * Ws * C) return;
+    const int s = (int)(e / C), c = (int)(e % C);
+    const int ys = s / Ws, xs = s - ys * Ws;
+    const double acc = resize_gather(resize_scale(Hs, Hd), resize_scale(Ws, Wd), ys, xs, Hs, Ws, Hd, Wd,
+                                     [&](int pd) { return g[(size_t)pd * ldg + c]; });
+    grad_in[(size_t)s * ldgi + c] = (float)acc;
+}
+
+// the geometry checks of the two gradients (the forward entry's, and k k Cout as well): DR_OK, DR_EINVAL or DR_ENOSUP, and the geometry
+static int conv_check_geom(int Hi, int Wi, int Cin, int Cout, int k, int stride, int padding, int dilation, ConvGeom& g) {
+    if (Hi < 1 || Wi < 1 || Cin < 1 || Cout < 1 || k < 1 || stride < 1 || padding < 0 || dilation < 1) return DR_EINVAL;
+    if (k > 31 || stride > 64 || padding > 1024 || dilation > 64) return DR_ENOSUP;
+    if ((long long)Hi * Wi > (1ll << 24) || Cin > (1 << 16) || Cout > (1 << 16) || (long long)k * k * Cin > (1ll << 20) ||
+        (long long)k * k * Cout > (1ll << 20))
+        return DR_ENOSUP;
+    g = conv_geom(Hi, Wi, Cin, Cout, k, stride, padding, dilation);
+    if (g.Ho < 1 || g.Wo < 1) return DR_EINVAL;
+    if ((long long)g.Ho * g.Wo > (1ll << 24)) return DR_ENOSUP;
+    return DR_OK;
+}
 
 }  // namespace dr
 
@@ -248,9 +485,7 @@ int dr_conv2d_rows_f32(int Hi, int Wi, int Cin, int Cout, int k, int stride, int
     const hipStream_t st = (hipStream_t)stream;
     if (Cin % 4 == 0) {
         const bool vec = ((((uintptr_t)x) | ((uintptr_t)weight)) & 15u) == 0 && ldx % 4 == 0;
-        const long long large = (long long)((g.Ho * g.Wo + 127) / 128) * ((Cout + 127) / 128);
-        if (g.K <= CV_SHORT_K) return launch_conv_mfma<1, 1, 2, 1>(A, vec, st);     // (the large tile has no registers for a window per group)
-        return large >= CV_LARGE_TILES ? launch_conv_mfma<2, 2, 1, 4>(A, vec, st) : launch_conv_mfma<1, 1, 2, 4>(A, vec, st);
+        return dispatch_conv_mfma<FwdMap>(A, vec, st);
     }
     const dim3 grid((g.Ho * g.Wo + 4 * CV_DPX - 1) / (4 * CV_DPX), (Cout + 63) / 64);
     hipLaunchKernelGGL(conv2d_direct_kernel, grid, dim3(256), 0, st, A);
@@ -268,6 +503,85 @@ int dr_resize_rows_f32(int C, int Hs, int Ws, int Hd, int Wd, const float* in, i
     const size_t n = (size_t)Hd * Wd * C;
     if ((n + 255) / 256 > 0x7fffffffull) return DR_ENOSUP;
     resize_rows_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(C, Hs, Ws, Hd, Wd, in, ldi, addend, lda, out, ldo);
+    DR_LAUNCH_CHECK();
+    return DR_OK;
+}
+
+int dr_conv2d_rows_backward_data_f32(int Hi, int Wi, int Cin, int Cout, int k, int stride, int padding, int dilation, const float* grad_out, int ldg,
+                                     const float* weight_t, const float* addend, int lda, float* grad_x, int ldgx, void* stream) {
+    ConvGeom g;
+    if (Hi < 1 || Wi < 1 || Cin < 1 || Cout < 1) return DR_EINVAL;
+    if (!grad_out || !weight_t || !grad_x || ldg < Cout || ldgx < Cin || (addend && lda < Cin)) return DR_EINVAL;
+    if ((((uintptr_t)grad_out) | ((uintptr_t)weight_t) | ((uintptr_t)addend) | ((uintptr_t)grad_x)) & 3u) return DR_EINVAL;
+    const int rc = conv_check_geom(Hi, Wi, Cin, Cout, k, stride, padding, dilation, g);
+    if (rc != DR_OK) return rc;
+    if (ldg > (1 << 20) || ldgx > (1 << 20) || lda > (1 << 20)) return DR_ENOSUP;
+    ConvArgs A{g, grad_out, weight_t, nullptr, addend, grad_x, ldg, lda, ldgx};
+    const hipStream_t st = (hipStream_t)stream;
+    if (Cout % 4 == 0) {
+        const bool vec = ((((uintptr_t)grad_out) | ((uintptr_t)weight_t)) & 15u) == 0 && ldg % 4 == 0;
+        return dispatch_conv_mfma<BwdMap>(A, vec, st);
+    }
+    const long long n = (long long)Hi * Wi * Cin;
+    if ((n + 255) / 256 > 0x7fffffffll) return DR_ENOSUP;
+    hipLaunchKernelGGL(conv2d_dgrad_direct_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A);
+    DR_LAUNCH_CHECK();
+    return DR_OK;
+}
+
+size_t dr_conv2d_rows_backward_weight_workspace_bytes(int Hi, int Wi, int Cin, int Cout, int k, int stride, int padding, int dilation) {
+    ConvGeom g;
+    if (conv_check_geom(Hi, Wi, Cin, Cout, k, stride, padding, dilation, g) != DR_OK) return 0;
+    return (size_t)conv_wg_workspace_bytes(g, conv_wgrad_slabs(g.Ho * g.Wo));
+}
+
+int dr_conv2d_rows_backward_weight_f32(int Hi, int Wi, int Cin, int Cout, int k, int stride, int padding, int dilation, const float* x, int ldx,
+                                       const float* grad_out, int ldg, float* grad_w, float* grad_bias, void* workspace, size_t workspace_bytes,
+                                       void* stream) {
+    ConvGeom g;
+    if (Hi < 1 || Wi < 1 || Cin < 1 || Cout < 1) return DR_EINVAL;
+    if (!x || !grad_out || !workspace || ldx < Cin || ldg < Cout) return DR_EINVAL;
+    if ((((uintptr_t)x) | ((uintptr_t)grad_out) | ((uintptr_t)grad_w) | ((uintptr_t)grad_bias)) & 3u) return DR_EINVAL;
+    if (((uintptr_t)workspace) & 15u) return DR_EINVAL;
+    const int rc = conv_check_geom(Hi, Wi, Cin, Cout, k, stride, padding, dilation, g);
+    if (rc != DR_OK) return rc;
+    if (ldx > (1 << 20) || ldg > (1 << 20)) return DR_ENOSUP;
+    const ConvSlabs sl = conv_wgrad_slabs(g.Ho * g.Wo);
+    if (workspace_bytes < (size_t)conv_wg_workspace_bytes(g, sl)) return DR_EINVAL;
+    if (!grad_w && !grad_bias) return DR_OK;
+    WgradArgs A{g, sl, x, grad_out, (float*)workspace, (double*)((char*)workspace + conv_wg_bias_part_byte(g, sl)), grad_w, grad_bias, ldx, ldg};
+    const hipStream_t st = (hipStream_t)stream;
+    if (grad_w) {
+        if (Cin % 4 == 0) {
+            const bool vec = ((((uintptr_t)x) | ((uintptr_t)grad_out)) & 15u) == 0 && ldx % 4 == 0 && ldg % 4 == 0 && Cout % 4 == 0;
+            const unsigned grid = (unsigned)(sl.S * ((Cout + WG_BT - 1) / WG_BT) * ((g.K + WG_BT - 1) / WG_BT));
+            ProfScope ps(PK_GEMM, 2.0 * g.Ho * g.Wo * Cout * g.K, st);
+            if (vec) hipLaunchKernelGGL(conv2d_wgrad_mfma_kernel<true>, dim3(grid), dim3(CV_NT), 0, st, A);
+            else hipLaunchKernelGGL(conv2d_wgrad_mfma_kernel<false>, dim3(grid), dim3(CV_NT), 0, st, A);
+        } else {
+            const dim3 grid((unsigned)(((long long)Cout * g.K + 255) / 256), (unsigned)sl.S);
+            hipLaunchKernelGGL(conv2d_wgrad_direct_kernel, grid, dim3(256), 0, st, A);
+        }
+        DR_LAUNCH_CHECK();
+    }
+    if (grad_bias) {
+        hipLaunchKernelGGL(conv2d_bias_partial_kernel, dim3((unsigned)((Cout + 63) / 64), (unsigned)sl.S), dim3(256), 0, st, A);
+        DR_LAUNCH_CHECK();
+    }
+    const long long n = (long long)Cout * g.K + Cout;
+    hipLaunchKernelGGL(conv2d_wgrad_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, A);
+    DR_LAUNCH_CHECK();
+    return DR_OK;
+}
+
+int dr_resize_rows_backward_f32(int C, int Hs, int Ws, int Hd, int Wd, const float* grad_out, int ldg, float* grad_in, int ldgi, void* stream) {
+    if (C < 1 || Hs < 1 || Ws < 1 || Hd < 1 || Wd < 1) return DR_EINVAL;
+    if (!grad_out || !grad_in || ldg < C || ldgi < C) return DR_EINVAL;
+    if ((((uintptr_t)grad_out) | ((uintptr_t)grad_in)) & 3u) return DR_EINVAL;
+    if ((long long)Hs * Ws > (1ll << 24) || (long long)Hd * Wd > (1ll << 24) || C > (1 << 20) || ldg > (1 << 20) || ldgi > (1 << 20)) return DR_ENOSUP;
+    const size_t n = (size_t)Hs * Ws * C;
+    if ((n + 255) / 256 > 0x7fffffffull) return DR_ENOSUP;
+    resize_rows_backward_kernel<<<(unsigned)((n + 255) / 256), 256, 0, (hipStream_t)stream>>>(C, Hs, Ws, Hd, Wd, grad_out, ldg, grad_in, ldgi);
     DR_LAUNCH_CHECK();
     return DR_OK;
 }

@@ -1,7 +1,7 @@
-// conv_index.h -- the index arithmetic of dr_conv2d_rows_f32 (conv2d.hip): nn.Conv2d (groups = 1, zero padding, square kernel k, stride s,
+// conv_index.h -- the index arithmetic of dr_conv2d_rows_f32 and of its two gradients (conv2d.hip): nn.Conv2d (groups = 1, zero padding, square kernel k, stride s,
 // padding p, dilation d) on token rows [H W, C].  The kernels compute every address through these functions and nothing else, and
 // tools/conv_index_check.cpp walks the same functions on the host over every (output pixel, tap, 4-channel group) of the tested and the
-// production shapes before anything runs on a device.  No HIP type in here: the file compiles as plain C++.
+// production shapes before anything runs on a device (tools/conv_bwd_index_check.cpp for the gradients).  No HIP type in here: the file compiles as plain C++.
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -71,6 +71,83 @@ DR_HD long long conv_w_offset(const ConvGeom& g, int co, int kk) {
 DR_HD long long conv_o_offset(const ConvGeom& g, int m, int co, int ld) {
     if (m < 0 || m >= g.Ho * g.Wo || co < 0 || co >= g.Cout) return -1;
     return (long long)m * ld + co;
+}
+
+// ---- the backward (dr_conv2d_rows_backward_data_f32, dr_conv2d_rows_backward_weight_f32); walked by tools/conv_bwd_index_check.cpp ----------
+
+// (input pixel (iy, ix), tap (ky, kx)) -> the output row oy Wo + ox whose tap (ky, kx) reads that pixel, or -1 when there is none: iy = oy s - p +
+// ky d has a solution only if iy + p - ky d is >= 0, divisible by s, and its quotient lies inside Ho (the same for x)
+DR_HD int conv_bwd_tap_row(const ConvGeom& g, int iy, int ix, int ky, int kx) {
+    const int ty = iy + g.p - ky * g.d, tx = ix + g.p - kx * g.d;
+    if (ty < 0 || tx < 0 || ty % g.s != 0 || tx % g.s != 0) return -1;
+    const int oy = ty / g.s, ox = tx / g.s;
+    return (oy < g.Ho && ox < g.Wo) ? oy * g.Wo + ox : -1;
+}
+
+// the length of one row of the data gradient's packed weight [Cin, k k Cout] (tap-major, co-minor)
+DR_HD int conv_bwd_k(const ConvGeom& g) { return g.k * g.k * g.Cout; }
+
+// The A operand of the data gradient: element (input pixel m, position kk = (tap, co)) -> offset into grad_out [Ho Wo, ldg], or -1 for "zero, load
+// nothing".  With Cout % 4 == 0 a 4-wide group lies inside one tap.
+DR_HD long long conv_bwd_a_offset(const ConvGeom& g, int m, int kk, int ldg) {
+    if (m < 0 || m >= g.Hi * g.Wi || kk < 0 || kk >= conv_bwd_k(g)) return -1;
+    const int iy = m / g.Wi, ix = m - iy * g.Wi;
+    const int tap = kk / g.Cout, co = kk - tap * g.Cout;
+    const int ky = tap / g.k, kx = tap - ky * g.k;
+    const int row = conv_bwd_tap_row(g, iy, ix, ky, kx);
+    return row < 0 ? -1 : (long long)row * ldg + co;
+}
+
+// The B operand of the data gradient: element (input channel ci, position kk) of the packed [Cin, k k Cout], or -1 outside it
+DR_HD long long conv_bwd_w_offset(const ConvGeom& g, int ci, int kk) {
+    if (ci < 0 || ci >= g.Cin || kk < 0 || kk >= conv_bwd_k(g)) return -1;
+    return (long long)ci * conv_bwd_k(g) + kk;
+}
+
+// The data gradient (and its addend): element (input pixel m, channel ci) of a [Hi Wi, ld] buffer, or -1 outside it
+DR_HD long long conv_bwd_o_offset(const ConvGeom& g, int m, int ci, int ld) {
+    if (m < 0 || m >= g.Hi * g.Wi || ci < 0 || ci >= g.Cin) return -1;
+    return (long long)m * ld + ci;
+}
+
+// The weight gradient reduces over the M = Ho Wo output pixels in S slabs of L pixels (the last one ragged).  S and L are functions of M alone --
+// never of the device -- so a problem sums in the same order everywhere: S0 = min(64, ceil(M / 2048)), L = ceil(M / S0) rounded up to the
+// 32-pixel chunk of the kernel, S = ceil(M / L) (no slab is empty).
+constexpr int CV_WG_CHUNK = 32, CV_WG_SLAB = 2048, CV_WG_MAX_SLABS = 64;
+struct ConvSlabs {
+    int S, L;
+};
+DR_HD ConvSlabs conv_wgrad_slabs(int M) {
+    int s0 = (M + CV_WG_SLAB - 1) / CV_WG_SLAB;
+    if (s0 > CV_WG_MAX_SLABS) s0 = CV_WG_MAX_SLABS;
+    if (s0 < 1) s0 = 1;
+    ConvSlabs r;
+    r.L = ((M + s0 - 1) / s0 + CV_WG_CHUNK - 1) / CV_WG_CHUNK * CV_WG_CHUNK;
+    if (r.L < CV_WG_CHUNK) r.L = CV_WG_CHUNK;
+    r.S = (M + r.L - 1) / r.L;
+    if (r.S < 1) r.S = 1;
+    return r;
+}
+
+// output pixel j of slab s -> the pixel m, or -1 beyond the slab or the image (a ragged chunk)
+DR_HD int conv_slab_pixel(const ConvGeom& g, const ConvSlabs& sl, int s, int j) {
+    if (s < 0 || s >= sl.S || j < 0 || j >= sl.L) return -1;
+    const long long m = (long long)s * sl.L + j;
+    return m < (long long)g.Ho * g.Wo ? (int)m : -1;
+}
+
+// element (slab s, output channel co, position kk) of the float32 partial sums [S, Cout, K], or -1 outside them
+DR_HD long long conv_wg_part_offset(const ConvGeom& g, const ConvSlabs& sl, int s, int co, int kk) {
+    if (s < 0 || s >= sl.S || co < 0 || co >= g.Cout || kk < 0 || kk >= g.K) return -1;
+    return ((long long)s * g.Cout + co) * g.K + kk;
+}
+
+// the workspace of the weight gradient: the float32 partials [S, Cout, K] (rounded up to 8 bytes), then the double partials [S, Cout] of grad_bias
+DR_HD long long conv_wg_bias_part_byte(const ConvGeom& g, const ConvSlabs& sl) {
+    return ((long long)sl.S * g.Cout * g.K * 4 + 7) / 8 * 8;
+}
+DR_HD long long conv_wg_workspace_bytes(const ConvGeom& g, const ConvSlabs& sl) {
+    return conv_wg_bias_part_byte(g, sl) + (long long)sl.S * g.Cout * 8;
 }
 
 }  // namespace dr

@@ -146,16 +146,7 @@ __global__ void __launch_bounds__(FR_BLOCK) resize_tokens_kernel(int C, int Hs, 
     }
 }
 
-// the destinations d in [lo, hi] are the only ones whose footprint can hold source index s (widened by one on either side; every
-// candidate is then tested with resize_src itself, so forward and backward agree on every footprint)
-__device__ __forceinline__ void resize_candidates(double scale, int s, int out, int& lo, int& hi) {
-    if (scale <= 0.0) { lo = 0; hi = out - 1; return; }
-    lo = (int)floor((s - 1) / scale) - 1;
-    hi = (int)ceil((s + 1) / scale) + 1;
-    if (lo < 0) lo = 0;
-    if (hi > out - 1) hi = out - 1;
-}
-
+// resize_candidates / resize_gather: resize_index.h (shared with dr_resize_rows_backward_f32)
 __global__ void __launch_bounds__(FR_BLOCK) resize_tokens_backward_kernel(int C, int Hs, int Ws, int Hd, int Wd, const float* __restrict__ g,
                                                                           float* __restrict__ grad_in) {
     __shared__ float tile[RS_TC * (RS_TP + 1)];
@@ -166,23 +157,7 @@ __global__ void __launch_bounds__(FR_BLOCK) resize_tokens_backward_kernel(int C,
         if (c0 + cl < C)
             for (int sl = threadIdx.x / RS_TC; sl < RS_TP && s0 + sl < Ps; sl += FR_BLOCK / RS_TC) {
                 const int ys = (s0 + sl) / Ws, xs = (s0 + sl) - ys * Ws;
-                int ylo, yhi, xlo, xhi;
-                resize_candidates(sh, ys, Hd, ylo, yhi);
-                resize_candidates(sw, xs, Wd, xlo, xhi);
-                double acc = 0.0;
-                for (int yd = ylo; yd <= yhi; ++yd) {
-                    int y0, y1, x0, x1;
-                    double ly, lx;
-                    resize_src(sh, yd, Hs, y0, y1, ly);
-                    const double wy = (y0 == ys ? 1.0 - ly : 0.0) + (y1 == ys ? ly : 0.0);
-                    if (y0 != ys && y1 != ys) continue;
-                    for (int xd = xlo; xd <= xhi; ++xd) {
-                        resize_src(sw, xd, Ws, x0, x1, lx);
-                        if (x0 != xs && x1 != xs) continue;
-                        const double wx = (x0 == xs ? 1.0 - lx : 0.0) + (x1 == xs ? lx : 0.0);
-                        acc += wy * wx * (double)g[(size_t)(yd * Wd + xd) * C + c0 + cl];
-                    }
-                }
+                const double acc = resize_gather(sh, sw, ys, xs, Hs, Ws, Hd, Wd, [&](int pd) { return g[(size_t)pd * C + c0 + cl]; });
                 tile[cl * (RS_TP + 1) + sl] = (float)acc;
             }
     }

@@ -301,6 +301,11 @@ SIGNATURES.update({
     # ABI 0.7.0, fourth set: the image backbone's inference forward on token rows
     "dr_conv2d_rows_f32": (c_int, [c_int] * 8 + [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
     "dr_resize_rows_f32": (c_int, [c_int] * 5 + [c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    # ABI 0.7.0, fifth set: the image backbone's backward on token rows
+    "dr_conv2d_rows_backward_data_f32": (c_int, [c_int] * 8 + [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
+    "dr_conv2d_rows_backward_weight_workspace_bytes": (c_size_t, [c_int] * 8),
+    "dr_conv2d_rows_backward_weight_f32": (c_int, [c_int] * 8 + [c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dr_resize_rows_backward_f32": (c_int, [c_int] * 5 + [c_void_p, c_int, c_void_p, c_int, c_void_p]),
 })
 
 
@@ -1623,6 +1628,86 @@ def resize_rows(x, src_size, size, addend=None, out=None):
     rawp = lambda t_: None if t_ is None else c_void_p(t_.data_ptr())
     check(_lib.dr_resize_rows_f32(C, Hs, Ws, Hd, Wd, rawp(x), x.stride(0), rawp(addend), addend.stride(0) if addend is not None else 0, rawp(out),
                                   out.stride(0), stream_of(x)))
+    return out
+
+
+def pack_conv_weight_t(weight):
+    """nn.Conv2d weight [Cout, Cin, k, k] -> the packed [Cin, k k Cout] (tap-major, co-minor) dr_conv2d_rows_backward_data_f32 reads"""
+    Cout, Cin, kh, kw = weight.shape
+    if kh != kw:
+        raise NotImplementedError("libdiffreg_hip: conv2d_rows takes square kernels (got %d x %d)" % (kh, kw))
+    return weight.detach().float().permute(1, 2, 3, 0).reshape(Cin, kh * kw * Cout).contiguous()
+
+
+def conv_wgrad_slabs(M):
+    """(S, L): the slabs of output pixels dr_conv2d_rows_backward_weight_f32 reduces over (conv_index.h: conv_wgrad_slabs) -- a function of
+    M = Ho Wo alone: S0 = min(64, ceil(M / 2048)), L = ceil(M / S0) rounded up to 32, S = ceil(M / L)"""
+    s0 = max(1, min(64, -(-M // 2048)))
+    L = max(32, -(-(-(-M // s0)) // 32) * 32)
+    return max(1, -(-M // L)), L
+
+
+def conv_wgrad_workspace_bytes(M, Cout, K):
+    """the workspace of dr_conv2d_rows_backward_weight_f32: float32 partials [S, Cout, K] rounded up to 8 bytes, double partials [S, Cout]"""
+    S, _ = conv_wgrad_slabs(M)
+    return (S * Cout * K * 4 + 7) // 8 * 8 + S * Cout * 8
+
+
+def _rawp(t_):
+    return None if t_ is None else c_void_p(t_.data_ptr())
+
+
+def conv2d_rows_backward_data(grad_out, size, w_packed_t, k, stride=1, padding=0, dilation=1, addend=None, out=None):
+    """grad_out [Ho*Wo, Cout] rows of the convolution of a size = (Hi, Wi) image, w_packed_t from pack_conv_weight_t -> grad_x [Hi*Wi, Cin]
+    (+ addend), every element written   (dr_conv2d_rows_backward_data_f32)"""
+    ensure_init()
+    Hi, Wi = int(size[0]), int(size[1])
+    Cout, Cin = grad_out.shape[1], w_packed_t.shape[0]
+    Ho, Wo = conv_out_size(Hi, k, stride, padding, dilation), conv_out_size(Wi, k, stride, padding, dilation)
+    if grad_out.shape[0] != Ho * Wo or w_packed_t.shape[1] != k * k * Cout or (Cout > 1 and grad_out.stride(1) != 1):
+        raise ValueError("conv2d_rows_backward_data: grad_out %s / weight %s do not fit a %d x %d image and a %d x %d kernel"
+                         % (tuple(grad_out.shape), tuple(w_packed_t.shape), Hi, Wi, k, k))
+    if out is None:
+        out = torch.empty(Hi * Wi, Cin, device=grad_out.device)
+    check(_lib.dr_conv2d_rows_backward_data_f32(Hi, Wi, Cin, Cout, k, stride, padding, dilation, _rawp(grad_out), grad_out.stride(0), ptr(w_packed_t),
+                                                _rawp(addend), addend.stride(0) if addend is not None else 0, _rawp(out), out.stride(0),
+                                                stream_of(grad_out)))
+    return out
+
+
+def conv2d_rows_backward_weight(x, size, grad_out, k, stride=1, padding=0, dilation=1, need_weight=True, need_bias=True, packed=False):
+    """x [Hi*Wi, Cin], grad_out [Ho*Wo, Cout] rows -> (grad_weight in the module's layout [Cout, Cin, k, k] -- or packed [Cout, k k Cin] with
+    packed=True -- or None, grad_bias [Cout] or None)   (dr_conv2d_rows_backward_weight_f32)"""
+    ensure_init()
+    Hi, Wi = int(size[0]), int(size[1])
+    Cin, Cout = x.shape[1], grad_out.shape[1]
+    Ho, Wo = conv_out_size(Hi, k, stride, padding, dilation), conv_out_size(Wi, k, stride, padding, dilation)
+    if x.shape[0] != Hi * Wi or grad_out.shape[0] != Ho * Wo or (Cin > 1 and x.stride(1) != 1) or (Cout > 1 and grad_out.stride(1) != 1):
+        raise ValueError("conv2d_rows_backward_weight: x %s / grad_out %s do not fit a %d x %d image and a %d x %d kernel"
+                         % (tuple(x.shape), tuple(grad_out.shape), Hi, Wi, k, k))
+    dev = x.device
+    gw = torch.empty(Cout, k * k * Cin, device=dev) if need_weight else None
+    gb = torch.empty(Cout, device=dev) if need_bias else None
+    wsb = _lib.dr_conv2d_rows_backward_weight_workspace_bytes(Hi, Wi, Cin, Cout, k, stride, padding, dilation)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    check(_lib.dr_conv2d_rows_backward_weight_f32(Hi, Wi, Cin, Cout, k, stride, padding, dilation, _rawp(x), x.stride(0), _rawp(grad_out),
+                                                  grad_out.stride(0), ptr(gw), ptr(gb), ptr(ws), wsb, stream_of(x)))
+    if gw is not None and not packed:
+        gw = gw.view(Cout, k, k, Cin).permute(0, 3, 1, 2).contiguous()
+    return gw, gb
+
+
+def resize_rows_backward(grad_out, src_size, size, out=None):
+    """grad_out [Hd*Wd, C] rows -> the gradient [Hs*Ws, C] of resize_rows' input; a gather, every element written   (dr_resize_rows_backward_f32)"""
+    ensure_init()
+    Hs, Ws = int(src_size[0]), int(src_size[1])
+    Hd, Wd = int(size[0]), int(size[1])
+    C = grad_out.shape[1]
+    if grad_out.shape[0] != Hd * Wd or (C > 1 and grad_out.stride(1) != 1):
+        raise ValueError("resize_rows_backward: grad_out %s is not a %d x %d image of rows" % (tuple(grad_out.shape), Hd, Wd))
+    if out is None:
+        out = torch.empty(Hs * Ws, C, device=grad_out.device)
+    check(_lib.dr_resize_rows_backward_f32(C, Hs, Ws, Hd, Wd, _rawp(grad_out), grad_out.stride(0), _rawp(out), out.stride(0), stream_of(grad_out)))
     return out
 
 

@@ -62,13 +62,18 @@ feature-layout calls (:374-375, :535-538) are inline `F.` code and take a one-li
 With `image_backbone=True` (any combination of the flags above) the image backbone's INFERENCE forward (`self.img_backbone(image, dino)`,
 EXP/model.py:358-361; EXP/image_backbone.py:254-289) runs on the device (diffreg_hip/image_backbone2d3d.py: NHWC token rows, the implicit-GEMM
 convolution and the row resample of csrc/conv2d.hip, the point backbone's GroupNorm entries): `img_backbone.forward` is re-bound on the instance and
-`remove()` restores it.  Under model.train() or with gradients enabled the bound forward calls the module's own code unchanged (there is no
-device backward).  The flag is opt-in and defaults off.
+`remove()` restores it.  Under model.train() or with gradients enabled the bound forward calls the module's own code unchanged.  The flag is
+opt-in and defaults off.
 
     accelerate(model, image_backbone=True)
 
-What then stays the reference's code in a training step: the image backbone (its device form is inference-only; DINOv2 / Depth-Anything are
-frozen third-party networks and stay out), the inline GT retry ladder and the other inline glue of MATR2D3D.forward.
+With `image_backbone_grad=True` (implies image_backbone=True) the device path also runs under model.train() and with gradients enabled, and its
+backward (the convolution's two gradients, the resample's gather, the GroupNorm backward) fills the .grad of img_backbone's own parameters.
+
+    accelerate(model, training=True, backbone=True, noising=True, image_backbone_grad=True)
+
+What then stays the reference's code in a training step: DINOv2 / Depth-Anything (frozen third-party networks), the inline GT retry ladder and
+the other inline glue of MATR2D3D.forward.
 """
 import sys
 import types
@@ -81,19 +86,20 @@ from .engine import DenoiseEngine2D3D
 
 class LoopOverlay2D3D:
     def __init__(self, model, n_head=4, engine_kwargs=None, training=False, partition=False, backbone=False, noising=False, front=False,
-                 image_backbone=False):
+                 image_backbone=False, image_backbone_grad=False):
         self.model = model
         self.training = bool(training)
         self.partition = bool(partition)
         self.backbone = bool(backbone)
         self.noising = bool(noising)
         self.front = bool(front)
-        self.image_backbone = bool(image_backbone)
+        self.image_backbone_grad = bool(image_backbone_grad)
+        self.image_backbone = bool(image_backbone) or self.image_backbone_grad
         if self.noising and not self.training:
             raise ValueError("noising=True is the training branch's front end: it needs training=True")
         if self.image_backbone:             # first: a module without a device form raises NotImplementedError here, before any site is bound
             from . import image_backbone2d3d
-            self.image_backbone_device = image_backbone2d3d.bind(model.img_backbone)
+            self.image_backbone_device = image_backbone2d3d.bind(model.img_backbone, grad=self.image_backbone_grad)
         self._globals_saved = {}
         self.n_head = n_head
         self.engine_kwargs = dict(engine_kwargs or {})
@@ -259,7 +265,7 @@ class LoopOverlay2D3D:
 
 
 def accelerate(model, n_head=4, training=False, partition=False, backbone=False, noising=False, front=False, image_backbone=False,
-               **engine_kwargs):
+               image_backbone_grad=False, **engine_kwargs):
     """install the overlay on a MATR2D3D instance (see the module docstring); returns the LoopOverlay2D3D (`.remove()` undoes it).
     training=True: the training branch's four coarse modules run on the device under model.train() as well.
     partition=True: the patch partition and GT patch overlaps (and, with training, the GT search) run on the device as well.
@@ -267,9 +273,10 @@ def accelerate(model, n_head=4, training=False, partition=False, backbone=False,
     noising=True (with training=True): the GT ladder's Procrustes fits, q_sample and the warp run on the device under model.train(), and the
     warp's gradient reaches denoising_coarse_matching.bin_score.
     front=True: back_project, render, create_meshgrid (globals of the model's module) and back_project_depth (the instance) run on the device.
-    image_backbone=True: model.img_backbone's inference forward runs on the device (eval mode under torch.no_grad(); otherwise its own code)."""
+    image_backbone=True: model.img_backbone's inference forward runs on the device (eval mode under torch.no_grad(); otherwise its own code).
+    image_backbone_grad=True (implies image_backbone): the device path also runs in training mode and with gradients enabled, with its backward."""
     return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs, training=training, partition=partition, backbone=backbone,
-                           noising=noising, front=front, image_backbone=image_backbone)
+                           noising=noising, front=front, image_backbone=image_backbone, image_backbone_grad=image_backbone_grad)
 
 
 def accelerate_loss(loss_module, fine=False):

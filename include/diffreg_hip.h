@@ -53,7 +53,10 @@ extern "C" {
  *          dr_rows_normalize_chw_backward_rows_f32 (new entries only; nothing older changed).
  *   0.7.0, third set (same rule)  dr_rotary_planes_f32: the rotary + image tail of a DR_PL_PLANES launch on its own (new entry only).
  *   0.7.0, fourth set (same rule: a minor bump was asked for, and the pinned 700 of that older check forbids it)  the 2D-3D image backbone's
- *          inference forward on token rows: dr_conv2d_rows_f32, dr_resize_rows_f32 (new entries only; nothing older changed). */
+ *          inference forward on token rows: dr_conv2d_rows_f32, dr_resize_rows_f32 (new entries only; nothing older changed).
+ *   0.7.0, fifth set (same rule)  the image backbone's backward on token rows: dr_conv2d_rows_backward_data_f32,
+ *          dr_conv2d_rows_backward_weight_f32 with dr_conv2d_rows_backward_weight_workspace_bytes, dr_resize_rows_backward_f32 (new entries
+ *          only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1098,6 +1101,33 @@ int dr_conv2d_rows_f32(int Hi, int Wi, int Cin, int Cout, int k, int stride, int
                        const float* weight, const float* bias, const float* addend, int lda, float* out, int ldo, void* stream);
 int dr_resize_rows_f32(int C, int Hs, int Ws, int Hd, int Wd, const float* in, int ldi, const float* addend, int lda, float* out, int ldo,
                        void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * ABI 0.7.0, fifth set: the backward of the fourth set's two entries (csrc/conv2d.hip, csrc/conv_index.h, csrc/resize_index.h).
+ * The forward's rules hold: token rows [H W, C] float32 with leading dimensions, nothing synchronises, nothing allocates, no atomics (two runs
+ * are bit-equal), DR_EINVAL / DR_ENOSUP before any launch for the forward entry's domain (and k k Cout <= 2^20), and EVERY element of every
+ * output is written -- zeros where no gradient arrives.
+ *
+ * dr_conv2d_rows_backward_data_f32: grad_out [Ho Wo, ldg] -> grad_x [Hi Wi, ldgx] (+ addend [Hi Wi, lda] or NULL, added last).  weight_t is
+ *   PACKED [Cin, k k Cout], tap-major and co-minor (the module's [Cout, Cin, k, k] permuted to [Cin, k, k, Cout]).  Cout % 4 == 0: the forward's
+ *   implicit GEMM with the roles turned (m = input pixel, N = Cin, kk = (tap, co)); a slot whose tap has no output pixel -- the padding, or a
+ *   position the stride skips -- loads nothing and is zero.  Other Cout: a direct kernel, double accumulation in a fixed order.
+ * dr_conv2d_rows_backward_weight_f32: x [Hi Wi, ldx], grad_out [Ho Wo, ldg] -> grad_w PACKED [Cout, k k Cin] as the forward's weight, and
+ *   grad_bias [Cout]; either may be NULL.  The Ho Wo output pixels are reduced in S slabs of L pixels, S and L functions of Ho Wo alone
+ *   (S0 = min(64, ceil(M / 2048)), L = ceil(M / S0) rounded up to 32, S = ceil(M / L)): float32 partial sums per slab in the workspace, added in
+ *   ascending slab order in double and rounded once.  Cin % 4 == 0: an MFMA kernel; other Cin: a direct kernel over the same slabs.  The
+ *   workspace holds dr_conv2d_rows_backward_weight_workspace_bytes(...) bytes (0 for arguments outside the domain: a pure host call) and is
+ *   16-byte aligned.
+ * dr_resize_rows_backward_f32: grad_out [Hd Wd, ldg] -> grad_in [Hs Ws, ldgi], the backward of dr_resize_rows_f32 with respect to `in` (the
+ *   addend's gradient is grad_out itself).  A gather: every source texel sums its destination pixels in a fixed order, through the statement
+ *   dr_resize_tokens_backward_f32 uses -- the two agree bit for bit. */
+int dr_conv2d_rows_backward_data_f32(int Hi, int Wi, int Cin, int Cout, int k, int stride, int padding, int dilation, const float* grad_out, int ldg,
+                                     const float* weight_t, const float* addend, int lda, float* grad_x, int ldgx, void* stream);
+size_t dr_conv2d_rows_backward_weight_workspace_bytes(int Hi, int Wi, int Cin, int Cout, int k, int stride, int padding, int dilation);
+int dr_conv2d_rows_backward_weight_f32(int Hi, int Wi, int Cin, int Cout, int k, int stride, int padding, int dilation, const float* x, int ldx,
+                                       const float* grad_out, int ldg, float* grad_w, float* grad_bias, void* workspace, size_t workspace_bytes,
+                                       void* stream);
+int dr_resize_rows_backward_f32(int C, int Hs, int Ws, int Hd, int Wd, const float* grad_out, int ldg, float* grad_in, int ldgi, void* stream);
 
 #ifdef __cplusplus
 }
