@@ -1182,6 +1182,11 @@ static int g_flash_min = -1;    // tests / tools: force the flash form from this
 static int g_attn_split = -1;   // tests / tools: 0 = f32-input MFMA flash kernel, 1 = split-operand one (-1 = default)
 void attention_force_flash_min(int n) { g_flash_min = n; }
 void attention_force_split(int on) { g_attn_split = on; }
+// tests: the form the last launch_attention of this thread launched (DR_ATTN_FORM_* of diffreg_hip_debug.h; 0 = it launched nothing)
+static thread_local int g_last_form = 0;
+int attention_last_form() { return g_last_form; }
+template <int DG>
+static inline void note_form(int form) { g_last_form = form | (DG << DR_ATTN_FORM_GEOM_SHIFT); }
 
 template <int DG, int NDT>
 static int launch_attn(const AttnArgs& a, hipStream_t st) {
@@ -1211,6 +1216,7 @@ static int launch_attn(const AttnArgs& a, hipStream_t st) {
         // profiles/r06_cfg3_experiments.json).  DR_ATTN_KG2=0 (diagnostics) switches it off.
         const int minLk = a.nseg2 > 0 && a.Lkb < a.Lk ? a.Lkb : a.Lk;
         const bool kg2 = (long)fgrid.x * fgrid.y * fgrid.z <= (long)device_cu_count() && minLk >= 128 && env_knob("DR_ATTN_KG2", 1) != 0;
+        note_form<DG>((kg2 ? DR_ATTN_FORM_PLANES_KG2 : DR_ATTN_FORM_PLANES_KG1) | (a.f16_single ? DR_ATTN_FORM_F16 : 0) | (ax.xcd_groups ? DR_ATTN_FORM_XCD : 0));
         if (kg2) {
             const size_t plds2 = AttnPlGeom<KS, NDT>::SMEM2;
             if (a.f16_single) hipLaunchKernelGGL((attention_planes_kernel<KS, NDT, true, 2>), fgrid, dim3(512), plds2, st, ax);
@@ -1229,12 +1235,14 @@ static int launch_attn(const AttnArgs& a, hipStream_t st) {
             constexpr int KS = (DG * 8 + 15) / 16;
             using SG = FlashSplitGeom<KS, NDT>;
             const size_t slds = (size_t)SG::SMEM;
+            note_form<DG>(DR_ATTN_FORM_FLASH_SPLIT);
             hipLaunchKernelGGL((attention_flash_split_kernel<KS, NDT>), fgrid, dim3(256), slds, st, a);
             DR_LAUNCH_CHECK();
             return DR_OK;
         }
         using FG = FlashGeom<DG, NDT>;
         const size_t flds = (size_t)FG::SMEM_FLOATS * sizeof(float);
+        note_form<DG>(DR_ATTN_FORM_FLASH_F32);
         hipLaunchKernelGGL((attention_flash_kernel<DG, NDT>), fgrid, dim3(256), flds, st, a);
         DR_LAUNCH_CHECK();
         return DR_OK;
@@ -1246,17 +1254,20 @@ static int launch_attn(const AttnArgs& a, hipStream_t st) {
         const int w8_env = env_knob("DR_ATTN_W8_MAX", 256);
         const int maxLk = a.nseg2 > 0 && a.Lkb > a.Lk ? a.Lkb : a.Lk;
         if ((int)(grid.x * grid.y * grid.z) <= w8_env && maxLk > 4 * 32) {
+            note_form<DG>(DR_ATTN_FORM_Q32_W8);
             hipLaunchKernelGGL((attention_kernel<DG, NDT, 8>), grid, dim3(512), lds8, st, a);
             DR_LAUNCH_CHECK();
             return DR_OK;
         }
     }
+    note_form<DG>(DR_ATTN_FORM_Q32_W4);
     hipLaunchKernelGGL((attention_kernel<DG, NDT>), grid, dim3(256), lds, st, a);
     DR_LAUNCH_CHECK();
     return DR_OK;
 }
 
 int launch_attention(const AttnArgs& a, hipStream_t st) {
+    g_last_form = 0;
     if (a.d % 4 || (!a.qimg[0] && (a.ldq % 4 || a.ldk % 4 || a.ldv % 4))) return DR_ENOSUP;
     if (a.nseg + a.nseg2 <= 0) return DR_OK;
     if (a.d <= 64) return launch_attn<8, 2>(a, st);       // 2D-3D: d = 64
@@ -1266,6 +1277,7 @@ int launch_attention(const AttnArgs& a, hipStream_t st) {
         using G = AttnGeom<20, 5>;
         static_assert(G::SMEM_FLOATS * sizeof(float) <= 160 * 1024, "LDS of the d <= 160 geometry");
         const int maxLq = a.nseg2 > 0 && a.Lqb > a.Lq ? a.Lqb : a.Lq;
+        note_form<20>(DR_ATTN_FORM_Q32_W4);
         hipLaunchKernelGGL((attention_kernel<20, 5>), dim3((maxLq + 31) / 32, a.H, a.nseg + a.nseg2), dim3(256), G::SMEM_FLOATS * sizeof(float), st, a);
         DR_LAUNCH_CHECK();
         return DR_OK;

@@ -87,6 +87,8 @@ int launch_attention(const AttnArgs& a, hipStream_t st);
 int attention_configure();
 void attention_force_flash_min(int n);
 void attention_force_split(int on);
+// which kernel form the last launch_attention of this thread launched (host bookkeeping for the tests; DR_ATTN_FORM_* of diffreg_hip_debug.h)
+int attention_last_form();
 
 // ---------------------------------------------------------------------------------------------
 // row-wise ops

@@ -50,6 +50,25 @@ int dr_debug_gemm_f32(const dr_debug_gemm_problem* problems, int n, void* stream
 void dr_debug_attention_config(int flash_min_workgroups);
 /* flash attention arithmetic: 1 = split-operand bf16 MFMA products (default), 0 = f32-input MFMA, -1 = default */
 void dr_debug_attention_split(int on);
+/* which kernel form the last attention launch of the calling thread chose (dr_attention_f32, dr_attention_planes[_f16], the attention launches
+ * inside a layer or loop call): set on the host just before the kernel launch, 0 before any launch and after a call that launched nothing
+ * (an argument the dispatcher refused, zero segments).
+ *   bits 0..3   the form: 1 the 32-query kernel with 4 waves, 2 the 32-query kernel with 8 waves, 3 the 128-query flash kernel on the f32-input
+ *               MFMA, 4 the flash kernel on split bf16 operands, 5 the plane-image kernel with one key group, 6 the one with two key groups
+ *   bit 4       plane-image forms: ONE fp16 product per contraction (dr_attention_planes_f16)
+ *   bit 5       plane-image forms: the XCD dealing of the workgroups is on
+ *   bits 8..15  the head-dim geometry's count of 8-column groups: 8 (d <= 64), 14 (d <= 112), 17 (d <= 136), 20 (d <= 160) */
+#define DR_ATTN_FORM_Q32_W4 1
+#define DR_ATTN_FORM_Q32_W8 2
+#define DR_ATTN_FORM_FLASH_F32 3
+#define DR_ATTN_FORM_FLASH_SPLIT 4
+#define DR_ATTN_FORM_PLANES_KG1 5
+#define DR_ATTN_FORM_PLANES_KG2 6
+#define DR_ATTN_FORM_MASK 0xf
+#define DR_ATTN_FORM_F16 0x10
+#define DR_ATTN_FORM_XCD 0x20
+#define DR_ATTN_FORM_GEOM_SHIFT 8
+int dr_debug_attention_last_form(void);
 /* polls before a workgroup of the single-launch Sinkhorn gives up waiting for the others (0 = the default, 2^22); the timeout test
  * sets 1 so that the first failed poll already gives up (tests/test_errors_gpu.py) */
 void dr_debug_sinkhorn_spin_limit(unsigned polls);
