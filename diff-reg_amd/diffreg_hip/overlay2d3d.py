@@ -72,8 +72,18 @@ backward (the convolution's two gradients, the resample's gather, the GroupNorm 
 
     accelerate(model, training=True, backbone=True, noising=True, image_backbone_grad=True)
 
-What then stays the reference's code in a training step: DINOv2 / Depth-Anything (frozen third-party networks), the inline GT retry ladder and
-the other inline glue of MATR2D3D.forward.
+With `dino=True` (any combination of the flags above) the frozen DINOv2 ViT-L/14 that produces `img_feats_x_dino` (EXP/model.py:354-358,
+EXP/encoders.py:107-119: `self.encoder.dinov2_vitl14[0].forward_features`) runs on the device in the reference's own fp16 arithmetic
+(diffreg_hip/vit2d3d.py, csrc/vit.hip: fp16 MFMA GEMMs with fp32 accumulation, an fp32 residual stream, fp16 flash attention):
+`forward_features` is re-bound on the ViT instance and `remove()` restores it.  It runs in eval and in training, with or without gradients
+enabled (the reference wraps the call in torch.no_grad() and the network is frozen).  A ViT the kernels do not cover (not fp16, SwiGLU, a head
+dim other than 64, ...) raises NotImplementedError here, before any site is bound.  The flag is opt-in and defaults off.
+
+    accelerate(model, dino=True)
+
+What then stays the reference's code in a training step: Depth-Anything (the same ViT class run in fp32, and its DPT head), the encoder's CNN
+branch (`encoder.cnn`, whose outputs MATR2D3D.forward discards) and `dino_2_u`, the inline GT retry ladder and the other inline glue of
+MATR2D3D.forward.
 """
 import sys
 import types
@@ -86,8 +96,9 @@ from .engine import DenoiseEngine2D3D
 
 class LoopOverlay2D3D:
     def __init__(self, model, n_head=4, engine_kwargs=None, training=False, partition=False, backbone=False, noising=False, front=False,
-                 image_backbone=False, image_backbone_grad=False):
+                 image_backbone=False, image_backbone_grad=False, dino=False):
         self.model = model
+        self.dino = bool(dino)
         self.training = bool(training)
         self.partition = bool(partition)
         self.backbone = bool(backbone)
@@ -100,6 +111,9 @@ class LoopOverlay2D3D:
         if self.image_backbone:             # first: a module without a device form raises NotImplementedError here, before any site is bound
             from . import image_backbone2d3d
             self.image_backbone_device = image_backbone2d3d.bind(model.img_backbone, grad=self.image_backbone_grad)
+        if self.dino:                       # likewise: refuses before any site is bound
+            from . import vit2d3d
+            self.dino_binding = vit2d3d.bind(model.encoder)
         self._globals_saved = {}
         self.n_head = n_head
         self.engine_kwargs = dict(engine_kwargs or {})
@@ -161,6 +175,8 @@ class LoopOverlay2D3D:
             sites += [(m, "back_project_depth")]
         if self.image_backbone:
             sites += [(m.img_backbone, "forward")]
+        if self.dino:
+            self.dino_binding.remove()
         for obj, name in sites:
             if name in obj.__dict__:
                 del obj.__dict__[name]
@@ -265,7 +281,7 @@ class LoopOverlay2D3D:
 
 
 def accelerate(model, n_head=4, training=False, partition=False, backbone=False, noising=False, front=False, image_backbone=False,
-               image_backbone_grad=False, **engine_kwargs):
+               image_backbone_grad=False, dino=False, **engine_kwargs):
     """install the overlay on a MATR2D3D instance (see the module docstring); returns the LoopOverlay2D3D (`.remove()` undoes it).
     training=True: the training branch's four coarse modules run on the device under model.train() as well.
     partition=True: the patch partition and GT patch overlaps (and, with training, the GT search) run on the device as well.
@@ -274,9 +290,11 @@ def accelerate(model, n_head=4, training=False, partition=False, backbone=False,
     warp's gradient reaches denoising_coarse_matching.bin_score.
     front=True: back_project, render, create_meshgrid (globals of the model's module) and back_project_depth (the instance) run on the device.
     image_backbone=True: model.img_backbone's inference forward runs on the device (eval mode under torch.no_grad(); otherwise its own code).
-    image_backbone_grad=True (implies image_backbone): the device path also runs in training mode and with gradients enabled, with its backward."""
+    image_backbone_grad=True (implies image_backbone): the device path also runs in training mode and with gradients enabled, with its backward.
+    dino=True: the frozen DINOv2 ViT of model.encoder (dinov2_vitl14[0].forward_features) runs on the device in fp16, in eval and in training."""
     return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs, training=training, partition=partition, backbone=backbone,
-                           noising=noising, front=front, image_backbone=image_backbone, image_backbone_grad=image_backbone_grad)
+                           noising=noising, front=front, image_backbone=image_backbone, image_backbone_grad=image_backbone_grad,
+                           dino=dino)
 
 
 def accelerate_loss(loss_module, fine=False):

@@ -1129,6 +1129,97 @@ int dr_conv2d_rows_backward_weight_f32(int Hi, int Wi, int Cin, int Cout, int k,
                                        void* stream);
 int dr_resize_rows_backward_f32(int C, int Hs, int Ws, int Hd, int Wd, const float* grad_out, int ldg, float* grad_in, int ldgi, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, sixth set (detected by symbol like the fourth and fifth sets): the frozen DINOv2 ViT encoder of the 2D-3D model in the
+ * reference's own fp16 arithmetic (csrc/vit.hip, index arithmetic in csrc/vit_index.h).  fp16 operands, ONE fp16 MFMA product per MAC,
+ * fp32 accumulation; the residual stream is fp32.  Nothing synchronises, nothing allocates, no atomics and no split-k: two runs are bit-equal.
+ * Every pointer below is device memory unless said otherwise; "fp16 rows" are IEEE half rows with a leading dimension in elements.
+ *
+ * dr_pack_weight_f16: an nn.Linear weight [N, K] fp16 (row stride ldw) -> the image dr_gemm_rows_f16 streams, K padded with zeros to
+ *   Kp = round_up(K, 32) (the patch embedding's flattened Conv2d weight: 588 -> 608); dr_pack_weight_f16_bytes(N, K) bytes, 16-byte aligned.
+ *   N % 16 == 0 (else DR_EINVAL / 0 bytes).
+ * dr_gemm_rows_f16: out = A W^T (+ bias), A [M, K] fp16 rows (lda >= K, lda % 8 == 0, 16-byte aligned), W packed with Kp == K.  nn.Linear of
+ *   layers/attention.py:52, :60 and layers/mlp.py:35-39, the Conv2d of layers/patch_embed.py:75.  M is ragged: rows past M are never read and
+ *   never stored.  K % 32 == 0 and N % 16 == 0, anything else is DR_EINVAL before any access.  bias fp32 [N] or NULL.  mode:
+ *     DR_GEMM_ROWS_F16             (acc + bias) * colscale for columns < colscale_cols (a multiple of 16; the q third of qkv takes d^-0.5,
+ *                                  layers/attention.py:54), rounded once to fp16 rows
+ *     DR_GEMM_ROWS_GELU_F16        exact erf GELU (nn.GELU() default) of acc + bias, rounded once to fp16 rows
+ *     DR_GEMM_ROWS_SCALE_RESID_F32 out[row] += gamma[col] * (acc + bias) on fp32 rows in place (gamma fp32 [N], NULL = 1): LayerScale and the
+ *                                  residual of layers/block.py:83-87
+ *     DR_GEMM_ROWS_F32             acc + bias (+ addend rows fp32 [M, ld_addend], or NULL) as fp32 rows
+ *   out, bias, gamma, addend 16-byte aligned, ldo and ld_addend multiples of 4.
+ * dr_layernorm_rows_f16: nn.LayerNorm(C, eps) over fp32 rows (layers/block.py:83, :86; dinov2.py:232): statistics in fp32, two passes;
+ *   out_f32 = 0: fp16 rows, 1: fp32 rows.  gamma / beta fp32 [C] or NULL.
+ * dr_attention_rows_f16: softmax(q k^T) v without a mask over packed qkv rows [L, 3 H d] fp16 in the layout of qkv.reshape(N, 3, H, d)
+ *   (layers/attention.py:49-62), q already scaled; out fp16 rows [L, H d].  Flash form, fp32 online softmax, P rounded to fp16 once.  d == 64 only
+ *   (else DR_EINVAL); ldqkv % 8 == 0, ldo % 4 == 0, qkv 16-byte and out 8-byte aligned.  Not a form of dr_attention_f32's dispatcher.
+ * dr_patch_rows_f16: the p x p patches of a [3, H, W] image (fp16, or fp32 with img_f32 = 1) as fp16 rows [(H / p)(W / p), ldo >= Kp], k in the
+ *   order of the flattened Conv2d weight, Kp = round_up(3 p p, 32), pad columns zero (layers/patch_embed.py:69-82).  H % p == W % p == 0.
+ * dr_vit_forward_f16: DinoVisionTransformer.forward_features of one image (dinov2.py:166-237): prepare_tokens_with_masks without masks, every
+ *   block (layers/block.py:82-107 in eval mode), the final norm.  Writes x_prenorm fp32 [L, D] (L = 1 + patches; it IS the residual stream),
+ *   x_norm fp16 [L, D], and the stream after block take[i] into take_out[i] (fp32 [L, D]) for get_intermediate_layers.  `blocks`, `take` and
+ *   `take_out` are HOST arrays read during the call; pos is the position rows [L, D] fp32 for this (H, W).  heads * 64 == D, Dh % 32 == 0.
+ *   The workspace holds dr_vit_workspace_bytes(H, W, p, D, Dh) bytes (0 outside the domain), 256-byte aligned; less is DR_EINVAL.  The size query
+ *   and the entry share one carve function.  It can be captured in a graph. */
+#define DR_GEMM_ROWS_F16 0
+#define DR_GEMM_ROWS_GELU_F16 1
+#define DR_GEMM_ROWS_SCALE_RESID_F32 2
+#define DR_GEMM_ROWS_F32 3
+typedef struct dr_gemm_rows_f16_args {
+    const void* a;                 /* [M, lda] fp16                                                                      */
+    const void* w_packed;          /* dr_pack_weight_f16 image of [N, K]                                                 */
+    const float* bias;             /* [N] or NULL                                                                        */
+    const float* gamma;            /* SCALE_RESID_F32: [N] or NULL                                                       */
+    const float* addend;           /* F32: [M, ld_addend] or NULL                                                        */
+    void* out;                     /* fp16 or fp32 rows [M, ldo]                                                         */
+    int M, K, N, lda, ldo, ld_addend;
+    int mode;                      /* DR_GEMM_ROWS_*                                                                     */
+    int colscale_cols;             /* F16: columns [0, colscale_cols) are multiplied by colscale                         */
+    float colscale;
+} dr_gemm_rows_f16_args;
+typedef struct dr_vit_block_f16 {
+    const float *norm1_g, *norm1_b;
+    const void* qkv_w;             /* packed [3 D, D]   */
+    const float* qkv_b;
+    const void* proj_w;            /* packed [D, D]     */
+    const float* proj_b;
+    const float* ls1;              /* LayerScale gamma [D] or NULL */
+    const float *norm2_g, *norm2_b;
+    const void* fc1_w;             /* packed [Dh, D]    */
+    const float* fc1_b;
+    const void* fc2_w;             /* packed [D, Dh]    */
+    const float* fc2_b;
+    const float* ls2;
+} dr_vit_block_f16;
+typedef struct dr_vit_config_f16 {
+    int H, W, p, D, heads, Dh, depth;
+    float eps;
+    const void* img;               /* [3, H, W] fp16, or fp32 with img_f32 = 1 */
+    int img_f32;
+    const void* patch_w;           /* packed [D, 3 p p] */
+    const float* patch_b;
+    const float* cls;              /* [D]               */
+    const float* pos;              /* [L, D]            */
+    const dr_vit_block_f16* blocks;/* HOST array [depth] */
+    const float *norm_g, *norm_b;
+    float* x_prenorm;              /* out fp32 [L, D]   */
+    void* x_norm;                  /* out fp16 [L, D]   */
+    int n_take;
+    const int* take;               /* HOST [n_take] block indices */
+    float* const* take_out;        /* HOST [n_take] device pointers, fp32 [L, D] each */
+    void* workspace;
+    size_t workspace_bytes;
+} dr_vit_config_f16;
+size_t dr_pack_weight_f16_bytes(int N, int K);
+int dr_pack_weight_f16(int N, int K, const void* w, int ldw, void* packed, void* stream);
+int dr_gemm_rows_f16(const dr_gemm_rows_f16_args* args, void* stream);
+int dr_layernorm_rows_f16(int rows, int C, const float* x, int ldx, const float* gamma, const float* beta, float eps, int out_f32, void* out, int ldo,
+                          void* stream);
+int dr_attention_rows_f16(int L, int H, int d, const void* qkv, int ldqkv, void* out, int ldo, void* stream);
+int dr_patch_rows_f16(int H, int W, int p, const void* img, int img_f32, void* out, int ldo, void* stream);
+size_t dr_vit_workspace_bytes(int H, int W, int p, int D, int Dh);
+int dr_vit_forward_f16(const dr_vit_config_f16* cfg, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

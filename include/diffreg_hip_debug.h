@@ -72,6 +72,9 @@ int dr_debug_attention_last_form(void);
 /* polls before a workgroup of the single-launch Sinkhorn gives up waiting for the others (0 = the default, 2^22); the timeout test
  * sets 1 so that the first failed poll already gives up (tests/test_errors_gpu.py) */
 void dr_debug_sinkhorn_spin_limit(unsigned polls);
+/* the workgroup tile of dr_gemm_rows_f16 (and of the GEMMs inside dr_vit_forward_f16): -1 the automatic rule (the largest tile that still gives
+ * every CU a workgroup), 0 / 1 / 2 force 64 x 64 / 128 x 64 / 128 x 128; any other value makes every launch DR_EINVAL */
+void dr_debug_gemm_rows_tile(int c);
 /* n dependent launches of an empty kernel (tools/launch_floor.py) */
 int dr_debug_launch_chain(int n, int workgroups, int threads, void* stream);
 
