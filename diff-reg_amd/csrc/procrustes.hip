@@ -5,8 +5,8 @@
 // One workgroup per pair:
 //   1. the tile (<= 256 x 256) is read once into registers as ordered keys; radix select (4 x 8-bit
 //      digits, run-length aggregated LDS atomics, parallel bin search) -> key of the K-th largest
-//   2. entries > tau, plus the first entries == tau in a fixed (thread, element) order (torch.sort is
-//      unstable, ties are unspecified upstream), feed the moment sums directly -- deterministic
+//   2. entries > tau, plus the entries == tau with the lowest flat indices (torch.sort is unstable, ties
+//      are unspecified upstream; include/diffreg_hip.h fixes them), feed the moment sums directly -- deterministic
 //   3. fp64 sums  W1 = sum|w|, sum w X, sum w Y, sum w Y X^T  ->  Sxy = sum w^ Y X^T - (2 - s) Ybar Xbar^T
 //      with w^ = w / (W1 + eps), s = sum w^  (identical to (Y - Ybar)^T (w^ (X - Xbar)), procrustes.py:27-33)
 //   4. one-sided Jacobi SVD, R = U diag(1,1,det U det V) V^T, t = Ybar - R Xbar, cond = Dmax / Dmin
@@ -56,6 +56,10 @@ __device__ __forceinline__ float key_value(unsigned k) {
 }
 
 constexpr int CAND_MAX = 4096;   // candidate list held in LDS
+
+// ties at the K-th value go to the lowest flat indices (include/diffreg_hip.h): a register-resident tile (e < 65536) ranks its tied
+// entries by this key -- lower index <=> larger key, never 0 -- with the two leading digits of radix_select
+__device__ __forceinline__ unsigned tie_key(int e) { return ((65535u - (unsigned)e) << 16) | 0xFFFFu; }
 
 // radix select over the keys enumerated by `for_each` (4 x 8-bit digits, run-length aggregated LDS
 // atomics, parallel bin search by wave 0): on return tau = key of the K-th largest, remaining = how
@@ -492,9 +496,9 @@ __global__ __launch_bounds__(1024) void procrustes_kernel(ProcArgs A) {
                 }
             }
             __syncthreads();
-        } else if (K <= 1024) {
-            // (threads whose slice is empty have tmax = 0 and are not enumerated; K <= #non-empty is
-            //  guaranteed when K <= min(NM, 1024) because slices are filled round-robin)
+        } else if (K <= 1024 && K <= (NM + 3) / 4) {
+            // (threads whose slice is empty have tmax = 0 and are not enumerated: a thread owns four consecutive elements, so
+            //  (NM + 3) / 4 threads are non-empty and K must not exceed that -- tiles with min(N, M) < 4 sample_rate go below)
             // L = the K-th largest thread maximum, all four digits (round 3: the 16-bit bucket of rounds 1-2 admitted the whole
             // near-uniform background of the sharp late-step matrices -- K-th falls into it as soon as two large entries share a
             // thread -- and sent the last four steps of every run to the 60 us dearer exact select below; +1.1 us here)
@@ -511,8 +515,9 @@ __global__ __launch_bounds__(1024) void procrustes_kernel(ProcArgs A) {
             }
             __syncthreads();
         } else {
-            // K > 1024 (thin tiles such as 2048 x 2, or a large sample_rate): the per-thread maxima do not bound the K-th largest
-            // entry, so no candidate list is built -- take the full-tile radix path whatever the tile's size (without this the
+            // K > 1024 (thin tiles such as 2048 x 2, or a large sample_rate) or K beyond the number of threads that own elements (tiny
+            // tiles: the select over the maxima would be asked for more keys than it enumerates and leave L unset): the per-thread
+            // maxima do not bound the K-th largest entry, so no candidate list is built -- take the full-tile radix path whatever the tile's size (without this the
             // list would be read uninitialised when N M <= CAND_MAX)
             ncand = CAND_MAX + 1;
         }
@@ -567,6 +572,63 @@ __global__ __launch_bounds__(1024) void procrustes_kernel(ProcArgs A) {
             int off_g = block_excl_scan(cg, s_w, tg);
             int rank_e = block_excl_scan(ce, s_w, te);
             frem = (unsigned)(K - tg);
+            // more entries equal to the K-th value than the top K holds: the `frem` lowest flat indices among them are taken (the
+            // registers are in thread-major order, not index order, once a thread owns more than one key quad).  Element
+            // e = 4096 q + 4 t + c: index order is quad q first, then thread order.  ecut = one past the last tie taken.  Only tied
+            // tiles pay for it: one more pass over the keys (a bit per tie), the rest works on the thread's 64 bits.
+            int ecut = 0x7fffffff;
+            if (REG && te > (int)frem) {
+                unsigned mlo = 0, mhi = 0;                        // bit 4 q + c: key[4 q + c] is a tie
+#pragma unroll
+                for (int i = 0; i < 32; ++i) {
+                    mlo |= (key[REG ? i : 0] == ftau ? 1u : 0u) << i;
+                    mhi |= (key[REG ? 32 + i : 0] == ftau ? 1u : 0u) << i;
+                }
+                // (the compares above are not to be shared with the passes before and after: kept alive as lane masks they spill)
+#pragma unroll
+                for (int i = 0; i < 64; ++i) asm volatile("" : "+v"(key[REG ? i : 0]));
+                const unsigned long long m = ((unsigned long long)mhi << 32) | mlo;
+                unsigned* s_q = s_hist;                           // [16 waves][8]: ties of quads 2 j | 2 j + 1 << 16; block sums in s_ckey[0..7]
+#pragma unroll
+                for (int j = 0; j < 8; ++j) {
+                    const unsigned two = (unsigned)(m >> (8 * j)) & 0xFFu;
+                    const unsigned v = wave_sum((unsigned)__popc(two & 0xFu) | ((unsigned)__popc(two >> 4) << 16));
+                    if (lane == 0) s_q[w * 8 + j] = v;
+                }
+                __syncthreads();
+                if (t < 8) {
+                    unsigned v = 0;
+#pragma unroll
+                    for (int k2 = 0; k2 < 16; ++k2) v += s_q[k2 * 8 + t];
+                    s_ckey[t] = v;                                // (at most 4096 per quad: 16 bits hold it)
+                }
+                __syncthreads();
+                int qs = 0;                                       // the quad that holds the frem-th tie; `need` of its ties are taken
+                int need = (int)frem;
+#pragma unroll
+                for (int q = 0; q < 16; ++q) {
+                    const int c = (int)((s_ckey[q >> 1] >> (16 * (q & 1))) & 0xFFFFu);
+                    if (qs == q && need > c) { need -= c; qs = q + 1; }
+                }
+                const unsigned nib = (unsigned)(m >> (4 * qs)) & 0xFu;
+                const int cq = __popc(nib);
+                int tq;
+                const int base = block_excl_scan(cq, s_w, tq);
+                int mine = need - base;                           // ties of quad qs this thread contributes
+                mine = mine < 0 ? 0 : (mine > cq ? cq : mine);
+                if (base < need && need <= base + cq) {           // the thread that holds the last tie taken
+                    int seen = 0;
+#pragma unroll
+                    for (int c = 0; c < 4; ++c) {
+                        seen += (int)((nib >> c) & 1u);
+                        if (((nib >> c) & 1u) && seen == mine) s_pr[0] = (unsigned)(4096 * qs + 4 * t + c + 1);
+                    }
+                }
+                __syncthreads();
+                ecut = (int)s_pr[0];
+                const int cs = __popcll(m & ((1ull << (4 * qs)) - 1ull)) + mine;
+                rank_e = block_excl_scan(cs, s_w, te);
+            }
             // (the same element-to-thread assignment as the counts above: the registers' when REG)
             auto for_own = [&](auto&& f) {
                 if (REG) for_each(f);
@@ -575,10 +637,11 @@ __global__ __launch_bounds__(1024) void procrustes_kernel(ProcArgs A) {
             for_own([&](unsigned k, int e) {
                 if (k >= ftau && k != 0u) {                       // rare (K of the tile's entries) unless the tile is flat
                     const bool g = k > ftau;
+                    const bool tie = !g && e < ecut;
                     const int pos = g ? off_g : tg + rank_e;
-                    if (g || rank_e < (int)frem) { s_ckey[pos] = k; s_cidx[pos] = e; }
+                    if (g || (tie && rank_e < (int)frem)) { s_ckey[pos] = k; s_cidx[pos] = e; }
                     off_g += g ? 1 : 0;                           // (selects: incrementing one of two counters per branch sent both to scratch)
-                    rank_e += g ? 0 : 1;
+                    rank_e += tie ? 1 : 0;
                 }
             });
             ncand = K;                      // the list now holds exactly the top K: select all of it below
@@ -599,9 +662,18 @@ __global__ __launch_bounds__(1024) void procrustes_kernel(ProcArgs A) {
         });
         int tot_ties;
         int rank = block_excl_scan(ties, s_w, tot_ties);
+        // more ties than places: the list is in (thread, element) order and its entry c belongs to thread c % 1024, neither of which is
+        // index order -- take the `remaining` lowest flat indices (a branch that only tied tiles enter)
+        const bool excess = REG && tot_ties > (int)remaining;
+        unsigned itie = 0;
+        if (excess) {
+            unsigned one;
+            radix_select<2>([&](auto&& f) { for_cand([&](unsigned k, int e) { f(k == tau ? tie_key(e) : 0u, e); }); }, remaining, s_hist,
+                            s_pr, itie, one);
+        }
         for_cand([&](unsigned k, int e) {
             if (k == tau) {
-                if (rank < (int)remaining) take(k, e);
+                if (excess ? tie_key(e) >= itie : rank < (int)remaining) take(k, e);
                 ++rank;
             }
         });
@@ -711,10 +783,15 @@ size_t procrustes_workspace_bytes(int P, int N, int M) {
     return (size_t)P * (PC_CAP * 8 + S * PH_LAST * 8) + (((size_t)P * 4 + 255) & ~(size_t)255) + proc_zeroed_bytes(P) + 512;
 }
 
+// which launch form the calling thread's last launch_procrustes took (dr_debug_procrustes_last_form): -1 = none
+static thread_local int g_last_form = -1;
+int procrustes_last_form() { return g_last_form; }
+
 int launch_procrustes(const float* conf, const float* src_pcd, const float* tgt_pcd, const uint8_t* src_mask,
                       const uint8_t* tgt_mask, int P, int N, int M, int use_mask_len, float sample_rate, float max_cond,
                       float* R, float* t, float* Rf, float* tf, double* cond, int* ok, int* topk_idx, hipStream_t st,
                       void* ws, size_t ws_bytes) {
+    g_last_form = -1;
     if (P <= 0) return DR_OK;
     if ((long)N * M > 0x7fffffffL) return DR_ENOSUP;
     ProcArgs a;
@@ -729,6 +806,7 @@ int launch_procrustes(const float* conf, const float* src_pcd, const float* tgt_
     ProfScope ps(PK_PROCRUSTES, (double)P * N * M * 4.0, st);
     const long NM = (long)N * M;
     if (NM <= 65536) {
+        g_last_form = 0;
         hipLaunchKernelGGL(procrustes_kernel<true>, dim3(P), dim3(1024), 0, st, a);
     } else {
         if (ws && ws_bytes >= procrustes_workspace_bytes(P, N, M)) {
@@ -748,6 +826,7 @@ int launch_procrustes(const float* conf, const float* src_pcd, const float* tgt_
             DR_LAUNCH_CHECK();
             hipLaunchKernelGGL(proc_hist_kernel<2>, dim3(a.S, P), dim3(1024), 0, st, a);
             DR_LAUNCH_CHECK();
+            g_last_form = a.SL <= 32768 ? 1 : 2;
             if (a.SL <= 32768) hipLaunchKernelGGL(proc_take_kernel<true>, dim3(a.S, P), dim3(1024), 0, st, a);
             else hipLaunchKernelGGL(proc_take_kernel<false>, dim3(a.S, P), dim3(1024), 0, st, a);
             DR_LAUNCH_CHECK();

@@ -81,9 +81,18 @@ __device__ __forceinline__ void svd3_jacobi(double (&A)[3][3], double (&U)[3][3]
     swap_cols(A, V, S, 1, 2);
     const double tiny = 1e-200;
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+    for (int i = 0; i < 3; ++i) U[i][0] = S[0] > tiny ? A[i][0] / S[0] : (i == 0 ? 1.0 : 0.0);
+    if (S[1] > tiny) {
 #pragma unroll
-        for (int i = 0; i < 3; ++i) U[i][j] = S[j] > tiny ? A[i][j] / S[j] : (i == j ? 1.0 : 0.0);
+        for (int i = 0; i < 3; ++i) U[i][1] = A[i][1] / S[1];
+    } else {   // rank <= 1: the unit vector orthogonal to U[:,0] nearest the axis on which U[:,0] is smallest (e_1 would repeat U[:,0] when that is e_1)
+        const double a0 = fabs(U[0][0]), a1 = fabs(U[1][0]), a2 = fabs(U[2][0]);
+        const int k = (a0 < a1 && a0 <= a2) ? 0 : (a1 <= a2 ? 1 : 2);
+        const double uk = k == 0 ? U[0][0] : (k == 1 ? U[1][0] : U[2][0]);
+        const double inv = 1.0 / sqrt(1.0 - uk * uk);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) U[i][1] = ((i == k ? 1.0 : 0.0) - uk * U[i][0]) * inv;
+    }
     if (S[2] > 1e-14 * S[0] && S[2] > tiny) {
 #pragma unroll
         for (int i = 0; i < 3; ++i) U[i][2] = A[i][2] / S[2];

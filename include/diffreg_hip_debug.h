@@ -69,6 +69,15 @@ void dr_debug_attention_split(int on);
 #define DR_ATTN_FORM_XCD 0x20
 #define DR_ATTN_FORM_GEOM_SHIFT 8
 int dr_debug_attention_last_form(void);
+/* which launch form the last dr_procrustes_f32 of the calling thread (or the fit inside a loop call) took: set on the host just before the
+ * launches, -1 before any call and after a call that launched nothing (P = 0, DR_ENOSUP).
+ *   0  one workgroup per pair on a register-resident tile (N M <= 65536)
+ *   1  whole-chip sliced selection, the take pass keeps its slice's keys in registers (slices of at most 32768 entries)
+ *   2  whole-chip sliced selection, the take pass re-reads its keys (longer slices) */
+#define DR_PROC_FORM_REG 0
+#define DR_PROC_FORM_SLICED 1
+#define DR_PROC_FORM_SLICED_REREAD 2
+int dr_debug_procrustes_last_form(void);
 /* polls before a workgroup of the single-launch Sinkhorn gives up waiting for the others (0 = the default, 2^22); the timeout test
  * sets 1 so that the first failed poll already gives up (tests/test_errors_gpu.py) */
 void dr_debug_sinkhorn_spin_limit(unsigned polls);

@@ -205,8 +205,8 @@ def test_procrustes_thin_tile_more_than_1024_selected():
 def test_procrustes_large_tile_exact_selection(N, M, kind):
     """Tiles beyond 256 x 256 select their K entries with the whole chip (three digit-histogram passes + an ordered take pass,
     procrustes.hip).  Bit-exact index work: the selected VALUES are torch.topk's (procrustes.py:66), no index twice, and among the
-    entries equal to the K-th value the lowest indices are the ones taken (the rule the one-workgroup kernels follow; torch.topk
-    leaves it implementation-defined).  `quantised` (16 levels) and `flat` overflow any bounded candidate list; `sparse` has fewer
+    entries equal to the K-th value the lowest indices are the ones taken (the header's rule; torch.topk leaves it implementation-defined.
+    The one-workgroup kernel is held to the same rule in test_procrustes_paths_gpu.py: until then it ranked ties in thread order).  `quantised` (16 levels) and `flat` overflow any bounded candidate list; `sparse` has fewer
     non-zero entries than K."""
     from diffreg_hip import lib
     P = 2
