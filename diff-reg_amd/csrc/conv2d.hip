@@ -17,6 +17,14 @@
 //   dr_conv2d_rows_backward_weight_f32   dW[co][kk] = sum_m G[m][co] A[m][kk] over slabs of output pixels (a function of the shape alone): float32
 //                                        partial sums per slab, added in ascending order in double; grad_bias likewise; direct for Cin % 4 != 0
 //   dr_resize_rows_backward_f32          the gather of resize_index.h, shared with dr_resize_tokens_backward_f32
+//
+// The decoder of Depth-Anything (DPTHead.forward, depth_anything/dpt.py:103-136), the same MFMA kernel with an epilogue parameter and a
+// third slot map, the main loop untouched:
+//   dr_conv2d_rows_act_f32               out = relu?(conv(relu?(x)) + bias) + addend + addend2: the pre-activation ResidualConvUnit and the sum of a
+//                                        FeatureFusionBlock (depth_anything/blocks.py:69-92, :126-153) on the fetch and the store
+//   dr_conv_transpose2d_rows_f32         nn.ConvTranspose2d with kernel = stride (dpt.py:40-51): one GEMM over TransMap, the store a pixel shuffle
+//   dr_conv2d_rows_project_f32           conv -> ReLU -> 1 x 1 conv to one channel -> ReLU (dpt.py:95-99) in one launch: the hidden row of a pixel
+//                                        is summed inside the workgroup, in double, in a fixed order
 #include "kernels.h"
 #include "conv_index.h"
 #include "resize_index.h"
@@ -33,7 +41,18 @@ struct ConvArgs {
     const float* addend;   // [Ho Wo, lda] or nullptr
     float* out;            // [Ho Wo, ldo]
     int ldx, lda, ldo;
+    // the DPT head's epilogues (EP != CV_EP_PLAIN); zero elsewhere
+    int flags;             // DR_CONV_RELU_IN | DR_CONV_RELU_OUT
+    const float* addend2;  // [Ho Wo, lda2] or nullptr, added after addend
+    int lda2;
+    const float* w2;       // CV_EP_PROJECT: [Cmid]
+    const float* b2;       // CV_EP_PROJECT: [1] or nullptr
 };
+
+// the epilogue of conv2d_mfma_kernel.  PLAIN: + bias, + addend (every entry before the DPT head's; its code is what it was).  ACT: ReLU on A as
+// it is fetched, + bias, ReLU, + addend, + addend2 (dr_conv2d_rows_act_f32).  PROJECT: + bias, ReLU, the dot product with w2 over the
+// workgroup's columns, + b2, ReLU: one value per row (dr_conv2d_rows_project_f32).
+constexpr int CV_EP_PLAIN = 0, CV_EP_ACT = 1, CV_EP_PROJECT = 2;
 
 constexpr int CV_BKC = 32, CV_LDT = CV_BKC + 4, CV_C4 = CV_BKC / 4, CV_NT = 256;
 
@@ -48,6 +67,7 @@ struct FwdMap {
     static __device__ long long a(const ConvGeom& g, int m, int kk, int ld) { return conv_a_offset(g, m, kk, ld); }
     static __device__ long long b(const ConvGeom& g, int n, int kk) { return conv_w_offset(g, n, kk); }
     static __device__ long long o(const ConvGeom& g, int m, int n, int ld) { return conv_o_offset(g, m, n, ld); }
+    static __device__ int bias(const ConvGeom&, int n) { return n; }
 };
 struct BwdMap {
     static __device__ __host__ int rows(const ConvGeom& g) { return g.Hi * g.Wi; }
@@ -56,6 +76,18 @@ struct BwdMap {
     static __device__ long long a(const ConvGeom& g, int m, int kk, int ld) { return conv_bwd_a_offset(g, m, kk, ld); }
     static __device__ long long b(const ConvGeom& g, int n, int kk) { return conv_bwd_w_offset(g, n, kk); }
     static __device__ long long o(const ConvGeom& g, int m, int n, int ld) { return conv_bwd_o_offset(g, m, n, ld); }
+    static __device__ int bias(const ConvGeom&, int n) { return n; }
+};
+// TransMap: nn.ConvTranspose2d with kernel = stride (dr_conv_transpose2d_rows_f32): m = input pixel, n = (i, j, co), kk = ci; A = x, B = the weight
+// packed [s s Cout, Cin]; the store is a pixel shuffle and the bias is per co.
+struct TransMap {
+    static __device__ __host__ int rows(const ConvGeom& g) { return g.Hi * g.Wi; }
+    static __device__ __host__ int cols(const ConvGeom& g) { return conv_t_cols(g); }
+    static __device__ __host__ int depth(const ConvGeom& g) { return g.Cin; }
+    static __device__ long long a(const ConvGeom& g, int m, int kk, int ld) { return conv_t_a_offset(g, m, kk, ld); }
+    static __device__ long long b(const ConvGeom& g, int n, int kk) { return conv_t_w_offset(g, n, kk); }
+    static __device__ long long o(const ConvGeom& g, int m, int n, int ld) { return conv_t_o_offset(g, m, n, ld); }
+    static __device__ int bias(const ConvGeom& g, int n) { return conv_t_channel(g, n); }
 };
 
 // 2 x 2 waves, each TM x TN MFMA tiles of 32 x 32: a workgroup owns 64 TM output pixels x 64 TN output channels.  NBUF = 2: double-buffered LDS,
@@ -66,8 +98,9 @@ struct BwdMap {
 // ulp of the result (measured: 4.7e-7 of max|out| at K = 144, 2-3e-6 at K = 1 152 .. 4 608); windows of m terms leave sqrt(m) from the chains
 // plus one rounding per window.  FG = 1 (8 terms) for short sums, where a reference that rounds once leaves no room; FG = 4 (one k-chunk)
 // for long ones, where the adds would otherwise rival the MFMAs.  The order is fixed either way: two runs are bit-equal.
-template <class MAP, int TM, int TN, int NBUF, int FG, bool VEC>
+template <class MAP, int TM, int TN, int NBUF, int FG, bool VEC, int EP>
 __global__ __launch_bounds__(CV_NT) __attribute__((amdgpu_waves_per_eu(2))) void conv2d_mfma_kernel(ConvArgs P) {
+    static_assert(EP != CV_EP_PROJECT || TN == 1, "the project epilogue sums one 64-wide column tile");
     constexpr int BM = 64 * TM, BN = 64 * TN, STAGE = (BM + BN) * CV_LDT;
     constexpr int A_SLOTS = BM * CV_C4 / CV_NT, B_SLOTS = BN * CV_C4 / CV_NT;
     __shared__ __attribute__((aligned(16))) float smem[NBUF * STAGE];
@@ -89,11 +122,14 @@ __global__ __launch_bounds__(CV_NT) __attribute__((amdgpu_waves_per_eu(2))) void
         return make_float4(base[off], base[off + 1], base[off + 2], base[off + 3]);
     };
     float4 ra[A_SLOTS], rb[B_SLOTS];
+    const bool relu_in = EP == CV_EP_ACT && (P.flags & DR_CONV_RELU_IN);
     auto load_chunk = [&](int ch) {
 #pragma unroll
         for (int s = 0; s < A_SLOTS; ++s) {
             const int slot = t + s * CV_NT;
             ra[s] = fetch(px, MAP::a(g, row0 + slot / CV_C4, ch * CV_BKC + 4 * (slot % CV_C4), ldx));
+            if (EP == CV_EP_ACT && relu_in)                     // (a slot that loaded nothing is zero and stays zero)
+                ra[s] = make_float4(fmaxf(ra[s].x, 0.f), fmaxf(ra[s].y, 0.f), fmaxf(ra[s].z, 0.f), fmaxf(ra[s].w, 0.f));
         }
 #pragma unroll
         for (int s = 0; s < B_SLOTS; ++s) {
@@ -160,11 +196,56 @@ __global__ __launch_bounds__(CV_NT) __attribute__((amdgpu_waves_per_eu(2))) void
         __syncthreads();
     }
 
+    if (EP == CV_EP_PROJECT) {
+        // One value per output pixel: sum over the Cmid <= 64 columns of relu(acc + b1) w2.  A row's columns lie across the 32 lanes of a lane
+        // half of wave wn = 0 and, above 32, of wave wn = 1.  The products are formed in double (exact) and added in double: a butterfly over
+        // lane distances 16, 8, 4, 2, 1 (every lane of the half ends with the same bits), then wave 1's sum reaches wave 0 through LDS and the
+        // total is (s0 + s1) + b2, rounded once.  The order is fixed.  The staging buffers are free: the main loop ended on a barrier.
+        double* red = reinterpret_cast<double*>(smem);
+        const int col = wn * 32 + l31;                                    // tiles_n == 1: col0 == 0
+        const bool live = col < MAP::cols(g);
+        const float bv = (P.bias && live) ? P.bias[col] : 0.f;
+        const double w2 = live ? (double)P.w2[col] : 0.0;
+        double sum[TM][16];
+#pragma unroll
+        for (int i = 0; i < TM; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                double v = (double)fmaxf(tot[i][0][r] + bv, 0.f) * w2;
+#pragma unroll
+                for (int dist = 16; dist >= 1; dist >>= 1) v += __shfl_xor(v, dist);
+                sum[i][r] = v;
+            }
+        if (wn == 1 && l31 == 0) {
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) red[conv_tile_row(wm * TM + i, r, h)] = sum[i][r];
+        }
+        __syncthreads();
+        if (wn == 0 && l31 == 0) {
+            const double b2 = P.b2 ? (double)P.b2[0] : 0.0;
+#pragma unroll
+            for (int i = 0; i < TM; ++i)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) {
+                    const int lr = conv_tile_row(wm * TM + i, r, h);
+                    const long long oo = conv_p_o_offset(g, row0 + lr, P.ldo);
+                    if (oo >= 0) {
+                        float v = (float)((sum[i][r] + red[lr]) + b2);
+                        if (P.flags & DR_CONV_RELU_OUT) v = fmaxf(v, 0.f);
+                        P.out[oo] = v;
+                    }
+                }
+        }
+        return;
+    }
+
     // C/D layout of the 32x32 MFMA: col = lane & 31, row = (r & 3) + 8 (r >> 2) + 4 (lane >> 5)
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
         const int col = col0 + (wn * TN + j) * 32 + l31;
-        const float bv = (P.bias && col < MAP::cols(g)) ? P.bias[col] : 0.f;
+        const float bv = (P.bias && col < MAP::cols(g)) ? P.bias[MAP::bias(g, col)] : 0.f;
 #pragma unroll
         for (int i = 0; i < TM; ++i)
 #pragma unroll
@@ -173,7 +254,9 @@ __global__ __launch_bounds__(CV_NT) __attribute__((amdgpu_waves_per_eu(2))) void
                 const long long oo = MAP::o(g, row, col, P.ldo);
                 if (oo >= 0) {
                     float v = tot[i][j][r] + bv;
+                    if (EP == CV_EP_ACT && (P.flags & DR_CONV_RELU_OUT)) v = fmaxf(v, 0.f);          // after the bias, before the addends
                     if (P.addend) v += P.addend[MAP::o(g, row, col, P.lda)];
+                    if (EP == CV_EP_ACT && P.addend2) v += P.addend2[MAP::o(g, row, col, P.lda2)];
                     P.out[oo] = v;
                 }
             }
@@ -244,23 +327,36 @@ constexpr long long CV_LARGE_TILES = 512;
 // sums of up to this many terms add their partial sums every 8 terms, longer ones every 32 (see the kernel)
 constexpr int CV_SHORT_K = 1024;
 
-template <class MAP, int TM, int TN, int NBUF, int FG>
+template <class MAP, int TM, int TN, int NBUF, int FG, int EP = CV_EP_PLAIN>
 static int launch_conv_mfma(const ConvArgs& A, bool vec, hipStream_t st) {
     const long long tiles = (long long)((MAP::rows(A.g) + 64 * TM - 1) / (64 * TM)) * ((MAP::cols(A.g) + 64 * TN - 1) / (64 * TN));
     ProfScope ps(PK_GEMM, 2.0 * MAP::rows(A.g) * MAP::cols(A.g) * MAP::depth(A.g), st);
-    if (vec) hipLaunchKernelGGL((conv2d_mfma_kernel<MAP, TM, TN, NBUF, FG, true>), dim3((unsigned)tiles), dim3(CV_NT), 0, st, A);
-    else hipLaunchKernelGGL((conv2d_mfma_kernel<MAP, TM, TN, NBUF, FG, false>), dim3((unsigned)tiles), dim3(CV_NT), 0, st, A);
+    if (vec) hipLaunchKernelGGL((conv2d_mfma_kernel<MAP, TM, TN, NBUF, FG, true, EP>), dim3((unsigned)tiles), dim3(CV_NT), 0, st, A);
+    else hipLaunchKernelGGL((conv2d_mfma_kernel<MAP, TM, TN, NBUF, FG, false, EP>), dim3((unsigned)tiles), dim3(CV_NT), 0, st, A);
     DR_LAUNCH_CHECK();
     return DR_OK;
 }
 
-// the tile and window choice of both implicit GEMMs: rows x cols x depth of the map
-template <class MAP>
+// the tile and window choice of every implicit GEMM: rows x cols x depth of the map
+template <class MAP, int EP = CV_EP_PLAIN>
 static int dispatch_conv_mfma(const ConvArgs& A, bool vec, hipStream_t st) {
     const long long large = (long long)((MAP::rows(A.g) + 127) / 128) * ((MAP::cols(A.g) + 127) / 128);
-    if (MAP::depth(A.g) <= CV_SHORT_K) return launch_conv_mfma<MAP, 1, 1, 2, 1>(A, vec, st);     // (the large tile has no registers for a window per group)
-    return large >= CV_LARGE_TILES ? launch_conv_mfma<MAP, 2, 2, 1, 4>(A, vec, st) : launch_conv_mfma<MAP, 1, 1, 2, 4>(A, vec, st);
+    if (MAP::depth(A.g) <= CV_SHORT_K) return launch_conv_mfma<MAP, 1, 1, 2, 1, EP>(A, vec, st);     // (the large tile has no registers for a window per group)
+    return large >= CV_LARGE_TILES ? launch_conv_mfma<MAP, 2, 2, 1, 4, EP>(A, vec, st) : launch_conv_mfma<MAP, 1, 1, 2, 4, EP>(A, vec, st);
 }
+
+// The project entry: its Cmid <= 64 columns are ONE 64-wide column tile, which the epilogue sums inside the workgroup, so the 128 x 128 tile
+// does not apply; the window rule is the one above.  (Cmid = 32 leaves wave column 1 multiplying zeros: a 32-wide geometry with the four waves
+// along m was not built -- DESIGN 5q.)
+static int dispatch_conv_project(const ConvArgs& A, bool vec, hipStream_t st) {
+    if (FwdMap::depth(A.g) <= CV_SHORT_K) return launch_conv_mfma<FwdMap, 1, 1, 2, 1, CV_EP_PROJECT>(A, vec, st);
+    return launch_conv_mfma<FwdMap, 1, 1, 2, 4, CV_EP_PROJECT>(A, vec, st);
+}
+
+// [p, p + n) and [q, q + m) share an element
+static bool cv_overlap(const float* p, long long n, const float* q, long long m) { return p && q && p < q + m && q < p + n; }
+// the extent in floats of rows [R, ld] of C columns
+static long long cv_extent(long long R, int ld, int C) { return (R - 1) * ld + C; }
 
 
 // ---- the backward ---------------------------------------------------------------------------------------------------------------------
@@ -491,6 +587,75 @@ int dr_conv2d_rows_f32(int Hi, int Wi, int Cin, int Cout, int k, int stride, int
     hipLaunchKernelGGL(conv2d_direct_kernel, grid, dim3(256), 0, st, A);
     DR_LAUNCH_CHECK();
     return DR_OK;
+}
+
+int dr_conv2d_rows_act_f32(int Hi, int Wi, int Cin, int Cout, int k, int stride, int padding, int dilation, const float* x, int ldx,
+                           const float* weight, const float* bias, int flags, const float* addend, int lda, const float* addend2, int lda2,
+                           float* out, int ldo, void* stream) {
+    if (Hi < 1 || Wi < 1 || Cin < 1 || Cout < 1 || k < 1 || stride < 1 || padding < 0 || dilation < 1) return DR_EINVAL;
+    if (!x || !weight || !out || ldx < Cin || ldo < Cout || (addend && lda < Cout) || (addend2 && lda2 < Cout)) return DR_EINVAL;
+    if (flags & ~(DR_CONV_RELU_IN | DR_CONV_RELU_OUT)) return DR_EINVAL;
+    if ((((uintptr_t)x) | ((uintptr_t)weight) | ((uintptr_t)bias) | ((uintptr_t)addend) | ((uintptr_t)addend2) | ((uintptr_t)out)) & 3u) return DR_EINVAL;
+    if (k > 31 || stride > 64 || padding > 1024 || dilation > 64) return DR_ENOSUP;
+    if ((long long)Hi * Wi > (1ll << 24) || Cin > (1 << 16) || Cout > (1 << 16) || (long long)k * k * Cin > (1ll << 20)) return DR_ENOSUP;
+    if (ldx > (1 << 20) || ldo > (1 << 20) || lda > (1 << 20) || lda2 > (1 << 20)) return DR_ENOSUP;
+    const ConvGeom g = conv_geom(Hi, Wi, Cin, Cout, k, stride, padding, dilation);
+    if (g.Ho < 1 || g.Wo < 1) return DR_EINVAL;
+    if ((long long)g.Ho * g.Wo > (1ll << 24)) return DR_ENOSUP;
+    const long long M = (long long)g.Ho * g.Wo, no = cv_extent(M, ldo, Cout);
+    if (cv_overlap(out, no, x, cv_extent((long long)Hi * Wi, ldx, Cin)) || cv_overlap(out, no, weight, (long long)Cout * g.K) ||
+        cv_overlap(out, no, bias, Cout) || cv_overlap(out, no, addend, cv_extent(M, lda, Cout)) ||
+        cv_overlap(out, no, addend2, cv_extent(M, lda2, Cout)))
+        return DR_EINVAL;
+    ConvArgs A{g, x, weight, bias, addend, out, ldx, lda, ldo, flags, addend2, lda2, nullptr, nullptr};
+    const hipStream_t st = (hipStream_t)stream;
+    if (Cin % 4 == 0) {
+        const bool vec = ((((uintptr_t)x) | ((uintptr_t)weight)) & 15u) == 0 && ldx % 4 == 0;
+        return dispatch_conv_mfma<FwdMap, CV_EP_ACT>(A, vec, st);
+    }
+    if (flags || addend2) return DR_ENOSUP;                                    // the direct arm has no flags
+    const dim3 grid((g.Ho * g.Wo + 4 * CV_DPX - 1) / (4 * CV_DPX), (Cout + 63) / 64);
+    hipLaunchKernelGGL(conv2d_direct_kernel, grid, dim3(256), 0, st, A);
+    DR_LAUNCH_CHECK();
+    return DR_OK;
+}
+
+int dr_conv_transpose2d_rows_f32(int H, int W, int Cin, int Cout, int s, const float* x, int ldx, const float* weight, const float* bias, float* out,
+                                 int ldo, void* stream) {
+    if (H < 1 || W < 1 || Cin < 1 || Cout < 1 || s < 1) return DR_EINVAL;
+    if (!x || !weight || !out || ldx < Cin || ldo < Cout) return DR_EINVAL;
+    if ((((uintptr_t)x) | ((uintptr_t)weight) | ((uintptr_t)bias) | ((uintptr_t)out)) & 3u) return DR_EINVAL;
+    if (s > 8 || Cin % 4 != 0 || Cin > (1 << 16) || (long long)s * s * Cout > (1ll << 16)) return DR_ENOSUP;
+    if ((long long)H * s * W * s > (1ll << 24) || ldx > (1 << 20) || ldo > (1 << 20)) return DR_ENOSUP;
+    const ConvGeom g = conv_t_geom(H, W, Cin, Cout, s);
+    const long long no = cv_extent((long long)g.Ho * g.Wo, ldo, Cout);
+    if (cv_overlap(out, no, x, cv_extent((long long)H * W, ldx, Cin)) || cv_overlap(out, no, weight, (long long)conv_t_cols(g) * Cin) ||
+        cv_overlap(out, no, bias, Cout))
+        return DR_EINVAL;
+    ConvArgs A{g, x, weight, bias, nullptr, out, ldx, 0, ldo, 0, nullptr, 0, nullptr, nullptr};
+    const bool vec = ((((uintptr_t)x) | ((uintptr_t)weight)) & 15u) == 0 && ldx % 4 == 0;
+    return dispatch_conv_mfma<TransMap>(A, vec, (hipStream_t)stream);
+}
+
+int dr_conv2d_rows_project_f32(int Hi, int Wi, int Cin, int Cmid, int k, int stride, int padding, int dilation, const float* x, int ldx,
+                               const float* w1, const float* b1, const float* w2, const float* b2, int relu_out, float* out, int ldo, void* stream) {
+    if (Hi < 1 || Wi < 1 || Cin < 1 || Cmid < 1 || k < 1 || stride < 1 || padding < 0 || dilation < 1) return DR_EINVAL;
+    if (!x || !w1 || !w2 || !out || ldx < Cin || ldo < 1) return DR_EINVAL;
+    if ((((uintptr_t)x) | ((uintptr_t)w1) | ((uintptr_t)b1) | ((uintptr_t)w2) | ((uintptr_t)b2) | ((uintptr_t)out)) & 3u) return DR_EINVAL;
+    if (k > 31 || stride > 64 || padding > 1024 || dilation > 64) return DR_ENOSUP;
+    if (Cmid > 64 || Cin % 4 != 0) return DR_ENOSUP;
+    if ((long long)Hi * Wi > (1ll << 24) || Cin > (1 << 16) || (long long)k * k * Cin > (1ll << 20)) return DR_ENOSUP;
+    if (ldx > (1 << 20) || ldo > (1 << 20)) return DR_ENOSUP;
+    const ConvGeom g = conv_geom(Hi, Wi, Cin, Cmid, k, stride, padding, dilation);
+    if (g.Ho < 1 || g.Wo < 1) return DR_EINVAL;
+    if ((long long)g.Ho * g.Wo > (1ll << 24)) return DR_ENOSUP;
+    const long long no = cv_extent((long long)g.Ho * g.Wo, ldo, 1);
+    if (cv_overlap(out, no, x, cv_extent((long long)Hi * Wi, ldx, Cin)) || cv_overlap(out, no, w1, (long long)Cmid * g.K) ||
+        cv_overlap(out, no, b1, Cmid) || cv_overlap(out, no, w2, Cmid) || cv_overlap(out, no, b2, 1))
+        return DR_EINVAL;
+    ConvArgs A{g, x, w1, b1, nullptr, out, ldx, 0, ldo, relu_out ? DR_CONV_RELU_OUT : 0, nullptr, 0, w2, b2};
+    const bool vec = ((((uintptr_t)x) | ((uintptr_t)w1)) & 15u) == 0 && ldx % 4 == 0;
+    return dispatch_conv_project(A, vec, (hipStream_t)stream);
 }
 
 int dr_resize_rows_f32(int C, int Hs, int Ws, int Hd, int Wd, const float* in, int ldi, const float* addend, int lda, float* out, int ldo,

@@ -1,7 +1,8 @@
 // conv_index.h -- the index arithmetic of dr_conv2d_rows_f32 and of its two gradients (conv2d.hip): nn.Conv2d (groups = 1, zero padding, square kernel k, stride s,
 // padding p, dilation d) on token rows [H W, C].  The kernels compute every address through these functions and nothing else, and
 // tools/conv_index_check.cpp walks the same functions on the host over every (output pixel, tap, 4-channel group) of the tested and the
-// production shapes before anything runs on a device (tools/conv_bwd_index_check.cpp for the gradients).  No HIP type in here: the file compiles as plain C++.
+// production shapes before anything runs on a device (tools/conv_bwd_index_check.cpp for the gradients; tools/dpt_index_check.cpp for the transposed
+// convolution and the project entry at the end of the file).  No HIP type in here: the file compiles as plain C++.
 #pragma once
 
 #if defined(__HIPCC__) || defined(__CUDACC__)
@@ -148,6 +149,59 @@ DR_HD long long conv_wg_bias_part_byte(const ConvGeom& g, const ConvSlabs& sl) {
 }
 DR_HD long long conv_wg_workspace_bytes(const ConvGeom& g, const ConvSlabs& sl) {
     return conv_wg_bias_part_byte(g, sl) + (long long)sl.S * g.Cout * 8;
+}
+
+// ---- the DPT head's two other forms (dr_conv_transpose2d_rows_f32, dr_conv2d_rows_project_f32); walked by tools/dpt_index_check.cpp ----------
+
+// nn.ConvTranspose2d(Cin, Cout, k = s, stride = s, padding 0): no two taps meet, so out[(y s + i)(W s) + x s + j][co] = sum_ci x[y W + x][ci]
+// W[ci][co][i][j] is a plain GEMM with m = input pixel, n = (i, j, co) (tap-major, co-minor), kk = ci.  The geometry reuses ConvGeom: k = s,
+// Ho = Hi s, Wo = Wi s, K = Cin (the length of one row of the packed weight [s s Cout, Cin]).
+DR_HD ConvGeom conv_t_geom(int Hi, int Wi, int Cin, int Cout, int s) {
+    ConvGeom g;
+    g.Hi = Hi; g.Wi = Wi; g.Cin = Cin; g.Cout = Cout;
+    g.k = s; g.s = s; g.p = 0; g.d = 1;
+    g.Ho = Hi * s;
+    g.Wo = Wi * s;
+    g.K = Cin;
+    return g;
+}
+
+// the number of GEMM columns n = (i, j, co)
+DR_HD int conv_t_cols(const ConvGeom& g) { return g.k * g.k * g.Cout; }
+
+// The A operand: element (input pixel m, channel kk) of x [Hi Wi, ldx], or -1 outside the problem
+DR_HD long long conv_t_a_offset(const ConvGeom& g, int m, int kk, int ldx) {
+    if (m < 0 || m >= g.Hi * g.Wi || kk < 0 || kk >= g.Cin) return -1;
+    return (long long)m * ldx + kk;
+}
+
+// The B operand: element (column n, channel kk) of the packed weight [s s Cout, Cin], or -1 outside it
+DR_HD long long conv_t_w_offset(const ConvGeom& g, int n, int kk) {
+    if (n < 0 || n >= conv_t_cols(g) || kk < 0 || kk >= g.Cin) return -1;
+    return (long long)n * g.Cin + kk;
+}
+
+// column n -> its output channel (the bias index); n inside [0, conv_t_cols)
+DR_HD int conv_t_channel(const ConvGeom& g, int n) { return n % g.Cout; }
+
+// The store, a pixel shuffle: (input pixel m = y Wi + x, column n = ((i s + j) Cout + co)) -> element (row (y s + i)(Wi s) + x s + j, co) of
+// out [Hi s Wi s, ld], or -1 outside the problem
+DR_HD long long conv_t_o_offset(const ConvGeom& g, int m, int n, int ld) {
+    if (m < 0 || m >= g.Hi * g.Wi || n < 0 || n >= conv_t_cols(g)) return -1;
+    const int y = m / g.Wi, x = m - y * g.Wi;
+    const int tap = n / g.Cout, co = n - tap * g.Cout;
+    const int i = tap / g.s, j = tap - i * g.s;
+    return ((long long)(y * g.s + i) * g.Wo + x * g.s + j) * ld + co;
+}
+
+// The C/D layout of the 32 x 32 MFMA: register r of lane half h of 32-row tile `tile` holds row tile 32 + (r & 3) + 8 (r >> 2) + 4 h of the
+// workgroup's rows (the column is lane & 31).  The project entry's epilogue keeps one sum per such row.
+DR_HD int conv_tile_row(int tile, int r, int h) { return tile * 32 + (r & 3) + 8 * (r >> 2) + 4 * h; }
+
+// The project entry's result: output pixel m of out [Ho Wo] with the leading dimension ld (one value per pixel), or -1 outside it
+DR_HD long long conv_p_o_offset(const ConvGeom& g, int m, int ld) {
+    if (m < 0 || m >= g.Ho * g.Wo) return -1;
+    return (long long)m * ld;
 }
 
 }  // namespace dr

@@ -344,11 +344,19 @@ SIGNATURES.update({
     "dr_vit_workspace_bytes": (c_size_t, [c_int] * 5),
     "dr_vit_forward_f16": (c_int, [ctypes.POINTER(VitConfigF16), c_void_p]),
     "dr_debug_gemm_rows_tile": (None, [c_int]),
+    # added after ABI 0.7.0, seventh set: the Depth-Anything DPT head's forward on token rows (csrc/conv2d.hip)
+    "dr_conv2d_rows_act_f32": (c_int, [c_int] * 8 + [c_void_p, c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int, c_void_p, c_int,
+                                       c_void_p]),
+    "dr_conv_transpose2d_rows_f32": (c_int, [c_int] * 5 + [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p]),
+    "dr_conv2d_rows_project_f32": (c_int, [c_int] * 8 + [c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p]),
 })
 
 
 def _bind(table):
     for name, (res, args) in table.items():
+        if not hasattr(_lib, name):          # the sets added under one ABI number are detected by symbol
+            raise ImportError("libdiffreg_hip.so has no %s: it was built from an older tree than this binding; rebuild (make -C diff-reg_amd/csrc)"
+                              % name)
         fn = getattr(_lib, name)
         fn.restype = res
         fn.argtypes = args
@@ -1667,6 +1675,86 @@ def resize_rows(x, src_size, size, addend=None, out=None):
     check(_lib.dr_resize_rows_f32(C, Hs, Ws, Hd, Wd, rawp(x), x.stride(0), rawp(addend), addend.stride(0) if addend is not None else 0, rawp(out),
                                   out.stride(0), stream_of(x)))
     return out
+
+
+CONV_RELU_IN, CONV_RELU_OUT = 1, 2          # DR_CONV_RELU_IN, DR_CONV_RELU_OUT
+
+
+def _rows_ok(t_, n, C):
+    return t_.dim() == 2 and t_.shape[0] == n and t_.shape[1] == C and (C == 1 or t_.stride(1) == 1)
+
+
+def conv2d_rows_act(x, size, w_packed, k, bias=None, stride=1, padding=0, dilation=1, relu_in=False, relu_out=False, addend=None, addend2=None,
+                    out=None):
+    """conv2d_rows with the DPT head's epilogue: out = relu_out?(conv(relu_in?(x)) + bias) + addend + addend2 -> (out [Ho*Wo, Cout], (Ho, Wo)).
+    relu_in leaves x itself untouched; relu_out comes after the bias and before the addends; out must not share memory with an input.
+    Flags and addend2 need Cin % 4 == 0   (dr_conv2d_rows_act_f32)"""
+    ensure_init()
+    Hi, Wi = int(size[0]), int(size[1])
+    Cin, Cout = x.shape[1], w_packed.shape[0]
+    if x.shape[0] != Hi * Wi or w_packed.shape[1] != k * k * Cin or (Cin > 1 and x.stride(1) != 1):
+        raise ValueError("conv2d_rows_act: x %s / weight %s do not fit a %d x %d image and a %d x %d kernel" % (tuple(x.shape), tuple(w_packed.shape),
+                                                                                                             Hi, Wi, k, k))
+    Ho, Wo = conv_out_size(Hi, k, stride, padding, dilation), conv_out_size(Wi, k, stride, padding, dilation)
+    for name, a in (("addend", addend), ("addend2", addend2)):
+        if a is not None and not _rows_ok(a, Ho * Wo, Cout):
+            raise ValueError("conv2d_rows_act: %s %s is not [%d, %d] rows" % (name, tuple(a.shape), Ho * Wo, Cout))
+    if out is None:
+        out = torch.empty(max(Ho * Wo, 0), Cout, device=x.device)
+    rawp = lambda t_: None if t_ is None else c_void_p(t_.data_ptr())
+    flags = (CONV_RELU_IN if relu_in else 0) | (CONV_RELU_OUT if relu_out else 0)
+    check(_lib.dr_conv2d_rows_act_f32(Hi, Wi, Cin, Cout, k, stride, padding, dilation, rawp(x), x.stride(0), ptr(w_packed), ptr(bias), flags,
+                                      rawp(addend), addend.stride(0) if addend is not None else 0, rawp(addend2),
+                                      addend2.stride(0) if addend2 is not None else 0, rawp(out), out.stride(0), stream_of(x)))
+    return out, (Ho, Wo)
+
+
+def pack_conv_transpose_weight(weight):
+    """nn.ConvTranspose2d weight [Cin, Cout, s, s] -> the packed [s s Cout, Cin] ((i, j) major, co minor) dr_conv_transpose2d_rows_f32 reads"""
+    Cin, Cout, kh, kw = weight.shape
+    if kh != kw:
+        raise NotImplementedError("libdiffreg_hip: conv_transpose2d_rows takes square kernels (got %d x %d)" % (kh, kw))
+    return weight.detach().float().permute(2, 3, 1, 0).reshape(kh * kw * Cout, Cin).contiguous()
+
+
+def conv_transpose2d_rows(x, size, w_packed, s, bias=None, out=None):
+    """nn.ConvTranspose2d(kernel = stride = s, padding 0) on token rows: x [H*W, Cin], size = (H, W), w_packed from pack_conv_transpose_weight
+    -> (out [H s * W s, Cout], (H s, W s)), every element written   (dr_conv_transpose2d_rows_f32)"""
+    ensure_init()
+    H, W, s = int(size[0]), int(size[1]), int(s)
+    Cin = x.shape[1]
+    if s < 1 or x.shape[0] != H * W or w_packed.shape[1] != Cin or w_packed.shape[0] % (s * s) != 0 or (Cin > 1 and x.stride(1) != 1):
+        raise ValueError("conv_transpose2d_rows: x %s / weight %s do not fit a %d x %d image and stride %d" % (tuple(x.shape), tuple(w_packed.shape),
+                                                                                                            H, W, s))
+    Cout = w_packed.shape[0] // (s * s)
+    if out is None:
+        out = torch.empty(H * s * W * s, Cout, device=x.device)
+    elif not _rows_ok(out, H * s * W * s, Cout):
+        raise ValueError("conv_transpose2d_rows: out %s is not [%d, %d] rows" % (tuple(out.shape), H * s * W * s, Cout))
+    check(_lib.dr_conv_transpose2d_rows_f32(H, W, Cin, Cout, s, c_void_p(x.data_ptr()), x.stride(0), ptr(w_packed), ptr(bias),
+                                            c_void_p(out.data_ptr()), out.stride(0), stream_of(x)))
+    return out, (H * s, W * s)
+
+
+def conv2d_rows_project(x, size, w1_packed, k, b1, w2, b2=None, stride=1, padding=0, dilation=1, relu_out=True, out=None):
+    """conv k x k (Cin -> Cmid <= 64, w1_packed from pack_conv_weight, + b1) -> ReLU -> w2 [Cmid] . (.) + b2 [1] -> ReLU if relu_out, in one
+    launch: x [Hi*Wi, Cin] rows -> (out [Ho*Wo] or a strided view of that length, (Ho, Wo))   (dr_conv2d_rows_project_f32)"""
+    ensure_init()
+    Hi, Wi = int(size[0]), int(size[1])
+    Cin, Cmid = x.shape[1], w1_packed.shape[0]
+    if x.shape[0] != Hi * Wi or w1_packed.shape[1] != k * k * Cin or (Cin > 1 and x.stride(1) != 1) or w2.numel() != Cmid or \
+            (b2 is not None and b2.numel() != 1):
+        raise ValueError("conv2d_rows_project: x %s / w1 %s / w2 %s do not fit a %d x %d image and a %d x %d kernel"
+                         % (tuple(x.shape), tuple(w1_packed.shape), tuple(w2.shape), Hi, Wi, k, k))
+    Ho, Wo = conv_out_size(Hi, k, stride, padding, dilation), conv_out_size(Wi, k, stride, padding, dilation)
+    if out is None:
+        out = torch.empty(max(Ho * Wo, 0), device=x.device)
+    elif out.dim() != 1 or out.shape[0] != Ho * Wo:
+        raise ValueError("conv2d_rows_project: out %s is not [%d]" % (tuple(out.shape), Ho * Wo))
+    check(_lib.dr_conv2d_rows_project_f32(Hi, Wi, Cin, Cmid, k, stride, padding, dilation, c_void_p(x.data_ptr()), x.stride(0), ptr(w1_packed),
+                                          ptr(b1), ptr(w2), ptr(b2), 1 if relu_out else 0, c_void_p(out.data_ptr()),
+                                          out.stride(0) if out.numel() > 1 else 1, stream_of(x)))
+    return out, (Ho, Wo)
 
 
 def pack_conv_weight_t(weight):

@@ -81,7 +81,18 @@ dim other than 64, ...) raises NotImplementedError here, before any site is boun
 
     accelerate(model, dino=True)
 
-What then stays the reference's code in a training step: Depth-Anything (the same ViT class run in fp32, and its DPT head), the encoder's CNN
+With `depth_head=True` (any combination of the flags above) the decoder of Depth-Anything (`model.depth_model.depth_head`, a DPTHead:
+depth_anything/dpt.py:103-136, reached through EXP/model.py:343-351) runs on the device in float32 (diffreg_hip/dpt2d3d.py: the implicit-GEMM
+convolution with the pre-activation / two-addend epilogue, the transposed convolution as a GEMM with a pixel-shuffle store, the fused tail and the
+row resample of csrc/conv2d.hip): `depth_head.forward` is re-bound on the instance and `remove()` restores it.  The device path runs in eval mode
+under torch.no_grad() with CUDA float32 inputs of batch 1; otherwise the bound forward calls the module's own code unchanged.  The trailing
+F.interpolate + relu of DPT_DINOv2.forward (dpt.py:163-164) and the host-side Resize transform stay as they are.  A head the kernels do not cover
+(use_clstoken, nclass > 1, batch norm, ...) raises NotImplementedError here, before any site is bound.  The flag is opt-in and defaults off.
+
+    accelerate(model, depth_head=True)
+
+What then stays the reference's code in a training step: the float32 ViT of Depth-Anything (the same ViT class as DINOv2, run in fp32; the
+device encoder is fp16 only) with the host-side Resize in front of it, the encoder's CNN
 branch (`encoder.cnn`, whose outputs MATR2D3D.forward discards) and `dino_2_u`, the inline GT retry ladder and the other inline glue of
 MATR2D3D.forward.
 """
@@ -96,9 +107,10 @@ from .engine import DenoiseEngine2D3D
 
 class LoopOverlay2D3D:
     def __init__(self, model, n_head=4, engine_kwargs=None, training=False, partition=False, backbone=False, noising=False, front=False,
-                 image_backbone=False, image_backbone_grad=False, dino=False):
+                 image_backbone=False, image_backbone_grad=False, dino=False, depth_head=False):
         self.model = model
         self.dino = bool(dino)
+        self.depth_head = bool(depth_head)
         self.training = bool(training)
         self.partition = bool(partition)
         self.backbone = bool(backbone)
@@ -114,6 +126,9 @@ class LoopOverlay2D3D:
         if self.dino:                       # likewise: refuses before any site is bound
             from . import vit2d3d
             self.dino_binding = vit2d3d.bind(model.encoder)
+        if self.depth_head:                 # likewise
+            from . import dpt2d3d
+            self.depth_head_undo = dpt2d3d.bind(model.depth_model.depth_head)
         self._globals_saved = {}
         self.n_head = n_head
         self.engine_kwargs = dict(engine_kwargs or {})
@@ -177,6 +192,8 @@ class LoopOverlay2D3D:
             sites += [(m.img_backbone, "forward")]
         if self.dino:
             self.dino_binding.remove()
+        if self.depth_head:
+            self.depth_head_undo()
         for obj, name in sites:
             if name in obj.__dict__:
                 del obj.__dict__[name]
@@ -281,7 +298,7 @@ class LoopOverlay2D3D:
 
 
 def accelerate(model, n_head=4, training=False, partition=False, backbone=False, noising=False, front=False, image_backbone=False,
-               image_backbone_grad=False, dino=False, **engine_kwargs):
+               image_backbone_grad=False, dino=False, depth_head=False, **engine_kwargs):
     """install the overlay on a MATR2D3D instance (see the module docstring); returns the LoopOverlay2D3D (`.remove()` undoes it).
     training=True: the training branch's four coarse modules run on the device under model.train() as well.
     partition=True: the patch partition and GT patch overlaps (and, with training, the GT search) run on the device as well.
@@ -291,10 +308,12 @@ def accelerate(model, n_head=4, training=False, partition=False, backbone=False,
     front=True: back_project, render, create_meshgrid (globals of the model's module) and back_project_depth (the instance) run on the device.
     image_backbone=True: model.img_backbone's inference forward runs on the device (eval mode under torch.no_grad(); otherwise its own code).
     image_backbone_grad=True (implies image_backbone): the device path also runs in training mode and with gradients enabled, with its backward.
-    dino=True: the frozen DINOv2 ViT of model.encoder (dinov2_vitl14[0].forward_features) runs on the device in fp16, in eval and in training."""
+    dino=True: the frozen DINOv2 ViT of model.encoder (dinov2_vitl14[0].forward_features) runs on the device in fp16, in eval and in training.
+    depth_head=True: model.depth_model.depth_head (Depth-Anything's DPT decoder) runs on the device in float32 (eval mode under torch.no_grad();
+    otherwise its own code)."""
     return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs, training=training, partition=partition, backbone=backbone,
                            noising=noising, front=front, image_backbone=image_backbone, image_backbone_grad=image_backbone_grad,
-                           dino=dino)
+                           dino=dino, depth_head=depth_head)
 
 
 def accelerate_loss(loss_module, fine=False):

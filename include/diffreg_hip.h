@@ -56,7 +56,9 @@ extern "C" {
  *          inference forward on token rows: dr_conv2d_rows_f32, dr_resize_rows_f32 (new entries only; nothing older changed).
  *   0.7.0, fifth set (same rule)  the image backbone's backward on token rows: dr_conv2d_rows_backward_data_f32,
  *          dr_conv2d_rows_backward_weight_f32 with dr_conv2d_rows_backward_weight_workspace_bytes, dr_resize_rows_backward_f32 (new entries
- *          only; nothing older changed). */
+ *          only; nothing older changed).
+ *   0.7.0, seventh set (same rule)  the Depth-Anything DPT head's forward on token rows: dr_conv2d_rows_act_f32,
+ *          dr_conv_transpose2d_rows_f32, dr_conv2d_rows_project_f32 (new entries only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1219,6 +1221,43 @@ int dr_attention_rows_f16(int L, int H, int d, const void* qkv, int ldqkv, void*
 int dr_patch_rows_f16(int H, int W, int p, const void* img, int img_f32, void* out, int ldo, void* stream);
 size_t dr_vit_workspace_bytes(int H, int W, int p, int D, int Dh);
 int dr_vit_forward_f16(const dr_vit_config_f16* cfg, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, seventh set (detected by symbol like the fourth to sixth sets): the float32 convolutional decoder of Depth-Anything,
+ * DPTHead.forward (depth_anything/dpt.py:103-136, depth_anything/blocks.py:37-153; called through EXP/model.py:343-351).  csrc/conv2d.hip, index
+ * arithmetic in csrc/conv_index.h; DESIGN 5q.  The fourth set's rules hold: token rows [H W, C] float32 with leading dimensions, exact fp32
+ * products on the f32-input MFMA, no atomics and no split-k, one fixed accumulation order (two runs are bit-equal), nothing synchronises,
+ * nothing allocates, DR_EINVAL / DR_ENOSUP before any launch, and dr_conv2d_rows_f32's limits unless said otherwise.  `out` sharing an element
+ * with any input is DR_EINVAL.
+ *
+ * dr_conv2d_rows_act_f32: dr_conv2d_rows_f32 with a flags word and a second addend:
+ *     out = relu_out?(conv(relu_in?(x)) + bias) + addend + addend2
+ *   DR_CONV_RELU_IN: max(x, 0) on the input as it is fetched (the pre-activation of ResidualConvUnit.forward, blocks.py:79, :84; nn.ReLU(False),
+ *   so x itself is untouched and can be the residual).  DR_CONV_RELU_OUT: ReLU after the bias and BEFORE the addends.  addend2 [Ho Wo, lda2] or
+ *   NULL is added after addend (blocks.py:92 then :136).  One entry is conv1 of a unit (RELU_IN | RELU_OUT), conv2 of a unit (addend = the unit's
+ *   input, addend2 = xs[0] in a fusion block), layerN_rn (blocks.py:20-32), out_conv (:117), projects[i] (dpt.py:29-37, :113-115: the ViT's token
+ *   rows are the conv's rows as they are), resize_layers[3] (dpt.py:53-58) and output_conv1 (dpt.py:93).  With flags = 0 and addend2 = NULL the
+ *   result is bit-equal to dr_conv2d_rows_f32.  Flags and addend2 exist on the MFMA arm only: either with Cin % 4 != 0 is DR_ENOSUP.  Unknown flag
+ *   bits are DR_EINVAL.
+ * dr_conv_transpose2d_rows_f32: nn.ConvTranspose2d(Cin, Cout, kernel = s, stride = s, padding 0, output_padding 0, dilation 1, groups 1)
+ *   (dpt.py:40-51): x [H W, ldx] -> out [H s W s, ldo], out[(y s + i)(W s) + x s + j][co] = bias[co] + sum_ci x[y W + x][ci] w[ci][co][i][j].  No two
+ *   taps meet, so it is one GEMM whose store is a pixel shuffle.  weight is PACKED [s s Cout, Cin] ((i, j) major, co minor: the module's
+ *   [Cin, Cout, s, s] permuted to [s, s, Cout, Cin]).  bias [Cout] or NULL.  Every output element is written.  Domain: Cin % 4 == 0, 1 <= s <= 8,
+ *   (H s)(W s) <= 2^24, s s Cout <= 2^16, Cin <= 2^16, leading dimensions <= 2^20; s < 1 is DR_EINVAL, everything else outside is DR_ENOSUP.
+ * dr_conv2d_rows_project_f32: the head's tail (dpt.py:95-99) in one launch: out[m] = relu_out?(b2 + sum_c w2[c] relu(conv(x)[m][c] + b1[c])),
+ *   conv k x k from Cin to Cmid channels (w1 PACKED [Cmid, k k Cin] as dr_conv2d_rows_f32's weight, b1 [Cmid] or NULL), w2 [Cmid], b2 a DEVICE
+ *   pointer to one float or NULL; out [Ho Wo] with the leading dimension ldo >= 1 (one value per pixel).  The hidden [Ho Wo, Cmid] is never
+ *   written: the products relu(.) w2 are formed and added in double in a fixed order (across the 32 lanes of a row, then across the wave pair)
+ *   and rounded once.  Cmid <= 64 and Cin % 4 == 0, else DR_ENOSUP. */
+#define DR_CONV_RELU_IN 1
+#define DR_CONV_RELU_OUT 2
+int dr_conv2d_rows_act_f32(int Hi, int Wi, int Cin, int Cout, int k, int stride, int padding, int dilation, const float* x, int ldx,
+                           const float* weight, const float* bias, int flags, const float* addend, int lda, const float* addend2, int lda2,
+                           float* out, int ldo, void* stream);
+int dr_conv_transpose2d_rows_f32(int H, int W, int Cin, int Cout, int s, const float* x, int ldx, const float* weight, const float* bias, float* out,
+                                 int ldo, void* stream);
+int dr_conv2d_rows_project_f32(int Hi, int Wi, int Cin, int Cmid, int k, int stride, int padding, int dilation, const float* x, int ldx,
+                               const float* w1, const float* b1, const float* w2, const float* b2, int relu_out, float* out, int ldo, void* stream);
 
 #ifdef __cplusplus
 }
