@@ -49,6 +49,7 @@ struct GemmBatch {
 
 int launch_gemm(const GemmBatch& g, hipStream_t st);
 int gemm_configure();
+int vit_f32_configure();      // vit_f32.hip: the dynamic LDS of the float32 rows GEMM's tiles
 void gemm_force_config(int c);
 
 // ---------------------------------------------------------------------------------------------

@@ -352,6 +352,38 @@ SIGNATURES.update({
 })
 
 
+class GemmRowsF32Args(ctypes.Structure):
+    """dr_gemm_rows_f32_args"""
+    _fields_ = [("a", c_void_p), ("w", c_void_p), ("bias", c_void_p), ("gamma", c_void_p), ("addend", c_void_p), ("out", c_void_p),
+                ("M", c_int), ("K", c_int), ("N", c_int), ("lda", c_int), ("ldw", c_int), ("ldo", c_int), ("ld_addend", c_int), ("mode", c_int),
+                ("colscale_cols", c_int), ("colscale", c_float)]
+
+
+class VitBlockF32(ctypes.Structure):
+    """dr_vit_block_f32"""
+    _fields_ = [(n, c_void_p) for n in ("norm1_g", "norm1_b", "qkv_w", "qkv_b", "proj_w", "proj_b", "ls1", "norm2_g", "norm2_b", "fc1_w", "fc1_b",
+                                        "fc2_w", "fc2_b", "ls2")]
+
+
+class VitConfigF32(ctypes.Structure):
+    """dr_vit_config_f32"""
+    _fields_ = [("H", c_int), ("W", c_int), ("p", c_int), ("D", c_int), ("heads", c_int), ("Dh", c_int), ("depth", c_int), ("eps", c_float),
+                ("img", c_void_p), ("patch_w", c_void_p), ("patch_b", c_void_p), ("cls", c_void_p), ("pos", c_void_p),
+                ("blocks", ctypes.POINTER(VitBlockF32)), ("norm_g", c_void_p), ("norm_b", c_void_p), ("x_prenorm", c_void_p), ("x_norm", c_void_p),
+                ("n_take", c_int), ("norm_take", c_int), ("take", ctypes.POINTER(c_int)), ("take_out", ctypes.POINTER(c_void_p)),
+                ("workspace", c_void_p), ("workspace_bytes", c_size_t)]
+
+
+SIGNATURES.update({
+    # added after ABI 0.7.0, eighth set: Depth-Anything's float32 ViT encoder (csrc/vit_f32.hip)
+    "dr_gemm_rows_f32": (c_int, [ctypes.POINTER(GemmRowsF32Args), c_void_p]),
+    "dr_patch_rows_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_int, c_void_p]),
+    "dr_vit_workspace_bytes_f32": (c_size_t, [c_int] * 5),
+    "dr_vit_forward_f32": (c_int, [ctypes.POINTER(VitConfigF32), c_void_p]),
+    "dr_debug_gemm_rows_f32_tile": (None, [c_int]),
+})
+
+
 def _bind(table):
     for name, (res, args) in table.items():
         if not hasattr(_lib, name):          # the sets added under one ABI number are detected by symbol

@@ -91,8 +91,18 @@ F.interpolate + relu of DPT_DINOv2.forward (dpt.py:163-164) and the host-side Re
 
     accelerate(model, depth_head=True)
 
-What then stays the reference's code in a training step: the float32 ViT of Depth-Anything (the same ViT class as DINOv2, run in fp32; the
-device encoder is fp16 only) with the host-side Resize in front of it, the encoder's CNN
+With `depth_encoder=True` (any combination of the flags above) the float32 ViT-L/14 in front of that decoder (`model.depth_model.pretrained`, the
+hub's DinoVisionTransformer: depth_anything/dpt.py:158 calls its get_intermediate_layers(x, 4, return_class_token=True)) runs on the device in
+exact fp32 products (diffreg_hip/depth_encoder2d3d.py, csrc/vit_f32.hip: the float32 rows GEMM on the f32-input MFMA with the ViT's epilogues
+fused, the float32 attention on the packed qkv rows, the final norm of each taken stream written by the same call): `get_intermediate_layers`
+is re-bound on the ViT instance and `remove()` restores it.  The device path runs in eval mode under torch.no_grad() with a CUDA float32 batch;
+otherwise the bound method calls the module's own code unchanged.  A ViT the kernels do not cover (not entirely float32, register tokens, SwiGLU, a
+head dim other than 64, ...) raises NotImplementedError here, before any site is bound.  The flag is opt-in and defaults off.  With
+depth_head=True as well, everything from the transformed image tensor to the depth map runs in the library.
+
+    accelerate(model, depth_encoder=True, depth_head=True)
+
+What then stays the reference's code in a training step: the host-side Resize / NormalizeImage transform in front of Depth-Anything, the encoder's CNN
 branch (`encoder.cnn`, whose outputs MATR2D3D.forward discards) and `dino_2_u`, the inline GT retry ladder and the other inline glue of
 MATR2D3D.forward.
 """
@@ -107,10 +117,11 @@ from .engine import DenoiseEngine2D3D
 
 class LoopOverlay2D3D:
     def __init__(self, model, n_head=4, engine_kwargs=None, training=False, partition=False, backbone=False, noising=False, front=False,
-                 image_backbone=False, image_backbone_grad=False, dino=False, depth_head=False):
+                 image_backbone=False, image_backbone_grad=False, dino=False, depth_head=False, depth_encoder=False):
         self.model = model
         self.dino = bool(dino)
         self.depth_head = bool(depth_head)
+        self.depth_encoder = bool(depth_encoder)
         self.training = bool(training)
         self.partition = bool(partition)
         self.backbone = bool(backbone)
@@ -129,6 +140,13 @@ class LoopOverlay2D3D:
         if self.depth_head:                 # likewise
             from . import dpt2d3d
             self.depth_head_undo = dpt2d3d.bind(model.depth_model.depth_head)
+        if self.depth_encoder:              # likewise (a refusal here takes an already bound depth head back off)
+            from . import depth_encoder2d3d
+            try:
+                self.depth_encoder_undo = depth_encoder2d3d.bind(model.depth_model)
+            except NotImplementedError:
+                self._unbind_front_modules()
+                raise
         self._globals_saved = {}
         self.n_head = n_head
         self.engine_kwargs = dict(engine_kwargs or {})
@@ -162,6 +180,15 @@ class LoopOverlay2D3D:
 
     _MISSING = object()
 
+    def _unbind_front_modules(self):
+        """a later bind refused: take off what the earlier flags of this constructor bound, so that a refusal leaves no site bound"""
+        if self.image_backbone:
+            self.model.img_backbone.__dict__.pop("forward", None)
+        if self.dino:
+            self.dino_binding.remove()
+        if self.depth_head:
+            self.depth_head_undo()
+
     def _bind_partition(self):
         """re-bind the module-level functions of EXP/model.py:395-540 (and, with training, :569) in the globals of the model's defining module"""
         from . import partition2d3d as p
@@ -194,6 +221,8 @@ class LoopOverlay2D3D:
             self.dino_binding.remove()
         if self.depth_head:
             self.depth_head_undo()
+        if self.depth_encoder:
+            self.depth_encoder_undo()
         for obj, name in sites:
             if name in obj.__dict__:
                 del obj.__dict__[name]
@@ -298,7 +327,7 @@ class LoopOverlay2D3D:
 
 
 def accelerate(model, n_head=4, training=False, partition=False, backbone=False, noising=False, front=False, image_backbone=False,
-               image_backbone_grad=False, dino=False, depth_head=False, **engine_kwargs):
+               image_backbone_grad=False, dino=False, depth_head=False, depth_encoder=False, **engine_kwargs):
     """install the overlay on a MATR2D3D instance (see the module docstring); returns the LoopOverlay2D3D (`.remove()` undoes it).
     training=True: the training branch's four coarse modules run on the device under model.train() as well.
     partition=True: the patch partition and GT patch overlaps (and, with training, the GT search) run on the device as well.
@@ -310,10 +339,12 @@ def accelerate(model, n_head=4, training=False, partition=False, backbone=False,
     image_backbone_grad=True (implies image_backbone): the device path also runs in training mode and with gradients enabled, with its backward.
     dino=True: the frozen DINOv2 ViT of model.encoder (dinov2_vitl14[0].forward_features) runs on the device in fp16, in eval and in training.
     depth_head=True: model.depth_model.depth_head (Depth-Anything's DPT decoder) runs on the device in float32 (eval mode under torch.no_grad();
-    otherwise its own code)."""
+    otherwise its own code).
+    depth_encoder=True: model.depth_model.pretrained.get_intermediate_layers (Depth-Anything's float32 ViT-L/14) runs on the device in exact fp32
+    products (eval mode under torch.no_grad() with a CUDA float32 batch; otherwise its own code)."""
     return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs, training=training, partition=partition, backbone=backbone,
                            noising=noising, front=front, image_backbone=image_backbone, image_backbone_grad=image_backbone_grad,
-                           dino=dino, depth_head=depth_head)
+                           dino=dino, depth_head=depth_head, depth_encoder=depth_encoder)
 
 
 def accelerate_loss(loss_module, fine=False):

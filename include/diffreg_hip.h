@@ -58,7 +58,9 @@ extern "C" {
  *          dr_conv2d_rows_backward_weight_f32 with dr_conv2d_rows_backward_weight_workspace_bytes, dr_resize_rows_backward_f32 (new entries
  *          only; nothing older changed).
  *   0.7.0, seventh set (same rule)  the Depth-Anything DPT head's forward on token rows: dr_conv2d_rows_act_f32,
- *          dr_conv_transpose2d_rows_f32, dr_conv2d_rows_project_f32 (new entries only; nothing older changed). */
+ *          dr_conv_transpose2d_rows_f32, dr_conv2d_rows_project_f32 (new entries only; nothing older changed).
+ *   0.7.0, eighth set (same rule)  Depth-Anything's float32 ViT encoder forward: dr_gemm_rows_f32, dr_patch_rows_f32, dr_vit_forward_f32 with
+ *          dr_vit_workspace_bytes_f32 (new entries only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1258,6 +1260,87 @@ int dr_conv_transpose2d_rows_f32(int H, int W, int Cin, int Cout, int s, const f
                                  int ldo, void* stream);
 int dr_conv2d_rows_project_f32(int Hi, int Wi, int Cin, int Cmid, int k, int stride, int padding, int dilation, const float* x, int ldx,
                                const float* w1, const float* b1, const float* w2, const float* b2, int relu_out, float* out, int ldo, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, eighth set (detected by symbol like the fourth to seventh sets): the float32 ViT-L/14 encoder of Depth-Anything,
+ * DPT_DINOv2.forward's self.pretrained.get_intermediate_layers(x, 4, return_class_token=True) (depth_anything/dpt.py:155-166; the class is
+ * torchhub/facebookresearch_dinov2_main/vision_transformer.py, called once per pair through EXP/model.py:339-345).  csrc/vit_f32.hip, index
+ * arithmetic in csrc/vit_f32_index.h; DESIGN 5r.  float32 operands, exact fp32 products on the f32-input MFMA, fp32 accumulation in one fixed k
+ * order; no atomics and no split-k across workgroups: two runs are bit-equal.  Nothing synchronises, nothing allocates; every entry can be
+ * captured in a graph.  Every pointer below is device memory unless said otherwise.  The sixth set (fp16) is untouched.
+ *
+ * dr_gemm_rows_f32: out = A W^T (+ bias), A [M, K] float32 rows (lda >= K, lda % 4 == 0, 16-byte aligned), W the nn.Linear weight [N, K] as it is
+ *   (row stride ldw >= K, ldw % 4 == 0, 16-byte aligned; there is no packed image).  nn.Linear of dinov2/layers/attention.py:52, :60 and
+ *   dinov2/layers/mlp.py:35-39, the Conv2d of dinov2/layers/patch_embed.py:75.  M is ragged: rows past M are never read and never stored.
+ *   K % 32 == 0 and N % 16 == 0 (K >= 32, N >= 16), anything else is DR_EINVAL before any access.  bias [N] or NULL.  mode:
+ *     DR_GEMM_ROWS32_COLSCALE     (acc + bias) * colscale for columns < colscale_cols (a multiple of 16; the q third of qkv takes d^-0.5,
+ *                                 layers/attention.py:54); the other columns acc + bias
+ *     DR_GEMM_ROWS32_GELU         exact erf GELU (nn.GELU() default) of acc + bias
+ *     DR_GEMM_ROWS32_SCALE_RESID  out[row] += gamma[col] * (acc + bias) in place (gamma [N], NULL = 1): LayerScale and the residual of
+ *                                 layers/block.py:83-87
+ *     DR_GEMM_ROWS32_ADDEND       acc + bias (+ addend rows [M, ld_addend >= N], or NULL): the patch embedding plus the position rows
+ *   gamma outside SCALE_RESID, addend outside ADDEND and colscale_cols != 0 outside COLSCALE are DR_EINVAL.  out [M, ldo >= N] sharing an element
+ *   with A, W, bias, gamma or addend is DR_EINVAL (in SCALE_RESID out itself is the one input it has to be).  M lda, M ldo, N ldw < 2^31, else
+ *   DR_ENOSUP.  The workgroup tile follows from (M, K, N) alone (dr_debug_gemm_rows_f32_tile forces one).
+ * dr_patch_rows_f32: the p x p patches of a [3, H, W] float32 image as float32 rows [(H / p)(W / p), ldo >= Kp], k in the order of the flattened
+ *   Conv2d weight, Kp = round_up(3 p p, 32), pad columns zero (layers/patch_embed.py:69-82).  H % p == W % p == 0.
+ * dr_vit_forward_f32: DinoVisionTransformer.forward_features and get_intermediate_layers of one image (vision_transformer.py:212-231, :253-321):
+ *   prepare_tokens_with_masks without masks or register tokens, every block (layers/block.py in eval mode, Attention.forward of
+ *   layers/attention.py:49-62), the final norm.  Writes x_prenorm [L, D] (L = 1 + patches; it IS the residual stream), x_norm [L, D], and for
+ *   each i < n_take the stream after block take[i] into take_out[i] ([L, D]) -- through the final norm when norm_take = 1
+ *   (get_intermediate_layers(..., norm=True), :309-310), as it is when norm_take = 0.  `blocks`, `take` and `take_out` are HOST arrays read
+ *   during the call; pos is the position rows [L, D] for this (H, W).  Weights are the modules' own [N, K] matrices, contiguous; patch_w is
+ *   [D, Kp] with its pad columns zero.  heads * 64 == D, Dh % 32 == 0.  The workspace holds dr_vit_workspace_bytes_f32(H, W, p, D, Dh) bytes (0
+ *   outside the domain), 256-byte aligned; less is DR_EINVAL.  The size query and the entry share one carve function. */
+#define DR_GEMM_ROWS32_COLSCALE 0
+#define DR_GEMM_ROWS32_GELU 1
+#define DR_GEMM_ROWS32_SCALE_RESID 2
+#define DR_GEMM_ROWS32_ADDEND 3
+typedef struct dr_gemm_rows_f32_args {
+    const float* a;                /* [M, lda]                                                                           */
+    const float* w;                /* [N, ldw]                                                                           */
+    const float* bias;             /* [N] or NULL                                                                        */
+    const float* gamma;            /* SCALE_RESID: [N] or NULL                                                           */
+    const float* addend;           /* ADDEND: [M, ld_addend] or NULL                                                     */
+    float* out;                    /* [M, ldo]                                                                           */
+    int M, K, N, lda, ldw, ldo, ld_addend;
+    int mode;                      /* DR_GEMM_ROWS32_*                                                                   */
+    int colscale_cols;             /* COLSCALE: columns [0, colscale_cols) are multiplied by colscale                    */
+    float colscale;
+} dr_gemm_rows_f32_args;
+typedef struct dr_vit_block_f32 {
+    const float *norm1_g, *norm1_b;
+    const float *qkv_w, *qkv_b;    /* [3 D, D], [3 D]   */
+    const float *proj_w, *proj_b;  /* [D, D], [D]       */
+    const float* ls1;              /* LayerScale gamma [D] or NULL */
+    const float *norm2_g, *norm2_b;
+    const float *fc1_w, *fc1_b;    /* [Dh, D], [Dh]     */
+    const float *fc2_w, *fc2_b;    /* [D, Dh], [D]      */
+    const float* ls2;
+} dr_vit_block_f32;
+typedef struct dr_vit_config_f32 {
+    int H, W, p, D, heads, Dh, depth;
+    float eps;
+    const float* img;              /* [3, H, W]         */
+    const float* patch_w;          /* [D, Kp]           */
+    const float* patch_b;
+    const float* cls;              /* [D]               */
+    const float* pos;              /* [L, D]            */
+    const dr_vit_block_f32* blocks;/* HOST array [depth] */
+    const float *norm_g, *norm_b;
+    float* x_prenorm;              /* out [L, D]        */
+    float* x_norm;                 /* out [L, D]        */
+    int n_take;
+    int norm_take;                 /* 1: take_out[i] = norm(stream after block take[i]) */
+    const int* take;               /* HOST [n_take] block indices */
+    float* const* take_out;        /* HOST [n_take] device pointers, [L, D] each */
+    void* workspace;
+    size_t workspace_bytes;
+} dr_vit_config_f32;
+int dr_gemm_rows_f32(const dr_gemm_rows_f32_args* args, void* stream);
+int dr_patch_rows_f32(int H, int W, int p, const float* img, float* out, int ldo, void* stream);
+size_t dr_vit_workspace_bytes_f32(int H, int W, int p, int D, int Dh);
+int dr_vit_forward_f32(const dr_vit_config_f32* cfg, void* stream);
 
 #ifdef __cplusplus
 }

@@ -84,6 +84,10 @@ void dr_debug_sinkhorn_spin_limit(unsigned polls);
 /* the workgroup tile of dr_gemm_rows_f16 (and of the GEMMs inside dr_vit_forward_f16): -1 the automatic rule (the largest tile that still gives
  * every CU a workgroup), 0 / 1 / 2 force 64 x 64 / 128 x 64 / 128 x 128; any other value makes every launch DR_EINVAL */
 void dr_debug_gemm_rows_tile(int c);
+/* the workgroup tile of dr_gemm_rows_f32 (and of the GEMMs inside dr_vit_forward_f32): -1 the automatic rule of the shape (64 x 64, with
+ * two k-groups of waves reduced through LDS when K >= 1024; the 128 x 128 tile is never chosen by it), 0 / 1 / 2 force 64 x 64 with 4 waves /
+ * 128 x 128 with 4 waves / 64 x 64 with 8 waves and the k split; any other value makes every launch DR_EINVAL */
+void dr_debug_gemm_rows_f32_tile(int c);
 /* n dependent launches of an empty kernel (tools/launch_floor.py) */
 int dr_debug_launch_chain(int n, int workgroups, int threads, void* stream);
 
