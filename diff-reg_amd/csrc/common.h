@@ -35,6 +35,9 @@ int device_cu_count();
         }                                                    \
     } while (0)
 
+// is p on a multiple of a (a power of two)?  NULL is
+inline bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
+
 __device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 __device__ __forceinline__ int wave_id() { return threadIdx.x >> 6; }
 

@@ -92,6 +92,27 @@ void attention_force_split(int on);
 int attention_last_form();
 
 // ---------------------------------------------------------------------------------------------
+// the steps both ViT encoders launch (vit.hip; the schedule is vit_forward.h): no argument checks in here, the entries make them
+// ---------------------------------------------------------------------------------------------
+// nn.LayerNorm of fp32 rows [rows, C] -> fp16 rows, or fp32 rows with out_f32
+int launch_layernorm_rows(int rows, int C, const float* x, int ldx, const float* gamma, const float* beta, float eps, int out_f32, void* out,
+                          int ldo, hipStream_t st);
+// [3, H, W] image (fp16, or fp32 with img_f32) -> patch rows [(H / p)(W / p), ldo] (fp16, or fp32 with out_f32: then the image is fp32 too)
+int launch_patch_rows(int H, int W, int p, const void* img, int img_f32, void* out, int out_f32, int ldo, hipStream_t st);
+// the domain of dr_patch_rows_f16, and with out_f32 that of dr_patch_rows_f32
+int patch_rows_check(int H, int W, int p, const void* img, const void* out, int ldo, int out_f32);
+// row 0 of the stream: cls + pos[0]
+int launch_cls_row(int D, const float* cls, const float* pos, float* stream_row, hipStream_t st);
+// the steps of a vit_forward.h policy that do not depend on the precision
+struct VitDeviceSteps {
+    static int cls_row(int D, const float* cls, const float* pos, float* x, void* st) { return launch_cls_row(D, cls, pos, x, (hipStream_t)st); }
+    static int copy_rows(void* dst, const void* src, size_t bytes, void* st) {
+        DR_HIP_CHECK(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, (hipStream_t)st));
+        return DR_OK;
+    }
+};
+
+// ---------------------------------------------------------------------------------------------
 // row-wise ops
 // ---------------------------------------------------------------------------------------------
 // out[r] = (res ? res[r] : 0) + LayerNorm(x[r]) * g + b      (eps = 1e-5)

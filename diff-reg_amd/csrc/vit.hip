@@ -7,9 +7,11 @@
 //   dr_attention_rows_f16  flash attention over packed qkv rows, d = 64, v_mfma_f32_32x32x16_f16, V by ds_read_b64_tr_b16
 //   dr_patch_rows_f16      the patch gather in front of the patch-embedding GEMM
 //   dr_vit_forward_f16     the whole encoder on one stream: no host read-back, no allocation, no atomics (two runs are bit-equal)
-// Every global offset comes from vit_index.h (tools/vit_index_check.cpp walks it on the host).
-#include "common.h"
-#include "vit_index.h"
+// The encoder's schedule, its validation order and the workspace carve are vit_forward.h's, shared with vit_f32.hip; so are the patch-gather and
+// class-row kernels and the LayerNorm launch below (kernels.h).  Every global offset comes from vit_index.h (tools/vit_index_check.cpp walks it
+// on the host).
+#include "kernels.h"
+#include "vit_forward.h"
 
 namespace dr {
 
@@ -140,8 +142,6 @@ __global__ __launch_bounds__(256) void gemm_rows_f16_kernel(GemmRowsArgs A) {
     }
 }
 
-static bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
-
 static int gemm_rows_check(const GemmRowsArgs& g) {
     if (!g.a || !g.w || !g.out || g.M < 1 || g.K < 32 || g.N < 16 || g.K % 32 || g.N % 16) return DR_EINVAL;
     if (g.mode < DR_GEMM_ROWS_F16 || g.mode > DR_GEMM_ROWS_F32) return DR_EINVAL;
@@ -211,8 +211,8 @@ __global__ __launch_bounds__(256) void layernorm_rows_kernel(int rows, int C, co
     }
 }
 
-static int layernorm_rows_launch(int rows, int C, const float* x, int ldx, const float* gamma, const float* beta, float eps, int out_f32, void* out,
-                                 int ldo, hipStream_t st) {
+int launch_layernorm_rows(int rows, int C, const float* x, int ldx, const float* gamma, const float* beta, float eps, int out_f32, void* out,
+                          int ldo, hipStream_t st) {
     const dim3 grid((rows + 3) / 4), block(256);
     if (out_f32) hipLaunchKernelGGL(layernorm_rows_kernel<true>, grid, block, 0, st, rows, C, x, ldx, gamma, beta, eps, out, ldo);
     else hipLaunchKernelGGL(layernorm_rows_kernel<false>, grid, block, 0, st, rows, C, x, ldx, gamma, beta, eps, out, ldo);
@@ -374,30 +374,34 @@ static int attention_rows_launch(int L, int H, const _Float16* qkv, int ld, _Flo
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// patch gather; the class-token row of the stream
+// patch gather; the class-token row of the stream (both precisions)
 // ---------------------------------------------------------------------------------------------------------------------
-template <typename T>
-__global__ void patch_rows_kernel(int H, int W, int p, int Np, int Kp, const T* img, _Float16* out, int ldo) {
+template <typename Tin, typename Tout>
+__global__ void patch_rows_kernel(int H, int W, int p, int Np, int Kp, const Tin* img, Tout* out, int ldo) {
     const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= (size_t)Np * Kp) return;
     const int patch = (int)(idx / Kp), k = (int)(idx % Kp);
     const long long src = vit_patch_src(H, W, p, patch, k);
-    out[(size_t)patch * ldo + k] = src < 0 ? (_Float16)0.f : (_Float16)img[src];
+    out[(size_t)patch * ldo + k] = src < 0 ? (Tout)0.f : (Tout)img[src];
 }
 
-static int patch_rows_check(int H, int W, int p, const void* img, const void* out, int ldo) {
+// float32 rows additionally want 4-byte aligned pointers and Np ldo < 2^31 (dr_patch_rows_f32's domain)
+int patch_rows_check(int H, int W, int p, const void* img, const void* out, int ldo, int out_f32) {
     if (!img || !out || p < 1 || H < p || W < p || H % p || W % p) return DR_EINVAL;
     if (p > 64 || (long long)H * W >= (1ll << 26)) return DR_ENOSUP;
     if (ldo < vit_patch_kp(p)) return DR_EINVAL;
+    if (out_f32 && (!aligned_to(img, 4) || !aligned_to(out, 4))) return DR_EINVAL;
+    if (out_f32 && (long long)(H / p) * (W / p) * ldo >= (1ll << 31)) return DR_ENOSUP;
     return DR_OK;
 }
 
-static int patch_rows_launch(int H, int W, int p, const void* img, int img_f32, _Float16* out, int ldo, hipStream_t st) {
+int launch_patch_rows(int H, int W, int p, const void* img, int img_f32, void* out, int out_f32, int ldo, hipStream_t st) {
     const int Np = (H / p) * (W / p), Kp = vit_patch_kp(p);
     const size_t n = (size_t)Np * Kp;
     const dim3 grid((unsigned)((n + 255) / 256)), block(256);
-    if (img_f32) hipLaunchKernelGGL(patch_rows_kernel<float>, grid, block, 0, st, H, W, p, Np, Kp, (const float*)img, out, ldo);
-    else hipLaunchKernelGGL(patch_rows_kernel<_Float16>, grid, block, 0, st, H, W, p, Np, Kp, (const _Float16*)img, out, ldo);
+    if (out_f32) hipLaunchKernelGGL((patch_rows_kernel<float, float>), grid, block, 0, st, H, W, p, Np, Kp, (const float*)img, (float*)out, ldo);
+    else if (img_f32) hipLaunchKernelGGL((patch_rows_kernel<float, _Float16>), grid, block, 0, st, H, W, p, Np, Kp, (const float*)img, (_Float16*)out, ldo);
+    else hipLaunchKernelGGL((patch_rows_kernel<_Float16, _Float16>), grid, block, 0, st, H, W, p, Np, Kp, (const _Float16*)img, (_Float16*)out, ldo);
     DR_LAUNCH_CHECK();
     return DR_OK;
 }
@@ -406,6 +410,51 @@ __global__ void cls_row_kernel(int D, const float* cls, const float* pos, float*
     const int c = blockIdx.x * blockDim.x + threadIdx.x;
     if (c < D) stream[c] = cls[c] + pos[c];
 }
+
+int launch_cls_row(int D, const float* cls, const float* pos, float* stream_row, hipStream_t st) {
+    hipLaunchKernelGGL(cls_row_kernel, dim3((D + 255) / 256), dim3(256), 0, st, D, cls, pos, stream_row);
+    DR_LAUNCH_CHECK();
+    return DR_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// vit_forward.h's policy for fp16 operands: every pointer a kernel reads by 16-byte vectors (pos as the patch GEMM's addend, the biases and
+// LayerScale vectors in the GEMM epilogues, the packed weights) sits on 16 bytes; a take is a raw copy of the stream (the caller norms it)
+// ---------------------------------------------------------------------------------------------------------------------
+struct VitF16 : VitDeviceSteps {
+    typedef dr_vit_config_f16 config;
+    typedef dr_vit_block_f16 block;
+    enum { ELEM = 2, COLSCALE = DR_GEMM_ROWS_F16, GELU = DR_GEMM_ROWS_GELU_F16, SCALE_RESID = DR_GEMM_ROWS_SCALE_RESID_F32, ADDEND = DR_GEMM_ROWS_F32 };
+    static int img_f32(const config& c) { return c.img_f32; }
+    static int norm_take(const config&) { return 0; }
+    static bool aligned(const config& c) {
+        return aligned_to(c.workspace, 256) && aligned_to(c.x_prenorm, 16) && aligned_to(c.pos, 16) && aligned_to(c.patch_b, 16);
+    }
+    static bool aligned(const block& b) {
+        const void* al[] = {b.qkv_w, b.proj_w, b.fc1_w, b.fc2_w, b.qkv_b, b.proj_b, b.fc1_b, b.fc2_b, b.ls1, b.ls2};
+        for (const void* q : al)
+            if (!aligned_to(q, 16)) return false;
+        return true;
+    }
+    static bool take_aligned(const void*) { return true; }
+    static int patch_rows(int H, int W, int p, const void* img, int f32, void* out, int ldo, void* st) {
+        return launch_patch_rows(H, W, p, img, f32, out, 0, ldo, (hipStream_t)st);
+    }
+    static int gemm(const void* a, int lda, int M, int K, int N, const void* w, const float* bias, int mode, void* out, int ldo, float cs, int cs_cols,
+                    const float* gamma, const float* addend, int ld_addend, void* st) {
+        GemmRowsArgs g;
+        g.a = (const _Float16*)a; g.w = (const _Float16*)w; g.bias = bias; g.gamma = gamma; g.addend = addend; g.out = out;
+        g.M = M; g.K = K; g.N = N; g.lda = lda; g.ldo = ldo; g.ld_addend = ld_addend; g.mode = mode; g.colscale_cols = cs_cols; g.colscale = cs;
+        const int rc = gemm_rows_check(g);
+        return rc != DR_OK ? rc : gemm_rows_launch(g, (hipStream_t)st);
+    }
+    static int layernorm(int L, int D, const float* x, const float* g, const float* b, float eps, void* out, void* st) {
+        return launch_layernorm_rows(L, D, x, D, g, b, eps, 0, out, D, (hipStream_t)st);
+    }
+    static int attention(int L, int heads, int D, const void* qkv, void* ao, void* st) {
+        return attention_rows_launch(L, heads, (const _Float16*)qkv, 3 * D, (_Float16*)ao, D, (hipStream_t)st);
+    }
+};
 
 }  // namespace dr
 
@@ -451,7 +500,7 @@ int dr_layernorm_rows_f16(int rows, int C, const float* x, int ldx, const float*
                           void* stream) {
     if (rows < 1 || C < 1 || !x || !out || ldx < C || ldo < C || !(eps >= 0.f) || (out_f32 != 0 && out_f32 != 1)) return DR_EINVAL;
     if ((long long)rows * ldx >= (1ll << 31) || (long long)rows * ldo >= (1ll << 31)) return DR_ENOSUP;
-    return layernorm_rows_launch(rows, C, x, ldx, gamma, beta, eps, out_f32, out, ldo, (hipStream_t)stream);
+    return launch_layernorm_rows(rows, C, x, ldx, gamma, beta, eps, out_f32, out, ldo, (hipStream_t)stream);
 }
 
 int dr_attention_rows_f16(int L, int H, int d, const void* qkv, int ldqkv, void* out, int ldo, void* stream) {
@@ -460,82 +509,14 @@ int dr_attention_rows_f16(int L, int H, int d, const void* qkv, int ldqkv, void*
 }
 
 int dr_patch_rows_f16(int H, int W, int p, const void* img, int img_f32, void* out, int ldo, void* stream) {
-    const int rc = patch_rows_check(H, W, p, img, out, ldo);
+    const int rc = patch_rows_check(H, W, p, img, out, ldo, 0);
     if (rc != DR_OK) return rc;
     if (img_f32 != 0 && img_f32 != 1) return DR_EINVAL;
-    return patch_rows_launch(H, W, p, img, img_f32, (_Float16*)out, ldo, (hipStream_t)stream);
+    return launch_patch_rows(H, W, p, img, img_f32, out, 0, ldo, (hipStream_t)stream);
 }
 
-static bool vit_dims_ok(int H, int W, int p, int D, int Dh) {
-    return p >= 1 && p <= 64 && H >= p && W >= p && H % p == 0 && W % p == 0 && D >= 64 && D % 64 == 0 && Dh >= 32 && Dh % 32 == 0 &&
-           (long long)H * W < (1ll << 26) && (long long)((H / p) * (W / p) + 1) * (Dh > 3 * D ? Dh : 3 * D) < (1ll << 31);
-}
+size_t dr_vit_workspace_bytes(int H, int W, int p, int D, int Dh) { return vit_workspace_bytes(H, W, p, D, Dh, VitF16::ELEM); }
 
-size_t dr_vit_workspace_bytes(int H, int W, int p, int D, int Dh) {
-    if (!vit_dims_ok(H, W, p, D, Dh)) return 0;
-    const int Np = (H / p) * (W / p);
-    return vit_carve(Np + 1, D, Dh, Np, vit_patch_kp(p)).total;
-}
-
-int dr_vit_forward_f16(const dr_vit_config_f16* c, void* stream) {
-    if (!c || !vit_dims_ok(c->H, c->W, c->p, c->D, c->Dh)) return DR_EINVAL;
-    const int D = c->D, Dh = c->Dh, heads = c->heads;
-    if (heads < 1 || heads * 64 != D || c->depth < 0 || (c->depth && !c->blocks) || !(c->eps >= 0.f) || (c->img_f32 != 0 && c->img_f32 != 1)) return DR_EINVAL;
-    if (!c->img || !c->patch_w || !c->cls || !c->pos || !c->x_prenorm || !c->x_norm || !c->workspace) return DR_EINVAL;
-    if (!aligned_to(c->workspace, 256) || !aligned_to(c->x_prenorm, 16) || !aligned_to(c->pos, 16) || !aligned_to(c->patch_b, 16)) return DR_EINVAL;
-    if (c->n_take < 0 || (c->n_take && (!c->take || !c->take_out))) return DR_EINVAL;
-    for (int i = 0; i < c->n_take; ++i)
-        if (c->take[i] < 0 || c->take[i] >= c->depth || !c->take_out[i]) return DR_EINVAL;
-    for (int i = 0; i < c->depth; ++i) {
-        const dr_vit_block_f16& b = c->blocks[i];
-        if (!b.qkv_w || !b.proj_w || !b.fc1_w || !b.fc2_w) return DR_EINVAL;
-        const void* al[] = {b.qkv_w, b.proj_w, b.fc1_w, b.fc2_w, b.qkv_b, b.proj_b, b.fc1_b, b.fc2_b, b.ls1, b.ls2};
-        for (const void* q : al)
-            if (!aligned_to(q, 16)) return DR_EINVAL;
-    }
-    const int Np = (c->H / c->p) * (c->W / c->p), L = Np + 1, Kp = vit_patch_kp(c->p);
-    const VitCarve cv = vit_carve(L, D, Dh, Np, Kp);          // the one carve dr_vit_workspace_bytes reports
-    if (c->workspace_bytes < cv.total) return DR_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)c->workspace;
-    _Float16* xn = (_Float16*)(ws + cv.xn);
-    _Float16* qkv = (_Float16*)(ws + cv.qkv);
-    _Float16* ao = (_Float16*)(ws + cv.ao);
-    _Float16* hid = (_Float16*)(ws + cv.hid);
-    _Float16* patches = (_Float16*)(ws + cv.patches);
-    float* x = c->x_prenorm;                                   // the fp32 residual stream lives in the x_prenorm output
-
-    auto gemm = [&](const _Float16* a, int lda, int M, int K, int N, const void* w, const float* bias, int mode, void* out, int ldo, float cs,
-                    int cs_cols, const float* gamma, const float* addend, int ld_addend) {
-        GemmRowsArgs g;
-        g.a = a; g.w = (const _Float16*)w; g.bias = bias; g.gamma = gamma; g.addend = addend; g.out = out;
-        g.M = M; g.K = K; g.N = N; g.lda = lda; g.ldo = ldo; g.ld_addend = ld_addend; g.mode = mode; g.colscale_cols = cs_cols; g.colscale = cs;
-        const int rc = gemm_rows_check(g);
-        return rc != DR_OK ? rc : gemm_rows_launch(g, st);
-    };
-    // patch_embed.py:69-82 and dinov2.py:187-196: tokens = [cls; conv(x)] + pos
-    int rc = patch_rows_launch(c->H, c->W, c->p, c->img, c->img_f32, patches, Kp, st);
-    if (rc != DR_OK) return rc;
-    hipLaunchKernelGGL(cls_row_kernel, dim3((D + 255) / 256), dim3(256), 0, st, D, c->cls, c->pos, x);
-    DR_LAUNCH_CHECK();
-    rc = gemm(patches, Kp, Np, Kp, D, c->patch_w, c->patch_b, DR_GEMM_ROWS_F32, x + D, D, 1.f, 0, nullptr, c->pos + D, D);
-    if (rc != DR_OK) return rc;
-    for (int i = 0; i < c->depth; ++i) {
-        const dr_vit_block_f16& b = c->blocks[i];
-        // block.py:83-84, attention.py:49-62: x += ls1(proj(softmax(q k^T d^-0.5) v))
-        rc = layernorm_rows_launch(L, D, x, D, b.norm1_g, b.norm1_b, c->eps, 0, xn, D, st);
-        if (rc == DR_OK) rc = gemm(xn, D, L, D, 3 * D, b.qkv_w, b.qkv_b, DR_GEMM_ROWS_F16, qkv, 3 * D, 0.125f, D, nullptr, nullptr, 0);
-        if (rc == DR_OK) rc = attention_rows_launch(L, heads, qkv, 3 * D, ao, D, st);
-        if (rc == DR_OK) rc = gemm(ao, D, L, D, D, b.proj_w, b.proj_b, DR_GEMM_ROWS_SCALE_RESID_F32, x, D, 1.f, 0, b.ls1, nullptr, 0);
-        // block.py:86-87: x += ls2(fc2(gelu(fc1(norm2(x)))))
-        if (rc == DR_OK) rc = layernorm_rows_launch(L, D, x, D, b.norm2_g, b.norm2_b, c->eps, 0, xn, D, st);
-        if (rc == DR_OK) rc = gemm(xn, D, L, D, Dh, b.fc1_w, b.fc1_b, DR_GEMM_ROWS_GELU_F16, hid, Dh, 1.f, 0, nullptr, nullptr, 0);
-        if (rc == DR_OK) rc = gemm(hid, Dh, L, Dh, D, b.fc2_w, b.fc2_b, DR_GEMM_ROWS_SCALE_RESID_F32, x, D, 1.f, 0, b.ls2, nullptr, 0);
-        if (rc != DR_OK) return rc;
-        for (int k = 0; k < c->n_take; ++k)
-            if (c->take[k] == i) DR_HIP_CHECK(hipMemcpyAsync(c->take_out[k], x, (size_t)L * D * 4, hipMemcpyDeviceToDevice, st));
-    }
-    return layernorm_rows_launch(L, D, x, D, c->norm_g, c->norm_b, c->eps, 0, c->x_norm, D, st);
-}
+int dr_vit_forward_f16(const dr_vit_config_f16* c, void* stream) { return c ? vit_forward<VitF16>(*c, stream) : DR_EINVAL; }
 
 }  // extern "C"

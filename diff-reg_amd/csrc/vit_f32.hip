@@ -4,11 +4,14 @@
 //   dr_gemm_rows_f32      out = A W^T (+ bias) on float32 rows with four epilogues; operands staged through registers into padded LDS rows
 //   dr_patch_rows_f32     the patch gather in front of the patch-embedding GEMM, float32 rows
 //   dr_vit_forward_f32    the whole encoder on one stream: no host read-back, no allocation, no atomics (two runs are bit-equal)
-// LayerNorm is dr_layernorm_rows_f16(out_f32 = 1) and the attention is launch_attention (dr_attention_f32's dispatcher) on the packed qkv rows.
+// The schedule, its validation order and the workspace carve are vit_forward.h's, shared with vit.hip, and so are the patch-gather, class-row and
+// LayerNorm kernels (vit.hip, reached through kernels.h: launch_layernorm_rows with out_f32 = 1); the attention is launch_attention
+// (dr_attention_f32's dispatcher) on the packed qkv rows.
 // Every global and LDS offset comes from vit_f32_index.h (tools/vit_f32_index_check.cpp walks it on the host).
 #include <cstring>
 #include "kernels.h"
 #include "vit_f32_index.h"
+#include "vit_forward.h"
 
 namespace dr {
 
@@ -171,8 +174,6 @@ __global__ __launch_bounds__(T::NT) void gemm_rows_f32_kernel(GemmRows32Args A) 
     }
 }
 
-static bool aligned_to(const void* p, size_t a) { return (reinterpret_cast<size_t>(p) & (a - 1)) == 0; }
-
 // do the float ranges [p, p + n) and [q, q + m) share an element?  (a NULL range shares nothing)
 static bool overlaps(const float* p, long long n, const float* q, long long m) {
     if (!p || !q) return false;
@@ -230,36 +231,46 @@ int vit_f32_configure() {
 }
 
 // ---------------------------------------------------------------------------------------------------------------------
-// patch gather; the class-token row of the stream
+// vit_forward.h's policy for float32 operands: the GEMM kernel reads its two MATRICES by float4 (16 bytes) and every vector (bias, LayerScale,
+// the position rows as addend) and its output by scalars (4 bytes); a take goes through the final norm here when norm_take is set
 // ---------------------------------------------------------------------------------------------------------------------
-__global__ void patch_rows_f32_kernel(int H, int W, int p, int Np, int Kp, const float* img, float* out, int ldo) {
-    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= (size_t)Np * Kp) return;
-    const int patch = (int)(idx / Kp), k = (int)(idx % Kp);
-    const long long src = vit_patch_src(H, W, p, patch, k);
-    out[(size_t)patch * ldo + k] = src < 0 ? 0.f : img[src];
-}
-
-static int patch_rows32_check(int H, int W, int p, const void* img, const void* out, int ldo) {
-    if (!img || !out || p < 1 || H < p || W < p || H % p || W % p) return DR_EINVAL;
-    if (p > 64 || (long long)H * W >= (1ll << 26)) return DR_ENOSUP;
-    if (ldo < vit_patch_kp(p) || !aligned_to(img, 4) || !aligned_to(out, 4)) return DR_EINVAL;
-    if ((long long)(H / p) * (W / p) * ldo >= (1ll << 31)) return DR_ENOSUP;
-    return DR_OK;
-}
-
-static int patch_rows32_launch(int H, int W, int p, const float* img, float* out, int ldo, hipStream_t st) {
-    const int Np = (H / p) * (W / p), Kp = vit_patch_kp(p);
-    const size_t n = (size_t)Np * Kp;
-    hipLaunchKernelGGL(patch_rows_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, H, W, p, Np, Kp, img, out, ldo);
-    DR_LAUNCH_CHECK();
-    return DR_OK;
-}
-
-__global__ void cls_row_f32_kernel(int D, const float* cls, const float* pos, float* stream) {
-    const int c = blockIdx.x * blockDim.x + threadIdx.x;
-    if (c < D) stream[c] = cls[c] + pos[c];
-}
+struct VitF32 : VitDeviceSteps {
+    typedef dr_vit_config_f32 config;
+    typedef dr_vit_block_f32 block;
+    enum { ELEM = 4, COLSCALE = DR_GEMM_ROWS32_COLSCALE, GELU = DR_GEMM_ROWS32_GELU, SCALE_RESID = DR_GEMM_ROWS32_SCALE_RESID, ADDEND = DR_GEMM_ROWS32_ADDEND };
+    static int img_f32(const config&) { return 1; }
+    static int norm_take(const config& c) { return c.norm_take; }
+    static bool aligned(const config& c) {
+        return aligned_to(c.workspace, 256) && aligned_to(c.x_prenorm, 16) && aligned_to(c.x_norm, 4) && aligned_to(c.pos, 4) &&
+               aligned_to(c.patch_w, 16) && aligned_to(c.img, 4);
+    }
+    static bool aligned(const block& b) {
+        return aligned_to(b.qkv_w, 16) && aligned_to(b.proj_w, 16) && aligned_to(b.fc1_w, 16) && aligned_to(b.fc2_w, 16);
+    }
+    static bool take_aligned(const void* p) { return aligned_to(p, 4); }
+    static int patch_rows(int H, int W, int p, const void* img, int f32, void* out, int ldo, void* st) {
+        return launch_patch_rows(H, W, p, img, f32, out, 1, ldo, (hipStream_t)st);
+    }
+    static int gemm(const void* a, int lda, int M, int K, int N, const void* w, const float* bias, int mode, void* out, int ldo, float cs, int cs_cols,
+                    const float* gamma, const float* addend, int ld_addend, void* st) {
+        GemmRows32Args g;
+        g.a = (const float*)a; g.w = (const float*)w; g.bias = bias; g.gamma = gamma; g.addend = addend; g.out = (float*)out;
+        g.M = M; g.K = K; g.N = N; g.lda = lda; g.ldw = K; g.ldo = ldo; g.ld_addend = ld_addend; g.mode = mode; g.colscale_cols = cs_cols; g.colscale = cs;
+        const int rc = gemm_rows32_check(g);
+        return rc != DR_OK ? rc : gemm_rows32_launch(g, (hipStream_t)st);
+    }
+    static int layernorm(int L, int D, const float* x, const float* g, const float* b, float eps, void* out, void* st) {
+        return launch_layernorm_rows(L, D, x, D, g, b, eps, 1, out, D, (hipStream_t)st);
+    }
+    static int attention(int L, int heads, int D, const void* qkv_rows, void* ao, void* st) {
+        const float* qkv = (const float*)qkv_rows;
+        AttnArgs a;
+        memset(&a, 0, sizeof(a));
+        a.q = qkv; a.k = qkv + D; a.v = qkv + 2 * D; a.out = (float*)ao; a.ldq = a.ldk = a.ldv = 3 * D; a.ldo = D; a.H = heads; a.d = 64;
+        a.nseg = 1; a.qstride = L; a.Lq = L; a.kstride = L; a.Lk = L; a.scale = 1.f;      // q carries d^-0.5 already
+        return launch_attention(a, (hipStream_t)st);
+    }
+};
 
 }  // namespace dr
 
@@ -280,100 +291,12 @@ int dr_gemm_rows_f32(const dr_gemm_rows_f32_args* a, void* stream) {
 }
 
 int dr_patch_rows_f32(int H, int W, int p, const float* img, float* out, int ldo, void* stream) {
-    const int rc = patch_rows32_check(H, W, p, img, out, ldo);
-    return rc != DR_OK ? rc : patch_rows32_launch(H, W, p, img, out, ldo, (hipStream_t)stream);
+    const int rc = patch_rows_check(H, W, p, img, out, ldo, 1);
+    return rc != DR_OK ? rc : launch_patch_rows(H, W, p, img, 1, out, 1, ldo, (hipStream_t)stream);
 }
 
-static bool vit_f32_dims_ok(int H, int W, int p, int D, int Dh) {
-    return p >= 1 && p <= 64 && H >= p && W >= p && H % p == 0 && W % p == 0 && D >= 64 && D % 64 == 0 && Dh >= 32 && Dh % 32 == 0 &&
-           (long long)H * W < (1ll << 26) && (long long)((H / p) * (W / p) + 1) * (Dh > 3 * D ? Dh : 3 * D) < (1ll << 31);
-}
+size_t dr_vit_workspace_bytes_f32(int H, int W, int p, int D, int Dh) { return vit_workspace_bytes(H, W, p, D, Dh, VitF32::ELEM); }
 
-size_t dr_vit_workspace_bytes_f32(int H, int W, int p, int D, int Dh) {
-    if (!vit_f32_dims_ok(H, W, p, D, Dh)) return 0;
-    const int Np = (H / p) * (W / p);
-    return vit_f32_carve(Np + 1, D, Dh, Np, vit_patch_kp(p)).total;
-}
-
-int dr_vit_forward_f32(const dr_vit_config_f32* c, void* stream) {
-    if (!c || !vit_f32_dims_ok(c->H, c->W, c->p, c->D, c->Dh)) return DR_EINVAL;
-    const int D = c->D, Dh = c->Dh, heads = c->heads;
-    if (heads < 1 || heads * 64 != D || c->depth < 0 || (c->depth && !c->blocks) || !(c->eps >= 0.f) || (c->norm_take != 0 && c->norm_take != 1))
-        return DR_EINVAL;
-    if (!c->img || !c->patch_w || !c->cls || !c->pos || !c->x_prenorm || !c->x_norm || !c->workspace) return DR_EINVAL;
-    if (!aligned_to(c->workspace, 256) || !aligned_to(c->x_prenorm, 16) || !aligned_to(c->x_norm, 4) || !aligned_to(c->pos, 4) ||
-        !aligned_to(c->patch_w, 16) || !aligned_to(c->img, 4))
-        return DR_EINVAL;
-    if (c->n_take < 0 || (c->n_take && (!c->take || !c->take_out))) return DR_EINVAL;
-    for (int i = 0; i < c->n_take; ++i)
-        if (c->take[i] < 0 || c->take[i] >= c->depth || !c->take_out[i] || !aligned_to(c->take_out[i], 4)) return DR_EINVAL;
-    for (int i = 0; i < c->depth; ++i) {
-        const dr_vit_block_f32& b = c->blocks[i];
-        if (!b.qkv_w || !b.proj_w || !b.fc1_w || !b.fc2_w) return DR_EINVAL;
-        const void* al[] = {b.qkv_w, b.proj_w, b.fc1_w, b.fc2_w};
-        for (const void* q : al)
-            if (!aligned_to(q, 16)) return DR_EINVAL;
-    }
-    const int Np = (c->H / c->p) * (c->W / c->p), L = Np + 1, Kp = vit_patch_kp(c->p);
-    const VitF32Carve cv = vit_f32_carve(L, D, Dh, Np, Kp);      // the one carve dr_vit_workspace_bytes_f32 reports
-    if (c->workspace_bytes < cv.total) return DR_EINVAL;
-    hipStream_t st = (hipStream_t)stream;
-    char* ws = (char*)c->workspace;
-    float* xn = (float*)(ws + cv.xn);
-    float* qkv = (float*)(ws + cv.qkv);
-    float* ao = (float*)(ws + cv.ao);
-    float* hid = (float*)(ws + cv.hid);
-    float* patches = (float*)(ws + cv.patches);
-    float* x = c->x_prenorm;                                     // the residual stream lives in the x_prenorm output
-
-    auto gemm = [&](const float* a, int lda, int M, int K, int N, const float* w, const float* bias, int mode, float* out, int ldo, float cs,
-                    int cs_cols, const float* gamma, const float* addend, int ld_addend) {
-        GemmRows32Args g;
-        g.a = a; g.w = w; g.bias = bias; g.gamma = gamma; g.addend = addend; g.out = out;
-        g.M = M; g.K = K; g.N = N; g.lda = lda; g.ldw = K; g.ldo = ldo; g.ld_addend = ld_addend; g.mode = mode; g.colscale_cols = cs_cols; g.colscale = cs;
-        const int rc = gemm_rows32_check(g);
-        return rc != DR_OK ? rc : gemm_rows32_launch(g, st);
-    };
-    auto layernorm = [&](const float* g, const float* b, float* out) {
-        return dr_layernorm_rows_f16(L, D, x, D, g, b, c->eps, 1, out, D, stream);
-    };
-    // layers/patch_embed.py:69-82 and vision_transformer.py:212-219: tokens = [cls; conv(x)] + pos
-    int rc = patch_rows32_launch(c->H, c->W, c->p, c->img, patches, Kp, st);
-    if (rc != DR_OK) return rc;
-    hipLaunchKernelGGL(cls_row_f32_kernel, dim3((D + 255) / 256), dim3(256), 0, st, D, c->cls, c->pos, x);
-    DR_LAUNCH_CHECK();
-    rc = gemm(patches, Kp, Np, Kp, D, c->patch_w, c->patch_b, DR_GEMM_ROWS32_ADDEND, x + D, D, 1.f, 0, nullptr, c->pos + D, D);
-    if (rc != DR_OK) return rc;
-    for (int i = 0; i < c->depth; ++i) {
-        const dr_vit_block_f32& b = c->blocks[i];
-        // layers/block.py:83-84, layers/attention.py:49-62: x += ls1(proj(softmax(q d^-0.5 k^T) v))
-        rc = layernorm(b.norm1_g, b.norm1_b, xn);
-        if (rc == DR_OK) rc = gemm(xn, D, L, D, 3 * D, b.qkv_w, b.qkv_b, DR_GEMM_ROWS32_COLSCALE, qkv, 3 * D, 0.125f, D, nullptr, nullptr, 0);
-        if (rc == DR_OK) {
-            AttnArgs a;
-            memset(&a, 0, sizeof(a));
-            a.q = qkv; a.k = qkv + D; a.v = qkv + 2 * D; a.out = ao; a.ldq = a.ldk = a.ldv = 3 * D; a.ldo = D; a.H = heads; a.d = 64;
-            a.nseg = 1; a.qstride = L; a.Lq = L; a.kstride = L; a.Lk = L; a.scale = 1.f;      // q carries d^-0.5 already
-            rc = launch_attention(a, st);
-        }
-        if (rc == DR_OK) rc = gemm(ao, D, L, D, D, b.proj_w, b.proj_b, DR_GEMM_ROWS32_SCALE_RESID, x, D, 1.f, 0, b.ls1, nullptr, 0);
-        // layers/block.py:86-87: x += ls2(fc2(gelu(fc1(norm2(x)))))
-        if (rc == DR_OK) rc = layernorm(b.norm2_g, b.norm2_b, xn);
-        if (rc == DR_OK) rc = gemm(xn, D, L, D, Dh, b.fc1_w, b.fc1_b, DR_GEMM_ROWS32_GELU, hid, Dh, 1.f, 0, nullptr, nullptr, 0);
-        if (rc == DR_OK) rc = gemm(hid, Dh, L, Dh, D, b.fc2_w, b.fc2_b, DR_GEMM_ROWS32_SCALE_RESID, x, D, 1.f, 0, b.ls2, nullptr, 0);
-        if (rc != DR_OK) return rc;
-        // vision_transformer.py:271-281, :309-310: the stream after a taken block, through the final norm when norm_take is set
-        for (int k = 0; k < c->n_take; ++k) {
-            if (c->take[k] != i) continue;
-            if (c->norm_take) {
-                rc = layernorm(c->norm_g, c->norm_b, c->take_out[k]);
-                if (rc != DR_OK) return rc;
-            } else {
-                DR_HIP_CHECK(hipMemcpyAsync(c->take_out[k], x, (size_t)L * D * 4, hipMemcpyDeviceToDevice, st));
-            }
-        }
-    }
-    return layernorm(c->norm_g, c->norm_b, c->x_norm);
-}
+int dr_vit_forward_f32(const dr_vit_config_f32* c, void* stream) { return c ? vit_forward<VitF32>(*c, stream) : DR_EINVAL; }
 
 }  // extern "C"

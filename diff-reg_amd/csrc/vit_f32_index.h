@@ -1,7 +1,7 @@
 // vit_f32_index.h -- the index arithmetic of the float32 ViT encoder kernels (vit_f32.hip): the tile geometries of the float32 rows GEMM, the
 // global source and the LDS position of every staging slot (ragged last row tile, ragged last column tile), where a lane's accumulator registers
-// land in the output, the LDS slots of the in-workgroup k reduction and the workspace carve.  The patch gather is vit_index.h's (the same
-// arithmetic: vit_patch_kp, vit_patch_src).  The kernels compute every global and LDS offset through these functions and nothing else, and
+// land in the output and the LDS slots of the in-workgroup k reduction.  The patch gather is vit_index.h's (the same arithmetic: vit_patch_kp,
+// vit_patch_src) and the workspace carve vit_forward.h's.  The kernels compute every global and LDS offset through these functions and nothing else, and
 // tools/vit_f32_index_check.cpp walks the same functions on the host over the tested and the production shapes.  No HIP type in here: plain C++.
 #pragma once
 #include "vit_index.h"
@@ -60,21 +60,5 @@ DR_VHD int vit_f32_acc_row(int r, int h) { return (r & 3) + 8 * (r >> 2) + 4 * h
 DR_VHD long long vit_f32_out_at(int row, int ld, int col) { return (long long)row * ld + col; }
 // the k reduction: wave w parks register r of its tile (i, j) at this float offset; k-group 0 adds the others in the order 1 .. WK - 1
 DR_VHD int vit_f32_red_at(int w, int TM, int TN, int i, int j, int r, int lane) { return (((w * TM + i) * TN + j) * 16 + r) * 64 + lane; }
-
-// ---- workspace of dr_vit_forward_f32 -------------------------------------------------------------------------------------------------------
-struct VitF32Carve {
-    size_t xn, qkv, ao, hid, patches, total;      // byte offsets (256-byte aligned) and the total
-};
-DR_VHD VitF32Carve vit_f32_carve(int L, int D, int Dh, int Np, int Kp) {
-    VitF32Carve c;
-    size_t o = 0;
-    c.xn = o; o = vit_align256(o + (size_t)L * D * 4);
-    c.qkv = o; o = vit_align256(o + (size_t)L * 3 * D * 4);
-    c.ao = o; o = vit_align256(o + (size_t)L * D * 4);
-    c.hid = o; o = vit_align256(o + (size_t)L * Dh * 4);
-    c.patches = o; o = vit_align256(o + (size_t)Np * Kp * 4);
-    c.total = o;
-    return c;
-}
 
 }  // namespace dr

@@ -1,7 +1,8 @@
 // vit_index.h -- the index arithmetic of the fp16 ViT encoder kernels (vit.hip): the patch gather, the LDS-DMA staging of the rows GEMM's two
-// operands (ragged last row tile), the packed weight image, the K / V tile staging of the rows attention (ragged last key tile) and the workspace
-// carve.  The kernels compute every global offset through these functions and nothing else, and tools/vit_index_check.cpp walks the same
-// functions on the host over the tested and the production shapes before anything runs on a device.  No HIP type in here: plain C++.
+// operands (ragged last row tile), the packed weight image and the K / V tile staging of the rows attention (ragged last key tile).  (The
+// workspace carve is vit_forward.h's, one for both precisions.)  The kernels compute every global offset through these functions and nothing
+// else, and tools/vit_index_check.cpp walks the same functions on the host over the tested and the production shapes before anything runs on a
+// device.  No HIP type in here: plain C++.
 #pragma once
 #include <stddef.h>
 
@@ -63,23 +64,6 @@ DR_VHD long long vit_kv_src(int L, int ld, int H, int head, int which, int kt, i
     if (key > L - 1) key = L - 1;
     const int unit = (lane & 7) ^ (which == 1 ? vit_k_swz(r) : vit_v_swz(r));
     return (long long)key * ld + (which * H + head) * 64 + unit * 8;
-}
-
-// ---- workspace of dr_vit_forward_f16 -----------------------------------------------------------------------------------------------------
-struct VitCarve {
-    size_t xn, qkv, ao, hid, patches, total;      // byte offsets (256-byte aligned) and the total
-};
-DR_VHD size_t vit_align256(size_t v) { return (v + 255) & ~(size_t)255; }
-DR_VHD VitCarve vit_carve(int L, int D, int Dh, int Np, int Kp) {
-    VitCarve c;
-    size_t o = 0;
-    c.xn = o; o = vit_align256(o + (size_t)L * D * 2);
-    c.qkv = o; o = vit_align256(o + (size_t)L * 3 * D * 2);
-    c.ao = o; o = vit_align256(o + (size_t)L * D * 2);
-    c.hid = o; o = vit_align256(o + (size_t)L * Dh * 2);
-    c.patches = o; o = vit_align256(o + (size_t)Np * Kp * 2);
-    c.total = o;
-    return c;
 }
 
 }  // namespace dr

@@ -126,19 +126,37 @@ def _refuse(why):
 def _no_dropout(m, where):
     for sub in m.modules():
         if isinstance(sub, nn.Dropout) and sub.p != 0.0:
-            _refuse("non-zero dropout (%s)" % where)
+            _refuse("non-zero dropout (%s)" % where)          # (names DeviceViT for either class: the text is kept as it was)
 
 
-class DeviceViT:
+class DeviceEncoder:
+    """What DeviceViT (fp16, below) and depth_encoder2d3d.DeviceViTF32 (float32) share: the bind-time walk of the module, the cache of prepared
+    weights and position rows, the per-block pointer rows, one image through the C entry, and the reference's two methods on top.  A subclass states
+    its dtype, how a weight is prepared, its ctypes structs and entry, and who applies the final norm to a take ("the policy")."""
+    DTYPE = None                # every parameter's dtype, and what the refusal says otherwise
+    DTYPE_REFUSAL = None
+    X_NORM_DTYPE = None
+    BLOCK_C = CONFIG_C = None   # lib's ctypes structs
+    ENTRY = WORKSPACE_BYTES = None
+
+    @classmethod
+    def _refuse(cls, why):
+        raise NotImplementedError("libdiffreg_hip: %s has no device form for %s" % (cls.__name__, why))
+
+    def _refuse_module(self, module):
+        """what only this precision refuses, asked right behind the patch embedding's checks"""
+
     def __init__(self, module):
         self.module = module
         self.blocks = _flat_blocks(module.blocks)
+        _refuse = self._refuse
         pe = module.patch_embed
         if not isinstance(getattr(pe, "norm", nn.Identity()), nn.Identity):
             _refuse("a patch_embed.norm")
         ps = module.patch_size if isinstance(module.patch_size, int) else module.patch_size[0]
         if tuple(pe.proj.kernel_size) != (ps, ps) or tuple(pe.proj.stride) != (ps, ps) or pe.proj.in_channels != 3:
             _refuse("a patch embedding other than Conv2d(3, D, p, stride p)")
+        self._refuse_module(module)
         self.p = ps
         self.D = D = module.cls_token.shape[-1]
         self.heads = module.num_heads
@@ -171,33 +189,32 @@ class DeviceViT:
                 _refuse("stochastic depth (block %d)" % i)
         self.eps = float(module.norm.eps)
         for prm in module.parameters():
-            if prm.dtype != torch.float16:
-                _refuse("a module that is not in torch.float16 (the fp32 use of this class is Depth-Anything: out of scope)")
-        self._packed = {}
+            if prm.dtype != self.DTYPE:
+                _refuse(self.DTYPE_REFUSAL)
+        self._cache = {}
         self._pos = {}
         self._blocks_c = None
-        self._blocks_key = None
 
-    # ---- weights: packed once, re-packed when a parameter's version or storage changes
+    # ---- weights: prepared once (_matrix, _vector, _patch_w of the subclass), prepared again when a parameter's version or storage changes
     def _cached(self, name, prm, make):
         key = (prm._version, prm.data_ptr(), prm.device, tuple(prm.shape))
-        hit = self._packed.get(name)
+        hit = self._cache.get(name)
         if hit is None or hit[0] != key:
             with torch.no_grad():
                 hit = (key, make(prm.detach()))
-            self._packed[name] = hit
+            self._cache[name] = hit
             self._blocks_c = None
         return hit[1]
 
     def _w(self, name, lin):
-        return self._cached(name, lin.weight, lambda w: pack_weight_f16(w.reshape(w.shape[0], -1).contiguous()))
+        return self._cached(name, lin.weight, self._matrix)
 
     def _f(self, name, prm):
-        return None if prm is None else self._cached(name, prm, lambda v: v.float().reshape(-1).contiguous())
+        return None if prm is None else self._cached(name, prm, self._vector)
 
     def _weights(self):
         m = self.module
-        W = dict(patch_w=self._w("patch.w", m.patch_embed.proj), patch_b=self._f("patch.b", m.patch_embed.proj.bias),
+        W = dict(patch_w=self._cached("patch.w", m.patch_embed.proj.weight, self._patch_w), patch_b=self._f("patch.b", m.patch_embed.proj.bias),
                  cls=self._f("cls", m.cls_token), norm_g=self._f("norm.g", m.norm.weight), norm_b=self._f("norm.b", m.norm.bias))
         rows = []
         for i, b in enumerate(self.blocks):
@@ -208,9 +225,9 @@ class DeviceViT:
                          self._w(n + "fc1", b.mlp.fc1), self._f(n + "fc1b", b.mlp.fc1.bias), self._w(n + "fc2", b.mlp.fc2),
                          self._f(n + "fc2b", b.mlp.fc2.bias), self._f(n + "ls2", getattr(b.ls2, "gamma", None))])
         if self._blocks_c is None:
-            arr = (lib.VitBlockF16 * len(rows))()
+            arr = (self.BLOCK_C * len(rows))()
             for i, r in enumerate(rows):
-                arr[i] = lib.VitBlockF16(*[None if t is None else t.data_ptr() for t in r])
+                arr[i] = self.BLOCK_C(*[None if t is None else t.data_ptr() for t in r])
             self._blocks_c = arr
         return W
 
@@ -223,63 +240,61 @@ class DeviceViT:
             L = 1 + (H // self.p) * (W // self.p)
             with torch.no_grad():
                 rows = m.interpolate_pos_encoding(torch.empty(1, L, self.D, dtype=pe.dtype, device=pe.device), H, W)
-            hit = (key, rows.detach().reshape(L, self.D).float().contiguous())
+            # (a copy of its own: at the trained size the module hands back pos_embed itself)
+            hit = (key, rows.detach().reshape(L, self.D).to(torch.float32, copy=True).contiguous())
             self._pos[(H, W)] = hit
         return hit[1]
 
     # ---- one image
-    def _run(self, img, take=()):
-        """img [3, H, W] -> (x_prenorm fp32 [L, D], x_norm fp16 [L, D], [stream after block i for i in take])"""
+    def _run(self, img, take=(), norm=False, workspace=None):
+        """img [3, H, W] -> (x_prenorm fp32 [L, D], x_norm [L, D], [the fp32 stream after block i for i in take]); with `norm` (a subclass whose
+        entry has norm_take) a take went through the final norm"""
         _, H, Wd = img.shape
         if H % self.p or Wd % self.p:
             raise AssertionError("Input image size %d x %d is not a multiple of the patch size %d" % (H, Wd, self.p))
         lib.ensure_init()
-        if img.dtype not in (torch.float16, torch.float32):
-            img = img.to(torch.float16)
-        img = img.contiguous()
+        img = self._image(img).contiguous()
         Wt = self._weights()
         pos = self._pos_rows(H, Wd)
         L, D, dev = pos.shape[0], self.D, img.device
-        wsb = vit_workspace_bytes(H, Wd, self.p, D, self.Dh)
+        wsb = getattr(lib.raw(), self.WORKSPACE_BYTES)(H, Wd, self.p, D, self.Dh)
         if wsb == 0:
-            raise NotImplementedError("libdiffreg_hip: dr_vit_forward_f16 does not take this geometry")
-        ws = torch.empty(wsb, dtype=torch.uint8, device=dev)
+            raise NotImplementedError("libdiffreg_hip: %s does not take this geometry" % self.ENTRY)
+        ws = torch.empty(wsb, dtype=torch.uint8, device=dev) if workspace is None else workspace
         x_pre = torch.empty(L, D, dtype=torch.float32, device=dev)
-        x_norm = torch.empty(L, D, dtype=torch.float16, device=dev)
+        x_norm = torch.empty(L, D, dtype=self.X_NORM_DTYPE, device=dev)
         outs = [torch.empty(L, D, dtype=torch.float32, device=dev) for _ in take]
         take_c = (ctypes.c_int * max(len(take), 1))(*take)
         out_c = (ctypes.c_void_p * max(len(take), 1))(*[o.data_ptr() for o in outs])
-        cfg = lib.VitConfigF16(H, Wd, self.p, D, self.heads, self.Dh, len(self.blocks), self.eps, img.data_ptr(),
-                               1 if img.dtype == torch.float32 else 0, _p(Wt["patch_w"]), _p(Wt["patch_b"]), _p(Wt["cls"]), _p(pos), self._blocks_c,
-                               _p(Wt["norm_g"]), _p(Wt["norm_b"]), _p(x_pre), _p(x_norm), len(take), take_c, out_c, _p(ws), wsb)
-        lib.check(lib.raw().dr_vit_forward_f16(ctypes.byref(cfg), lib.stream_of(img)))
+        cfg = self.CONFIG_C(H=H, W=Wd, p=self.p, D=D, heads=self.heads, Dh=self.Dh, depth=len(self.blocks), eps=self.eps, img=img.data_ptr(),
+                            patch_w=_p(Wt["patch_w"]), patch_b=_p(Wt["patch_b"]), cls=_p(Wt["cls"]), pos=_p(pos), blocks=self._blocks_c,
+                            norm_g=_p(Wt["norm_g"]), norm_b=_p(Wt["norm_b"]), x_prenorm=_p(x_pre), x_norm=_p(x_norm), n_take=len(take), take=take_c,
+                            take_out=out_c, workspace=_p(ws), workspace_bytes=ws.numel(), **self._flags(img, norm))
+        lib.check(getattr(lib.raw(), self.ENTRY)(ctypes.byref(cfg), lib.stream_of(img)))
         return x_pre, x_norm, outs
 
-    # ---- the reference's interface (dinov2.py:213-237, :266-292)
+    # ---- the reference's interface (dinov2.py:213-237, :266-292; the hub's vision_transformer.py:253-269, :297-321)
     def forward_features(self, x, masks=None):
         if masks is not None:
-            raise NotImplementedError("libdiffreg_hip: DeviceViT.forward_features takes no masks")
+            raise NotImplementedError("libdiffreg_hip: %s.forward_features takes no masks" % type(self).__name__)
         if isinstance(x, (list, tuple)):
-            raise NotImplementedError("libdiffreg_hip: DeviceViT.forward_features takes one batch tensor, not a list")
+            raise NotImplementedError("libdiffreg_hip: %s.forward_features takes one batch tensor, not a list" % type(self).__name__)
         pre, nrm = [], []
         for b in range(x.shape[0]):                  # B > 1 loops over the images
             xp, xn, _ = self._run(x[b])
-            pre.append(xp.to(torch.float16))
+            pre.append(xp.to(self.X_NORM_DTYPE))     # (x_prenorm goes out in the module's dtype: a cast per image in fp16, nothing in float32)
             nrm.append(xn)
-        x_norm, x_pre = torch.stack(nrm), torch.stack(pre)
-        return {"x_norm_clstoken": x_norm[:, 0], "x_norm_patchtokens": x_norm[:, 1:], "x_prenorm": x_pre, "masks": masks}
+        return self._features(torch.stack(nrm), torch.stack(pre), masks)
 
     def get_intermediate_layers(self, x, n=1, reshape=False, return_class_token=False, norm=True):
         depth = len(self.blocks)
         take = list(range(depth - n, depth)) if isinstance(n, int) else list(n)
         if any(i < 0 or i >= depth for i in take):
             raise AssertionError("only %d blocks" % depth)
-        Wt = self._weights()
         per_layer = [[] for _ in take]
         for b in range(x.shape[0]):
-            _, _, outs = self._run(x[b], take)
-            for k, o in enumerate(outs):
-                per_layer[k].append(layernorm_rows_f16(o, Wt["norm_g"], Wt["norm_b"], self.eps) if norm else o.to(torch.float16))
+            for k, o in enumerate(self._takes(x[b], take, norm)):
+                per_layer[k].append(o)
         outputs = [torch.stack(rows) for rows in per_layer]
         class_tokens = [o[:, 0] for o in outputs]
         outputs = [o[:, 1:] for o in outputs]
@@ -289,6 +304,42 @@ class DeviceViT:
         if return_class_token:
             return tuple(zip(outputs, class_tokens))
         return tuple(outputs)
+
+
+class DeviceViT(DeviceEncoder):
+    DTYPE, X_NORM_DTYPE = torch.float16, torch.float16
+    DTYPE_REFUSAL = "a module that is not in torch.float16 (the fp32 use of this class is Depth-Anything: out of scope)"
+    BLOCK_C, CONFIG_C = lib.VitBlockF16, lib.VitConfigF16
+    ENTRY, WORKSPACE_BYTES = "dr_vit_forward_f16", "dr_vit_workspace_bytes"
+
+    # weights: packed images and float32 copies
+    @staticmethod
+    def _matrix(w):
+        return pack_weight_f16(w.reshape(w.shape[0], -1).contiguous())
+
+    _patch_w = _matrix
+
+    @staticmethod
+    def _vector(v):
+        return v.float().reshape(-1).contiguous()
+
+    @staticmethod
+    def _image(img):
+        return img if img.dtype in (torch.float16, torch.float32) else img.to(torch.float16)
+
+    @staticmethod
+    def _flags(img, norm):
+        assert not norm, "dr_vit_forward_f16 has no norm_take: _takes norms"
+        return dict(img_f32=1 if img.dtype == torch.float32 else 0)
+
+    def _features(self, x_norm, x_pre, masks):
+        return {"x_norm_clstoken": x_norm[:, 0], "x_norm_patchtokens": x_norm[:, 1:], "x_prenorm": x_pre, "masks": masks}
+
+    def _takes(self, img, take, norm):
+        """the entry hands back the raw fp32 streams: the final norm (or the cast) to fp16 rows is a launch of its own"""
+        Wt = self._weights()
+        outs = self._run(img, take)[2]
+        return [layernorm_rows_f16(o, Wt["norm_g"], Wt["norm_b"], self.eps) if norm else o.to(torch.float16) for o in outs]
 
 
 class Binding:

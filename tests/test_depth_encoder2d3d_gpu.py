@@ -277,6 +277,72 @@ def test_encoder_workspace_query_is_sufficient_and_one_byte_less_is_refused(E, f
         dev._run(x, workspace=ws[:n - 1])
 
 
+def shifted(t):
+    """the values of t one float further on in an allocation with slack: data_ptr() + 4 is a 4-byte-aligned, in-bounds copy"""
+    buf = torch.zeros(t.numel() + 4, dtype=t.dtype, device=t.device)
+    buf[1:1 + t.numel()] = t.reshape(-1)
+    return buf
+
+
+def test_forward_refusal_domain(E):
+    """dr_vit_forward_f32's own domain, one field perturbed per case: the workspace on 256 bytes, x_prenorm and every weight MATRIX on 16, every
+    vector (pos, a bias) on 4 only, norm_take a flag, the takes inside the depth, eps >= 0, the queried workspace size.  A refusal is DR_EINVAL
+    before any launch (outputs and workspace stay poisoned); a vector moved by 4 bytes is taken and gives the same bits.  28 x 28 image, D = 64,
+    one head, Dh = 128, one block."""
+    from diffreg_hip import lib
+    POISON = 777.0
+    vit = R.draw_weights(R.ViTF32(patch_size=14, img_size=28, embed_dim=64, depth=1, num_heads=1, mlp_ratio=2).to(DEV).eval(), seed=11)
+    dev = E.DeviceViTF32(vit)
+    L, D, Dh = 5, 64, 128
+    img = torch.randn(3, 28, 28, generator=gen(12), device=DEV)
+    Wt, pos = dev._weights(), dev._pos_rows(28, 28)
+    need = E.vit_workspace_bytes_f32(28, 28, 14, D, Dh)
+    assert need > 0
+    sh = dict(pos=shifted(pos), patch_w=shifted(Wt["patch_w"]), qkv_w=shifted(vit.blocks[0].attn.qkv.weight),
+              qkv_b=shifted(vit.blocks[0].attn.qkv.bias))
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+
+    def run(change):
+        c = types.SimpleNamespace()
+        c.ws = torch.full((need + 4096,), 0x5A, dtype=torch.uint8, device=DEV)
+        c.outs = [torch.full((L + 3, D), POISON, device=DEV) for _ in range(3)]
+        c.blocks = (lib.VitBlockF32 * 1)(dev._blocks_c[0])
+        c.take, c.take_out = (ctypes.c_int * 1)(0), (ctypes.c_void_p * 1)(c.outs[2].data_ptr())
+        c.cfg = lib.VitConfigF32(28, 28, 14, D, 1, Dh, 1, 1e-6, img.data_ptr(), p(Wt["patch_w"]), p(Wt["patch_b"]), p(Wt["cls"]), p(pos), c.blocks,
+                                 p(Wt["norm_g"]), p(Wt["norm_b"]), p(c.outs[0]), p(c.outs[1]), 1, 1, c.take, c.take_out, p(c.ws), need)
+        change(c)
+        c.rc = lib.raw().dr_vit_forward_f32(ctypes.byref(c.cfg), lib.stream_of(img))
+        torch.cuda.synchronize()
+        return c
+
+    field = lambda name, value: lambda c: setattr(c.cfg, name, value(c) if callable(value) else value)
+    block = lambda name: lambda c: setattr(c.blocks[0], name, sh[name].data_ptr() + 4)
+    refused = {
+        "workspace + 128 B": field("workspace", lambda c: c.cfg.workspace + 128),
+        "x_prenorm + 4 B": field("x_prenorm", lambda c: c.cfg.x_prenorm + 4),
+        "patch_w + 4 B": field("patch_w", sh["patch_w"].data_ptr() + 4),
+        "a block's qkv_w + 4 B": block("qkv_w"),
+        "norm_take = 2": field("norm_take", 2),
+        "take[0] = depth": lambda c: c.take.__setitem__(0, 1),
+        "eps = NaN": field("eps", NAN),
+        "workspace_bytes - 1": field("workspace_bytes", need - 1),
+    }
+    taken = {"pos + 4 B": field("pos", sh["pos"].data_ptr() + 4), "a block's qkv_b + 4 B": block("qkv_b")}
+    for name, change in refused.items():
+        c = run(change)
+        print("dr_vit_forward_f32, %s: status %d" % (name, c.rc))
+        assert c.rc == DR_EINVAL, name
+        assert all(bool((o == POISON).all()) for o in c.outs) and bool((c.ws == 0x5A).all()), name
+    base = run(lambda c: None)                                                        # the unperturbed call is inside the domain
+    assert base.rc == DR_OK and not any(bool((o[:L] == POISON).any()) for o in base.outs)
+    for name, change in taken.items():
+        c = run(change)
+        print("dr_vit_forward_f32, %s: status %d" % (name, c.rc))
+        assert c.rc == DR_OK, name
+        assert all(torch.equal(o, b) for o, b in zip(c.outs, base.outs)), name        # (the guard rows behind the L rows included)
+        assert bool((c.ws[need:] == 0x5A).all()), name
+
+
 def test_production_width_block_against_float64(E):
     """D = 1 024, 16 heads, one block, 131 tokens: the GEMM shapes' K and N of ViT-L/14 (qkv 3 072, fc1 4 096, fc2 over K = 4 096)"""
     vit = R.ViTF32(patch_size=14, img_size=70, embed_dim=1024, depth=1, num_heads=16, mlp_ratio=4).to(DEV).eval()

@@ -10,6 +10,7 @@ Bars.  Error measure everywhere: max |a - ref64| over a tensor, ref6
    bind-time refusals / re-pack after an in-place weight update; one production-width case (D = 1024, 16 heads, one block).
 """
 import ctypes
+import types
 
 import numpy as np
 import pytest
@@ -333,6 +334,65 @@ def test_workspace_query_is_sufficient_and_one_byte_less_is_refused(V, fx, fvit)
     torch.cuda.synchronize()
     assert torch.equal(x_pre[:131], ref_pre) and torch.equal(x_norm[:131], ref_norm)
     assert bool((ws[need:] == 0x5A).all()) and bool((x_pre[131:] == POISON).all()) and bool((x_norm[131:] == POISON).all())
+
+
+def shifted(t):
+    """the values of t one float further on in an allocation with slack: data_ptr() + 4 is a 4-byte-aligned, in-bounds copy"""
+    buf = torch.zeros(t.numel() + 4, dtype=t.dtype, device=t.device)
+    buf[1:1 + t.numel()] = t.reshape(-1)
+    return buf
+
+
+def test_forward_refusal_domain(V):
+    """dr_vit_forward_f16's own domain, one field perturbed per case: the workspace on 256 bytes, x_prenorm, pos, patch_b and every block pointer on
+    16, the takes inside the depth, heads x 64 = D, eps >= 0, img_f32 a flag, the queried workspace size.  Every case is DR_EINVAL before any
+    launch: outputs and workspace stay poisoned.  28 x 28 image, D = 64, one head, Dh = 128, one block."""
+    from diffreg_hip import lib
+    vit = R.draw_weights(small().to(DEV), seed=11).eval()
+    dev = V.DeviceViT(vit)
+    L, D, Dh = 5, 64, 128
+    img = torch.randn(3, 28, 28, generator=torch.Generator(device=DEV).manual_seed(12), device=DEV).half()
+    Wt, pos = dev._weights(), dev._pos_rows(28, 28)
+    need = V.vit_workspace_bytes(28, 28, 14, D, Dh)
+    assert need > 0
+    sh = dict(pos=shifted(pos), patch_b=shifted(Wt["patch_b"]), qkv_b=shifted(vit.blocks[0].attn.qkv.bias.float()))
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+
+    def run(change):
+        c = types.SimpleNamespace()
+        c.ws = torch.full((need + 4096,), 0x5A, dtype=torch.uint8, device=DEV)
+        c.outs = [torch.full((L + 3, D), POISON, dtype=dt, device=DEV) for dt in (torch.float32, torch.float16, torch.float32)]
+        c.blocks = (lib.VitBlockF16 * 1)(dev._blocks_c[0])
+        c.take, c.take_out = (ctypes.c_int * 1)(0), (ctypes.c_void_p * 1)(c.outs[2].data_ptr())
+        c.cfg = lib.VitConfigF16(28, 28, 14, D, 1, Dh, 1, 1e-6, img.data_ptr(), 0, p(Wt["patch_w"]), p(Wt["patch_b"]), p(Wt["cls"]), p(pos),
+                                 c.blocks, p(Wt["norm_g"]), p(Wt["norm_b"]), p(c.outs[0]), p(c.outs[1]), 1, c.take, c.take_out, p(c.ws), need)
+        change(c)
+        c.rc = lib.raw().dr_vit_forward_f16(ctypes.byref(c.cfg), lib.stream_of(img))
+        torch.cuda.synchronize()
+        return c
+
+    field = lambda name, value: lambda c: setattr(c.cfg, name, value(c) if callable(value) else value)
+    cases = {
+        "workspace + 128 B": field("workspace", lambda c: c.cfg.workspace + 128),
+        "x_prenorm + 4 B": field("x_prenorm", lambda c: c.cfg.x_prenorm + 4),
+        "pos + 4 B": field("pos", sh["pos"].data_ptr() + 4),
+        "patch_b + 4 B": field("patch_b", sh["patch_b"].data_ptr() + 4),
+        "a block's qkv_b + 4 B": lambda c: setattr(c.blocks[0], "qkv_b", sh["qkv_b"].data_ptr() + 4),
+        "take[0] = depth": lambda c: c.take.__setitem__(0, 1),
+        "a NULL take_out[0]": lambda c: c.take_out.__setitem__(0, None),
+        "heads = 2": field("heads", 2),
+        "eps = NaN": field("eps", float("nan")),
+        "img_f32 = 2": field("img_f32", 2),
+        "workspace_bytes - 1": field("workspace_bytes", need - 1),
+    }
+    for name, change in cases.items():
+        c = run(change)
+        print("dr_vit_forward_f16, %s: status %d" % (name, c.rc))
+        assert c.rc == EINVAL, name
+        assert all(bool((o == POISON).all()) for o in c.outs) and bool((c.ws == 0x5A).all()), name
+    base = run(lambda c: None)                                      # the unperturbed call is inside the domain
+    assert base.rc == 0 and not any(bool((o[:L] == POISON).any()) for o in base.outs)
+    assert all(bool((o[L:] == POISON).all()) for o in base.outs) and bool((base.ws[need:] == 0x5A).all())
 
 
 # ---- binding ------------------------------------------------------------------------------------------------------------------------------------

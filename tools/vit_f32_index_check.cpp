@@ -14,7 +14,8 @@
 //     accumulator register's store lands inside `out`, on a distinct element, and all of out[M, N] is covered exactly once; the k reduction's
 //     slots are distinct and inside the kernel's LDS;
 //   the tile rule: the production shapes take the tiles DESIGN 5r names;
-//   workspace: the carve's regions are disjoint, aligned and inside the total.
+//   workspace: the carve's regions are disjoint, aligned and inside the total, which is what the size query reports.
+// The patch and the workspace walks are tools/vit_check_common.h's, shared with tools/vit_index_check.cpp.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -34,24 +35,7 @@ static long long g_slots = 0;
         }                                                                                 \
     } while (0)
 
-static void check_patches(int H, int W, int p) {
-    const int Np = (H / p) * (W / p), Kp = vit_patch_kp(p);
-    CHECK(Kp % 32 == 0 && Kp >= 3 * p * p && Kp - 3 * p * p < 32);
-    std::vector<float> img((size_t)3 * H * W, 1.f), rows((size_t)Np * Kp, -1.f);
-    std::vector<unsigned char> seen(img.size(), 0);
-    for (int patch = 0; patch < Np; ++patch)
-        for (int k = 0; k < Kp; ++k) {
-            const long long s = vit_patch_src(H, W, p, patch, k);
-            if (k >= 3 * p * p) CHECK(s == -1);
-            else {
-                CHECK(s >= 0 && s < (long long)img.size() && !seen[s]);
-                seen[s] = 1;
-            }
-            rows.data()[(size_t)patch * Kp + k] = s < 0 ? 0.f : img.data()[s];
-            ++g_slots;
-        }
-    for (unsigned char v : seen) CHECK(v);
-}
+#include "vit_check_common.h"      // check_patches, check_carve
 
 // one operand's staging of one chunk by all threads of the workgroup, then what the fragment reads expect
 template <class T>
@@ -172,24 +156,11 @@ static void check_gemm(int M, int K, int N, int lda, int ldw, int ldo) {
     check_gemm_tile<VitF32Tile2>(M, K, N, lda, ldw, ldo);
 }
 
-static void check_carve(int H, int W, int p, int D, int Dh) {
-    const int Np = (H / p) * (W / p), L = Np + 1, Kp = vit_patch_kp(p);
-    const VitF32Carve c = vit_f32_carve(L, D, Dh, Np, Kp);
-    const size_t off[5] = {c.xn, c.qkv, c.ao, c.hid, c.patches};
-    const size_t len[5] = {(size_t)L * D * 4, (size_t)L * 3 * D * 4, (size_t)L * D * 4, (size_t)L * Dh * 4, (size_t)Np * Kp * 4};
-    for (int i = 0; i < 5; ++i) {
-        CHECK(off[i] % 256 == 0 && off[i] + len[i] <= c.total);
-        if (i) CHECK(off[i] >= off[i - 1] + len[i - 1]);
-    }
-    std::vector<unsigned char> ws(c.total, 0);
-    for (int i = 0; i < 5; ++i) ws.data()[off[i]] = ws.data()[off[i] + len[i] - 1] = 1;
-}
-
 int main() {
     static_assert(VitF32Tile0::SMEM_FLOATS * 4 <= 160 * 1024 && VitF32Tile1::SMEM_FLOATS * 4 <= 160 * 1024 && VitF32Tile2::SMEM_FLOATS * 4 <= 160 * 1024,
                   "a tile's LDS");
     const int images[][2] = {{476, 630}, {42, 70}, {70, 70}, {140, 182}};
-    for (const auto& im : images) check_patches(im[0], im[1], 14);
+    for (const auto& im : images) check_patches<float>(im[0], im[1], 14);
     const int Ms[] = {1, 31, 33, 129, 131}, Ks[] = {32, 128, 608, 1024, 4096}, Ns[] = {16, 128, 384};
     for (int M : Ms)
         for (int K : Ks)
@@ -222,11 +193,11 @@ int main() {
     CHECK(vit_f32_tile_rule(1531, 1024, 1024) == 2);
     CHECK(vit_f32_tile_rule(1531, 1024, 4096) == 2);
     CHECK(vit_f32_tile_rule(1531, 4096, 1024) == 2);
-    check_carve(476, 630, 14, 1024, 4096);
-    check_carve(42, 70, 14, 128, 512);
-    check_carve(70, 70, 14, 128, 512);
-    check_carve(140, 182, 14, 128, 512);
-    check_carve(140, 182, 14, 1024, 4096);
+    check_carve(476, 630, 14, 1024, 4096, 4);
+    check_carve(42, 70, 14, 128, 512, 4);
+    check_carve(70, 70, 14, 128, 512, 4);
+    check_carve(140, 182, 14, 128, 512, 4);
+    check_carve(140, 182, 14, 1024, 4096, 4);
     std::printf("vit_f32_index_check: ok (%lld slots)\n", g_slots);
     return 0;
 }

@@ -12,7 +12,8 @@
 //     the sources and compared with the operand, so the source-side swizzle and the read-side swizzle agree; the packer's map is a bijection;
 //   rows attention: every K / V staging instruction of every key tile (ragged last tile: keys past L clamp), and the rebuilt K / V images
 //     against the rows the fragment reads expect;
-//   workspace: the carve's regions are disjoint, aligned and inside the total.
+//   workspace: the carve's regions are disjoint, aligned and inside the total, which is what the size query reports.
+// The patch and the workspace walks are tools/vit_check_common.h's, shared with tools/vit_f32_index_check.cpp.
 #include <cstdint>
 #include <cstdio>
 #include <cstdlib>
@@ -32,27 +33,7 @@ static long long g_slots = 0;
         }                                                                             \
     } while (0)
 
-static void check_patches(int H, int W, int p) {
-    const int Np = (H / p) * (W / p), Kp = vit_patch_kp(p);
-    CHECK(Kp % 32 == 0 && Kp >= 3 * p * p && Kp - 3 * p * p < 32);
-    std::vector<uint16_t> img((size_t)3 * H * W, 1);
-    std::vector<unsigned char> seen(img.size(), 0);
-    volatile uint16_t sink = 0;
-    for (int patch = 0; patch < Np; ++patch)
-        for (int k = 0; k < Kp; ++k) {
-            const long long s = vit_patch_src(H, W, p, patch, k);
-            if (k >= 3 * p * p) { CHECK(s == -1); continue; }
-            CHECK(s >= 0 && s < (long long)img.size());
-            sink = sink + img.data()[s];
-            CHECK(!seen[s]);
-            seen[s] = 1;
-            // the definition: Conv2d weight [D, 3, p, p] flattened, patch row-major
-            const int c = k / (p * p), dy = (k / p) % p, dx = k % p, py = patch / (W / p), px = patch % (W / p);
-            CHECK(s == ((long long)c * H + py * p + dy) * W + px * p + dx);
-            ++g_slots;
-        }
-    for (unsigned char v : seen) CHECK(v);
-}
+#include "vit_check_common.h"      // check_patches, check_carve
 
 static void check_gemm(int M, int K, int N, int lda) {
     CHECK(K % 32 == 0 && N % 16 == 0 && lda >= K && lda % 8 == 0);
@@ -137,22 +118,9 @@ static void check_attention(int L, int H) {
             }
 }
 
-static void check_carve(int H, int W, int p, int D, int Dh) {
-    const int Np = (H / p) * (W / p), L = Np + 1, Kp = vit_patch_kp(p);
-    const VitCarve c = vit_carve(L, D, Dh, Np, Kp);
-    const size_t off[5] = {c.xn, c.qkv, c.ao, c.hid, c.patches};
-    const size_t len[5] = {(size_t)L * D * 2, (size_t)L * 3 * D * 2, (size_t)L * D * 2, (size_t)L * Dh * 2, (size_t)Np * Kp * 2};
-    for (int i = 0; i < 5; ++i) {
-        CHECK(off[i] % 256 == 0 && off[i] + len[i] <= c.total);
-        if (i) CHECK(off[i] >= off[i - 1] + len[i - 1]);
-    }
-    std::vector<unsigned char> ws(c.total, 0);
-    for (int i = 0; i < 5; ++i) ws[off[i]] = ws[off[i] + len[i] - 1] = 1;
-}
-
 int main() {
     const int images[][2] = {{448, 616}, {42, 70}, {70, 70}, {140, 182}};
-    for (const auto& im : images) check_patches(im[0], im[1], 14);
+    for (const auto& im : images) check_patches<uint16_t>(im[0], im[1], 14);
     const int Ms[] = {1, 15, 16, 17, 127, 128, 129, 131}, Ks[] = {32, 608, 1024}, Ns[] = {16, 112, 128, 384};
     for (int M : Ms)
         for (int K : Ks)
@@ -170,11 +138,11 @@ int main() {
     for (int L : Ls)
         for (int H = 1; H <= 2; ++H) check_attention(L, H);
     check_attention(1409, 16);
-    check_carve(448, 616, 14, 1024, 4096);
-    check_carve(42, 70, 14, 128, 512);
-    check_carve(70, 70, 14, 128, 512);
-    check_carve(140, 182, 14, 128, 512);
-    check_carve(42, 70, 14, 1024, 4096);
+    check_carve(448, 616, 14, 1024, 4096, 2);
+    check_carve(42, 70, 14, 128, 512, 2);
+    check_carve(70, 70, 14, 128, 512, 2);
+    check_carve(140, 182, 14, 128, 512, 2);
+    check_carve(42, 70, 14, 1024, 4096, 2);
     std::printf("vit_index_check: ok (%lld slots)\n", g_slots);
     return 0;
 }
