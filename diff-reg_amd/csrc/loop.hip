@@ -106,6 +106,11 @@ struct PlanesWs {
     float* pre0;                             // [PN][2 H dp] layer 0, src rows: q | k in front of the rotary step (the src code moves, feat0 does not)
     char* v0_img; float *v0_bnd, *grp0;      // layer 0, src rows: the V image, its bounds [PN]; [P] bound of feat0 per src group
     char* q1_img; float* q1_bnd;             // layer 1, second cross call: q image of the tgt rows (PM rows), its row bounds [T] (token-indexed)
+    // ... and the x half of mlp0 where x stays (`hoist_mlp0`: knob DR_LOOP_HOIST_MLP0, default on, off with DR_LOOP_HOIST=0): the accumulator slabs
+    // (pgemm.h: acc_store / acc_load) of layer 0's src rows [0] and of layer 1's second cross call, tgt rows [1]; their room in floats; the form and
+    // tiling that stored (launch_pgemm's tag: a host word -- the launches of one call are enqueued by one thread, in order)
+    bool hoist_mlp0;
+    float* x0_acc[2]; size_t x0_cap[2]; mutable unsigned long long x0_tag[2];
     float* csT;                              // [T][C/2][2] the rotary tables interleaved (cos, sin)
     size_t qkv_stride;                       // bytes from the q image to the k image (= to the next: v)
     size_t side_C, side_att, side_hid;      // byte offset of the tgt part inside an image of K = C / H dp / 2C
@@ -128,7 +133,7 @@ struct PlanesWs {
         w.qkv_img = c.take<char>(3 * w.qkv_stride); w.qkv_bnd = c.take<float>(3 * (size_t)T);
         w.kvc_img = c.take<char>(2 * w.qkv_stride); w.kvc_bnd = c.take<float>(2 * (size_t)T);
         w.grp_x = c.take<float>(2 * (size_t)P);
-        w.hoist = false;                         // (carve_hoist: the buffers live in memory the plane path leaves idle)
+        w.hoist = w.hoist_mlp0 = false;          // (carve_hoist: the buffers live in memory the plane path leaves idle)
         w.csT = c.take<float>((size_t)T * C);
         w.own_pack = c.take<char>(Prepack::carve(nullptr, cfg, nullptr));
         // (only launches of at most half a chip of 64-row workgroups are split: 128 row blocks on 256 CUs)
@@ -147,6 +152,15 @@ struct PlanesWs {
         w.v0_img = c.take<char>(plane_image_bytes(PN, Cq)); w.v0_bnd = c.take<float>(PN); w.grp0 = c.take<float>(P);
         w.q1_img = c.take<char>(plane_image_bytes(PM, Cq)); w.q1_bnd = c.take<float>(T);
         w.hoist = c.off <= bytes && env_knob("DR_LOOP_HOIST", 1) != 0;
+        // the slabs of mlp0's x half behind them, where the kernel form that runs mlp0 keeps accumulators between launches and the room is there
+        const int side_rows[2] = {PN, PM};
+        for (int i = 0; i < 2; ++i) {
+            w.x0_cap[i] = pgemm_acc_cache_floats(side_rows[i], cfg.C, 2);
+            w.x0_acc[i] = c.take<float>(w.x0_cap[i]);
+            w.x0_tag[i] = 0;
+        }
+        w.hoist_mlp0 = w.hoist && c.off <= bytes && env_knob("DR_LOOP_HOIST_MLP0", 1) != 0 &&
+                       pgemm_acc_cache_ok(cfg.C, cfg.C / 16, cfg.C / 16, Prepack::wide_layout(cfg) ? 2 : 0);
     }
 };
 
@@ -255,6 +269,11 @@ struct PlHoist {
     bool l0_use = false;    // layer 0, src rows: no projection launch -- q | k images by rot_images from pre0, V is v0_img
     bool q1_fill = false;   // project ONLY q of the x rows (tgt) into q1_img / q1_bnd and return
     bool q1_use = false;    // q of the x rows (tgt) is q1_img / q1_bnd: the projection launch carries K | V of the y rows only
+    // one-sided calls whose x rows stay during a loop call (x0_slab: PlanesWs::x0_acc 0 / 1): mlp0 contracts [x | message], x first --
+    bool x0_store = false;  // the first evaluation of a call: mlp0's launch leaves the accumulators of its x half in the slabs
+    bool x0_use = false;    // every later one: mlp0's launch starts from them and contracts the message half only
+    int x0_slab = 0;
+    bool no_f32_out = false;   // nobody reads the fp32 rows of this call's result (the loop's last layer: the head takes the image): image only
 };
 static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, const Tok& xin, int xs, const Tok& yin, int ys,
                              const Tok& out, const Family& f1, const Family* f2, hipStream_t st, const float* kv_cached = nullptr,
@@ -398,6 +417,11 @@ static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, c
         p.W = L.mlp0; p.nblk = 2; p.rows = S.rows(side); p.C = C; p.mode = PG_PLANES; p.relu = 1; p.scale = 1.f;
         p.pimg = S.at(pw.hid_img, pw.side_hid, side); p.p_nct = 2 * nC; p.pbnd = pw.hid_bnd + S.r0(side);
         if (p.W.sub == 2) xk(p, xk_wide_units(p));
+        if (hz.x0_store || hz.x0_use) {
+            if (hz.x0_store) p.acc_store = pw.x0_acc[hz.x0_slab];
+            else p.acc_load = pw.x0_acc[hz.x0_slab];
+            p.acc_cap = pw.x0_cap[hz.x0_slab]; p.acc_tag = &pw.x0_tag[hz.x0_slab];
+        }
     });
     ++pw.xk_epoch;
     rc = launch_pgemm(g, st);
@@ -410,7 +434,7 @@ static int layer_call_planes(const PlCtx& X, const dr_layer_weights& W, int l, c
         p.W = L.mlp2; p.nblk = 1; p.rows = S.rows(side); p.C = C; p.mode = PG_LN;
         p.gamma = W.norm2_w; p.beta = W.norm2_b; p.lnB = L.lnB2;
         p.resid = xin.f32 + (size_t)S.r0(side) * C; p.ldr = C; p.bnd_res = xin.bnd + S.r0(side);
-        p.out = out.f32 + (size_t)S.r0(side) * C; p.ldo = C;
+        p.out = hz.no_f32_out ? nullptr : out.f32 + (size_t)S.r0(side) * C; p.ldo = C;
         p.pimg = S.at(out.img, pw.side_C, side); p.p_nct = nC; p.pbnd = out.bnd + S.r0(side);
         xk(p, (size_t)(p.rows + 63) / 64);
     });
@@ -491,7 +515,10 @@ static int fill_step_invariants(const dr_loop_config& cfg, const dr_loop_weights
 }
 
 static int denoiser_and_sim(const dr_loop_config& cfg, const dr_loop_weights& w, const float* feat0, const uint8_t* tokmask, DenoiseWs& ws,
-                            const float** final_feats, hipStream_t st, bool use_cache = false) {
+                            const float** final_feats, hipStream_t st, bool use_cache = false, bool first_eval = true, bool final_f32 = true) {
+    // first_eval (with use_cache): the first evaluation since fill_step_invariants -- it leaves mlp0's x half of the two calls whose x stays
+    // (layer 0 on the src rows: x = feat0; layer 1's second cross call: x = the tgt rows of tgt_l0) for the later ones (PlanesWs::hoist_mlp0).
+    // final_f32 = false: the caller reads no fp32 rows of the last layer (*final_feats is then null on the plane path: the head takes the image).
     const Sides& S = ws.S;
     const int C = cfg.C, P = S.P, N = S.La, M = S.Lb, PN = S.rows_a;
     // the matching head on the f32-input GEMM: src_proj on BOTH sides (quirk Q1), rotary, / sqrt(C) ...
@@ -511,8 +538,13 @@ static int denoiser_and_sim(const dr_loop_config& cfg, const dr_loop_weights& w,
         const PlCtx X = plane_ctx(cfg, ws, tokmask);
         const Tok* cur = &ws.pl.feat0;
         int rc = DR_OK;
+        const bool x0 = use_cache && ws.pl.hoist_mlp0;
+        const bool head_f32 = env_knob("DR_HEAD_F32", 0) != 0;
+        const bool drop_f32 = !final_f32 && !head_f32;      // the last layer's fp32 rows have no reader
         if (use_cache) {
             PlHoist hz; hz.l0_use = ws.pl.hoist;
+            hz.x0_store = x0 && first_eval; hz.x0_use = x0 && !first_eval; hz.x0_slab = 0;
+            hz.no_f32_out = drop_f32 && cfg.n_layers == 1;
             rc = layer_call_planes(X, w.layers[0], 0, *cur, SIDE_A, *cur, SIDE_A, ws.pl.tgt_l0, S.self_a(), nullptr, st, nullptr, nullptr, hz);
             cur = &ws.pl.tgt_l0;
         }
@@ -521,11 +553,14 @@ static int denoiser_and_sim(const dr_loop_config& cfg, const dr_loop_weights& w,
                                 [&](int l, int xs, const Tok* x, int ys, const Tok* y, const Tok* out, const Family& f1, const Family* f2) {
                 const bool l1 = use_cache && l == 1;
                 PlHoist hz; hz.q1_use = l1 && xs == SIDE_B && ws.pl.hoist;
+                const bool x1 = x0 && l1 && xs == SIDE_B;
+                hz.x0_store = x1 && first_eval; hz.x0_use = x1 && !first_eval; hz.x0_slab = 1;
+                hz.no_f32_out = drop_f32 && l == cfg.n_layers - 1;
                 return layer_call_planes(X, w.layers[l], l, *x, xs, *y, ys, *out, f1, f2, st, (l1 && xs == SIDE_A) ? ws.kv_l1 : nullptr, nullptr, hz);
             });
         if (rc) return rc;
-        *final_feats = cur->f32;
-        if (env_knob("DR_HEAD_F32", 0)) {
+        *final_feats = drop_f32 ? nullptr : cur->f32;
+        if (head_f32) {
             // (experiment: the head's projection on the f32-input MFMA GEMM, 24-bit operands, from the fp32 rows of the last layer)
             rc = head(cur->f32);
             return rc ? rc : sim();
@@ -843,9 +878,12 @@ int dr_denoise_loop(const dr_loop_config* cfg, const dr_loop_weights* w, int P, 
     sa.noise = v4d ? noise : nullptr; sa.bin_score = w->bin_score; sa.trace = trace;
     sa.x = L.x; sa.x_final = x_final; sa.x0 = L.x0; sa.wconf = L.wconf; sa.R = L.R; sa.t = L.t; sa.Rf = L.Rf; sa.tf = L.tf; sa.cond = L.cond; sa.ok = L.ok;
     sa.skws = L.skws; sa.skws_bytes = L.skws_bytes; sa.pws = L.pws; sa.pws_bytes = L.pws_bytes; sa.status = L.status;
+    // (the fp32 rows of the last layer are read by the trace's feature outputs alone: the matching head takes the plane image)
+    const bool final_f32 = trace && (trace->feats_nopos || trace->feats_pos);
+    int evals = 0;                                // evaluations since fill_step_invariants
     rc = reverse_sampling(sa, [&](const float* Rf, const float* tf) -> int {
         int r = fill_pe(*cfg, *w, P, N, M, s_pcd, Rf, tf, t_pcd, true, false, L.dw, st);
-        if (r == DR_OK) r = denoiser_and_sim(*cfg, *w, L.feat0, tokmask, L.dw, &fin, st, true);
+        if (r == DR_OK) r = denoiser_and_sim(*cfg, *w, L.feat0, tokmask, L.dw, &fin, st, true, evals++ == 0, final_f32);
         if (r) return r;
         return sinkhorn_f32(P, N, M, L.dw.sim, src_mask, tgt_mask, w->bin_score, cfg->sk_iters, DR_SK_OUT_CONF | mflag, L.x0, L.skws, L.skws_bytes, st,
                             L.status);

@@ -67,6 +67,16 @@ struct PgProblem {
     // the launches that use the buffer since then).  xk_status: the caller's sticky status word (bit 1 = a partner did not arrive; nullable).
     float* xk_buf; unsigned* xk_flags; unsigned xk_epoch; unsigned* xk_status; int ksplit;
     int xk_cap;                         // exchange units (one per split tile: 64-row block / 128 x 288 tile) this problem's xk_buf / xk_flags hold
+    // Two-segment problems whose FIRST segment (A0, bnd0) stays from launch to launch (mlp0's x half where x does not move between denoise steps):
+    // acc_store: every workgroup writes its raw fp32 accumulators, as they stand in front of the segment boundary's rescale, to its own slab --
+    //            acc_stride floats per (row block, column block), in the workgroup's own fragment order: private to the kernel form, no matrix;
+    // acc_load : the workgroup starts from its slab instead: segment 0 is neither staged nor multiplied (A0 is never read; bnd0 still is: the
+    //            rescale needs it) and the launch continues with the rescale and segment 1 -- the same bits.
+    // The caller gives the room (acc_cap floats) and a host word per slab set (acc_tag); launch_pgemm sets acc_stride, writes the form and tiling that
+    // stored into *acc_tag and refuses (DR_EINVAL) a load whose own form and tiling differ from it.  PG_PLANES launches of the 448-column geometry
+    // take the fields; everything else (the wide-wave kernel, other column geometries or epilogues, a k-split launch) returns DR_ENOSUP: ask
+    // pgemm_acc_cache_ok first.
+    float* acc_store; const float* acc_load; long long acc_stride; size_t acc_cap; unsigned long long* acc_tag;
 };
 constexpr int PG_XK_MAX_RB = 160;                                  // row blocks (of 64 rows) a split launch can have: xk_buf / xk_flags are sized for it
 inline size_t pgemm_xk_buf_bytes(int bn) { return (size_t)PG_XK_MAX_RB * 2 * 4 * (bn / 64) * 2 * 64 * 16; }
@@ -77,6 +87,13 @@ struct PgBatch { PgProblem p[3]; int n; int dbg; int wg_as; };   // dbg (debug k
 
 bool pgemm_shape_ok(int C);                      // column-block widths the kernel is built for
 int pgemm_bn(int C);                             // rows of a packed weight block (256 for C <= 256, 448 for C <= 448, 576 above)
+// whether a two-segment problem of this shape (columns per block, k-chunks of the segments, PgW::sub of its weights) can take acc_store / acc_load
+bool pgemm_acc_cache_ok(int C, int nc0, int nc1, int sub);
+// floats of slab room a problem of `rows` rows and `nblk` column blocks needs (any row tiling: whole 128-row blocks)
+size_t pgemm_acc_cache_floats(int rows, int C, int nblk);
+// diagnostics (dr_debug_pgemm_acc_forms): the forms that took the fields on the calling thread since the last clear -- bit f - 1: form f stored,
+// bit 4 + f - 1: form f loaded; f = 1 the 128-row 16x16x32 loop, 2 the generic 128-row loop, 3 the generic 64-row loop
+int pgemm_acc_forms(bool clear);
 int launch_pgemm(const PgBatch& g, hipStream_t st);
 int pgemm_configure();
 

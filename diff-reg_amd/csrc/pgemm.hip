@@ -122,6 +122,22 @@ __global__ __launch_bounds__(128 * WMN) __attribute__((amdgpu_waves_per_eu(WMN /
     const int t = threadIdx.x, lane = t & 63, l31 = lane & 31, h = lane >> 5;
     const int w = __builtin_amdgcn_readfirstlane(t >> 6), wm = w % WMN, wn = w / WMN;
     const int rb128 = (rb * BM) >> 7, sub = (rb * BM) & 127;      // image block and first row inside it (0 / 64)
+    // The first segment's accumulators kept from launch to launch (pgemm.h: acc_store / acc_load; the 448-column geometry's forms, never a k-split
+    // launch: launch_pgemm refuses the rest).  A workgroup's slab is 28 float4 per thread -- the accumulator registers as they are, float4 k of
+    // thread t at float (k NTHR + t) 4: a wave instruction moves 1 KB contiguous.
+    constexpr bool ACC_OK = TNW == 7 && MODE == PG_PLANES;       // (mlp0's epilogue: the other instantiations stay as they were)
+    const bool acc_st = ACC_OK && nc1 > 0 && P.acc_store != nullptr, acc_ld = ACC_OK && nc1 > 0 && P.acc_load != nullptr;
+    auto acc_slab = [&]() __attribute__((always_inline)) { return ((size_t)rb * nblk + nb) * (size_t)P.acc_stride + (size_t)threadIdx.x * 4; };
+    // Both directions in assembly, like the main loops' DMA: a load or store the compiler knows of makes it guard the accumulator registers with
+    // s_waitcnt vmcnt(0) of its own INSIDE the steady loop (it does not see the loops' own waits), which parks the issuing waves behind the DMA
+    // pieces they have just issued.  The loads are waited for by the prologue's vmcnt(0); s_nop 1: a store of more than 64 bits and the next write
+    // of its data registers are one wait state apart.
+    auto acc_get = [&](f32x4& x, const float* p) __attribute__((always_inline)) {    // (in place: no copy of the result before it has landed)
+        asm volatile("global_load_dwordx4 %0, %1, off" : "+v"(x) : "v"(p) : "memory");
+    };
+    auto acc_put = [&](float* p, f32x4 x) __attribute__((always_inline)) {
+        asm volatile("global_store_dwordx4 %0, %1, off\n\ts_nop 1" ::"v"(p), "v"(x) : "memory");
+    };
 
     float* const s_fac = reinterpret_cast<float*>(lds + GG::WORK);   // 2^(s1 - s0) of the rows (two-segment A operand)
     float* const s_rinv = s_fac + 128;                               // 2^-s of the rows (last segment)
@@ -256,10 +272,33 @@ __global__ __launch_bounds__(128 * WMN) __attribute__((amdgpu_waves_per_eu(WMN /
         // issued in the SGPR-base + VGPR-offset + immediate form: per piece an s_mov to M0 and the load, nothing else
         const int st0 = GRP ? wl * (WB_CNT / WMN) + min(wl, WB_CNT % WMN) : WB_CNT + wl * (NW0 / WMN) + min(wl, NW0 % WMN);
         const unsigned voffW = lane * 16 + st0 * 1024, voffA = lane * 16 + 2 * wl * 1024;
-        const char* ga = P.A0 + ((size_t)rb128 * P.nc0 + kbeg) * GG::A_IMG + sub * 64;   // A block of stage ti (wave-uniform)
-        const char* gb = P.W.img + ((size_t)nb * (P.nc0 + nc1) + kbeg) * GG::B_ST;       // weight block of stage ti
         const char* const ga1 = nc1 > 0 ? P.A1 + (size_t)rb128 * nc1 * GG::A_IMG + sub * 64 : nullptr;
-        int ti = 0;                                                  // next stage this wave issues
+        // acc_load: the loop starts at the segment boundary -- stage nc0 in ITS ring slot, the accumulators from the slab (the loads are older than
+        // every DMA piece: the prologue's wait for stage nc0 is the wait for them)
+        const int s0 = acc_ld ? nc0 : 0;
+        const char* ga = acc_ld ? ga1 : P.A0 + ((size_t)rb128 * P.nc0 + kbeg) * GG::A_IMG + sub * 64;   // A block of stage ti (wave-uniform)
+        const char* gb = P.W.img + ((size_t)nb * (P.nc0 + nc1) + kbeg + s0) * GG::B_ST;                // weight block of stage ti
+        int ti = s0;                                                 // next stage this wave issues
+        // (the slab is fetched in the prologue behind stage nc0's DMA pieces, one accumulator tile at a time -- four loads, their wait, the tile's
+        // registers: an asm result must not be copied before it has landed; this loop serves the small launches, the tiles' latencies are its price)
+        auto acc_fetch = [&]() __attribute__((always_inline)) {
+            if constexpr (ACC_OK) {
+                if (acc_ld) {
+                    const float* const lp = P.acc_load + acc_slab();
+#pragma unroll
+                    for (int j = 0; j < TNW; ++j) {
+                        f32x4 x[4] = {};
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int r4 = 0; r4 < 4; ++r4) acc_get(x[r4], lp + (size_t)(j * 4 + r4) * (NTHR * 4));
+                        PG_VMCNT(0);
+                        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                        for (int r = 0; r < 16; ++r) acc[j][r] = x[r >> 2][r & 3];
+                    }
+                }
+            }
+        };
         // (the instruction's immediate offset is added to the global address AND to the LDS address M0 + 16 lane)
 #define PG_DMA(ldsaddr, voff, gbase, imm)                                                                  \
     asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2 offset:%3" ::"s"(ldsaddr), "v"(voff), "s"(gbase), "i"(imm) : "memory")
@@ -291,7 +330,18 @@ __global__ __launch_bounds__(128 * WMN) __attribute__((amdgpu_waves_per_eu(WMN /
             const bool do_issue = STEADY || ti < nst;
             const unsigned dstb = lds_base + (unsigned)(ti % NST) * STAGE;
             if (s == nc0 && nc1 > 0) {
-                // second A segment starts: bring the accumulators from the scale of segment 0 to that of segment 1 (exact powers of two)
+                // second A segment starts: [acc_store: segment 0's raw sums to the workgroup's slab;] bring the accumulators from the scale of
+                // segment 0 to that of segment 1 (exact powers of two)
+                if constexpr (ACC_OK) {
+                    if (acc_st) {
+                        float* const sp = P.acc_store + acc_slab();
+#pragma unroll
+                        for (int j = 0; j < TNW; ++j)
+#pragma unroll
+                            for (int r4 = 0; r4 < 4; ++r4)
+                                acc_put(sp + (size_t)(j * 4 + r4) * (NTHR * 4), f32x4{acc[j][4 * r4], acc[j][4 * r4 + 1], acc[j][4 * r4 + 2], acc[j][4 * r4 + 3]});
+                    }
+                }
                 const unsigned fb0 = lds_base + GG::WORK + (wm * 32 + 4 * h) * 4;
                 u32x4 f[4];
                 PG_READ(f[0], fb0, 0); PG_READ(f[1], fb0, 32); PG_READ(f[2], fb0, 64); PG_READ(f[3], fb0, 96);
@@ -369,26 +419,28 @@ __global__ __launch_bounds__(128 * WMN) __attribute__((amdgpu_waves_per_eu(WMN /
         // them is the wait for stage 0)
 #pragma unroll
         for (int q2 = 0; q2 < AHEAD; ++q2) {
-            const unsigned dstb = lds_base + (unsigned)q2 * STAGE;
+            const unsigned dstb = lds_base + (unsigned)((s0 + q2) % NST) * STAGE;
 #pragma unroll
             for (int i = 0; i < NPIECE; ++i) dma_piece(i, dstb);
             dma_advance();
             if (q2 == 0) {
                 __builtin_amdgcn_sched_barrier(0);
                 stage_inputs();
+                acc_fetch();
                 __builtin_amdgcn_sched_barrier(0);
                 PG_VMCNT(0);
             }
         }
         __builtin_amdgcn_s_barrier();
-        PG_READ(fa0[0], lds_base + offAh, 0);
-        PG_READ(fa0[1], lds_base + offAl, 0);
+        const unsigned sb0 = lds_base + (unsigned)(s0 % NST) * STAGE;    // slot of the first stage
+        PG_READ(fa0[0], sb0 + offAh, 0);
+        PG_READ(fa0[1], sb0 + offAl, 0);
 #pragma unroll
         for (int j = 0; j < TNW / 2; ++j) {
-            PG_READ(fx[j][0], lds_base + offBh, j * 2048);
-            PG_READ(fx[j][1], lds_base + offBl, j * 2048);
+            PG_READ(fx[j][0], sb0 + offBh, j * 2048);
+            PG_READ(fx[j][1], sb0 + offBl, j * 2048);
         }
-        int s = 0;
+        int s = s0;
         for (; s + 1 < nst - (NST - 1); s += 2) {                    // steady state: every stage issues, has a successor
             stage(s, std::true_type{}, fa0, fa1);
             stage(s + 1, std::true_type{}, fa1, fa0);
@@ -419,18 +471,35 @@ __global__ __launch_bounds__(128 * WMN) __attribute__((amdgpu_waves_per_eu(WMN /
         for (int i = 0; i < 4; ++i)
 #pragma unroll
             for (int j = 0; j < 7; ++j) c16[i][j] = f32x4{0.f, 0.f, 0.f, 0.f};
+        // acc_load: segment 0's sums from the slab, fetched in the prologue behind the first pair's DMA pieces and waited for on the spot (the
+        // compiler may copy an asm result as soon as the statement is behind it)
+        auto acc_fetch = [&]() __attribute__((always_inline)) {
+            if (acc_ld) {
+                const float* const lp = P.acc_load + acc_slab();
+                __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                for (int i = 0; i < 4; ++i)
+#pragma unroll
+                    for (int j = 0; j < 7; ++j) acc_get(c16[i][j], lp + (size_t)(i * 7 + j) * (NTHR * 4));
+                PG_VMCNT(0);
+                __builtin_amdgcn_sched_barrier(0);
+            }
+        };
         u32x4 fb[7][2], fa[2][2];
         const int nv0 = (nc0 + 1) & ~1, nvt = nv0 + ((nc1 + 1) & ~1), npair = nvt >> 1;      // virtual chunk counts (segments padded to pairs)
         const int z0 = (nc0 & 1) ? nv0 - 1 : -1, z1 = (nc1 & 1) ? nvt - 1 : -1;              // the virtual (zero) chunks
         const int wl = w & 3, st0 = wl * 7;
         const unsigned voffW = lane * 16 + st0 * 1024, voffA = lane * 16 + 2 * wl * 1024;
-        const char* ga = P.A0 + (size_t)rb128 * nc0 * GG::A_IMG + sub * 64;
-        const char* gb = P.W.img + (size_t)nb * nst * GG::B_ST;
         const char* const ga1 = nc1 > 0 ? P.A1 + (size_t)rb128 * nc1 * GG::A_IMG + sub * 64 : nullptr;
-        int ti = 0, tr = 0;                                              // next virtual chunk to issue, real chunks issued
+        // acc_load: the loop starts at the first pair of segment 1 (virtual chunk nv0: an even chunk, so pairs, ring slots and the boundary's rescale
+        // stay where they are; segment 0's own virtual chunk is never met)
+        const int p0 = acc_ld ? nv0 >> 1 : 0;
+        const char* ga = acc_ld ? ga1 : P.A0 + (size_t)rb128 * nc0 * GG::A_IMG + sub * 64;
+        const char* gb = P.W.img + ((size_t)nb * nst + (acc_ld ? nc0 : 0)) * GG::B_ST;
+        int ti = 2 * p0, tr = acc_ld ? nc0 : 0;                          // next virtual chunk to issue, real chunks issued
         auto piece = [&](int q) __attribute__((always_inline)) {        // q = 0 .. 8 of chunk ti
             if (ti == z0 || ti == z1) return;
-            const unsigned dstb = lds_base + (unsigned)(ti % NST) * STAGE;
+            const unsigned dstb = lds_base + ((unsigned)ti % NST) * STAGE;
             const unsigned m0w = dstb + A_ST + st0 * 1024;
             const int pw = q - 2;
             const unsigned hop = (unsigned)(pw >> 2) * 4096;
@@ -453,6 +522,13 @@ __global__ __launch_bounds__(128 * WMN) __attribute__((amdgpu_waves_per_eu(WMN /
             const unsigned sb = lds_base + (unsigned)(p & 1) * 2 * STAGE, sbn = lds_base + (unsigned)((p + 1) & 1) * 2 * STAGE;
             const bool has_next = STEADY || p + 1 < npair;
             if (2 * p == nv0 && nc1 > 0) {
+                if (acc_st) {                                            // acc_store: segment 0's raw sums, in front of the rescale
+                    float* const sp = P.acc_store + acc_slab();
+#pragma unroll
+                    for (int i = 0; i < 4; ++i)
+#pragma unroll
+                        for (int j = 0; j < 7; ++j) acc_put(sp + (size_t)(i * 7 + j) * (NTHR * 4), c16[i][j]);
+                }
 #pragma unroll
                 for (int i = 0; i < 4; ++i) {
                     const float f = s_fac[wm2 * 64 + 16 * i + l15];                     // row 16 i + l15 of the wave's 64
@@ -534,21 +610,24 @@ __global__ __launch_bounds__(128 * WMN) __attribute__((amdgpu_waves_per_eu(WMN /
             advance();
             __builtin_amdgcn_sched_barrier(0);
             stage_inputs();
+            acc_fetch();
             __builtin_amdgcn_sched_barrier(0);
             PG_VMCNT(0);
 #pragma unroll
             for (int q = 0; q < 7; ++q) piece(q);
         } else {
             stage_inputs();
+            acc_fetch();
         }
         __builtin_amdgcn_s_barrier();
-        PG_READ(fa[0][0], lds_base + oAh, 0);
-        PG_READ(fa[0][1], lds_base + oAl, 0);
+        const unsigned sb0 = lds_base + (unsigned)(p0 & 1) * 2 * STAGE;      // slots of the first pair
+        PG_READ(fa[0][0], sb0 + oAh, 0);
+        PG_READ(fa[0][1], sb0 + oAl, 0);
 #pragma unroll
-        for (int j = 0; j < 7; ++j) PG_READ(fb[j][1], lds_base + oBl, j * 1024);
+        for (int j = 0; j < 7; ++j) PG_READ(fb[j][1], sb0 + oBl, j * 1024);
 #pragma unroll
-        for (int j = 0; j < 7; ++j) PG_READ(fb[j][0], lds_base + oBh, j * 1024);
-        int p = 0;
+        for (int j = 0; j < 7; ++j) PG_READ(fb[j][0], sb0 + oBh, j * 1024);
+        int p = p0;
         for (; p < npair - 2; ++p) stage(p, std::true_type{});
         for (; p < npair; ++p) stage(p, std::false_type{});
     };
@@ -1577,6 +1656,17 @@ using G9H = PgGeom<9, 3, 2>;
 bool pgemm_shape_ok(int C) { return C > 0 && C % 16 == 0 && C <= G9::BN; }
 int pgemm_bn(int C) { return C <= G4::BN ? G4::BN : (C <= G7::BN ? G7::BN : G9::BN); }
 static size_t pg_bst(int C) { return (size_t)pgemm_bn(C) * 64; }
+// acc_store / acc_load: pgemm_kernel's forms on the 448-column geometry (the 16x16x32 loop and the generic loop in both row tilings).  Segments of
+// >= 5 chunks: a loop that starts at the boundary fills its ring from segment 1 alone, and the 16x16x32 loop's virtual chunk needs a slot that
+// has held real weight planes.
+bool pgemm_acc_cache_ok(int C, int nc0, int nc1, int sub) { return sub == 0 && pgemm_shape_ok(C) && pgemm_bn(C) == G7::BN && nc0 >= 5 && nc1 >= 5; }
+size_t pgemm_acc_cache_floats(int rows, int C, int nblk) { return (size_t)((rows + 127) / 128) * 128 * (size_t)nblk * pgemm_bn(C); }
+static thread_local int g_acc_forms = 0;
+int pgemm_acc_forms(bool clear) {
+    const int f = g_acc_forms;
+    if (clear) g_acc_forms = 0;
+    return f;
+}
 
 // The 576-column geometry exists in the 64-row form only: its 128-row form (8 waves, 256 registers per wave: 144 accumulators + two fragment
 // sets) spilled 198-226 registers and measured 4 % slower than the 64-row form even where it fills the chip (32 pairs of 512 x 512: 147.6
@@ -1622,6 +1712,8 @@ static int launch_pgemm16w(const PgBatch& g, hipStream_t st) {
     double flops = 0;
     const int mode = g.p[0].mode;
     if (mode != PG_F32 && mode != PG_PLANES) return DR_ENOSUP;
+    for (int i = 0; i < g.n; ++i)
+        if (g.p[i].acc_store || g.p[i].acc_load) return DR_ENOSUP;      // (pgemm.h: the wide-wave kernel keeps no accumulators between launches)
     // KSPLIT: at most half a chip of tiles, every problem with an exchange region large enough and halves of >= 5 chunks (>= 6: the split chunk is even)
     bool ksplit = env_knob("DR_PG_KSPLIT", 1) != 0 && env_knob("DR_PG_KSPLITW", 1) != 0;
     long tiles = 0;
@@ -1697,12 +1789,28 @@ int launch_pgemm(const PgBatch& g, hipStream_t st) {
     PgBatch gd = g;
     gd.dbg = env_knob("DR_PG_NOEPI", 0);
     for (int i = 0; i < g.n; ++i) gd.p[i].ksplit = ksplit ? 1 : 0;
+    // the 16x16x32 main loop (128-row workgroups): a virtual chunk's slot must have held real weight planes before (segments of >= 5 chunks)
+    bool m16 = env_knob("DR_PG_M16", 1) != 0;
+    for (int i = 0; i < g.n; ++i) m16 = m16 && g.p[i].nc0 >= 5 && (!g.p[i].A1 || g.p[i].nc1 >= 5);
+    // acc_store / acc_load (pgemm.h): the forms of the 448-column geometry, never a k-split launch; a slab is the workgroup's bm x 448 accumulators.
+    // The tag names the form and the tiling that stored: a load under any other would misread the slabs, so it is refused here.
+    for (int i = 0; i < g.n; ++i) {
+        PgProblem& p = gd.p[i];
+        if (!p.acc_store && !p.acc_load) continue;
+        if ((p.acc_store && p.acc_load) || !p.A1 || !p.acc_tag) return DR_EINVAL;
+        if (ksplit || mode != PG_PLANES || !pgemm_acc_cache_ok(p.C, p.nc0, p.nc1, p.W.sub)) return DR_ENOSUP;
+        const int form = half ? 3 : (m16 ? 1 : 2);
+        p.acc_stride = (long long)bm * G7::BN;
+        if ((size_t)((p.rows + bm - 1) / bm) * p.nblk * (size_t)p.acc_stride > p.acc_cap) return DR_EWORKSPACE;
+        const unsigned long long tag = (unsigned long long)form | ((unsigned long long)p.nblk << 4) | ((unsigned long long)p.nc0 << 8) |
+                                       ((unsigned long long)p.nc1 << 20) | ((unsigned long long)p.rows << 32);
+        if (p.acc_store) *p.acc_tag = tag;
+        else if (*p.acc_tag != tag) return DR_EINVAL;
+        g_acc_forms |= 1 << ((p.acc_store ? 0 : 4) + form - 1);
+    }
     if (bn == G9::BN) pg_launch<9, 3, 2>(mode, grid, st, gd);
     else if (bn == G4::BN) { if (half) pg_launch<4, 4, 2>(mode, grid, st, gd); else pg_launch<4, 4, 4>(mode, grid, st, gd); }
     else {
-        // the 16x16x32 main loop (128-row workgroups): a virtual chunk's slot must have held real weight planes before (segments of >= 5 chunks)
-        bool m16 = env_knob("DR_PG_M16", 1) != 0;
-        for (int i = 0; i < g.n; ++i) m16 = m16 && g.p[i].nc0 >= 5 && (!g.p[i].A1 || g.p[i].nc1 >= 5);
         if (half) pg_launch<7, 4, 2>(mode, grid, st, gd);
         else if (m16) {
             using GG = PgGeom<7, 4, 4>;

@@ -180,6 +180,7 @@ SIGNATURES.update({
     "dr_debug_attention_split": (None, [c_int]),
     "dr_debug_attention_last_form": (c_int, []),
     "dr_debug_procrustes_last_form": (c_int, []),
+    "dr_debug_pgemm_acc_forms": (c_int, [c_int]),
     "dr_pnp_ransac_workspace_bytes": (c_size_t, [c_int, c_int]),
     "dr_pnp_ransac_f64": (c_int, [c_int, c_void_p, c_void_p, c_int, c_void_p, c_int, c_double, ctypes.c_uint64, c_void_p, c_void_p, c_void_p, c_void_p, c_size_t,
                                   c_void_p]),

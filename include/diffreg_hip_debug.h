@@ -78,6 +78,14 @@ int dr_debug_attention_last_form(void);
 #define DR_PROC_FORM_SLICED 1
 #define DR_PROC_FORM_SLICED_REREAD 2
 int dr_debug_procrustes_last_form(void);
+/* which plane-GEMM forms kept or took up the accumulators of a step-invariant first operand segment (the x half of mlp0 in the 3D / 4D loop)
+ * in the launches the calling thread has enqueued since the last call with clear != 0; 0: none did (the feature is off, or the geometry has
+ * no such form).  Bit f - 1: form f stored, bit 4 + f - 1: form f loaded;
+ *   f = 1  128-row workgroups, the 16x16x32 main loop     2  128-row workgroups, the generic main loop     3  64-row workgroups */
+#define DR_PGEMM_ACC_FORM_M16 1
+#define DR_PGEMM_ACC_FORM_ROWS128 2
+#define DR_PGEMM_ACC_FORM_ROWS64 3
+int dr_debug_pgemm_acc_forms(int clear);
 /* polls before a workgroup of the single-launch Sinkhorn gives up waiting for the others (0 = the default, 2^22); the timeout test
  * sets 1 so that the first failed poll already gives up (tests/test_errors_gpu.py) */
 void dr_debug_sinkhorn_spin_limit(unsigned polls);
