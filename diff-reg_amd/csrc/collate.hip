@@ -21,16 +21,19 @@ constexpr unsigned long long CL_PAD_KEY = ~0ull;
 // ------------------------------------------------------------------------------------------------------------
 struct CloudInfo {
     int begin, end;          // rows of the stacked array
-    float ox, oy, oz;        // subsample: origin corner floor(min * (1 / dl)) * dl;  neighbours: min corner
+    float ox, oy, oz;        // origin corner by CL_ORIGIN_*: the min corner (neighbours), floor(min * (1 / dl)) * dl (KPConv's subsample),
+                             // floor(min / dl) * dl (vision3d's subsample)
     int lx, ly, lz;          // smallest voxel coordinate of the cloud (keys are stored relative to it)
     int bad;                 // a coordinate range does not fit CL_AXIS_BITS
 };
+
+constexpr int CL_ORIGIN_MIN = 0, CL_ORIGIN_KPCONV = 1, CL_ORIGIN_VISION3D = 2;     // CloudInfo origin: see cloud_info_kernel
 
 __device__ __forceinline__ int cl_floor_div(float p, float o, float d) { return (int)floorf((p - o) / d); }
 
 // one workgroup per cloud: bounding box -> origin, voxel coordinate range
 __global__ __launch_bounds__(1024) void cloud_info_kernel(const float* __restrict__ pts, const int* __restrict__ lengths, int nb,
-                                                          float cell, int subsample_origin, CloudInfo* __restrict__ info,
+                                                          float cell, int origin_mode, CloudInfo* __restrict__ info,
                                                           int* __restrict__ status) {
     __shared__ float s_mn[16][3], s_mx[16][3];
     __shared__ int s_begin;
@@ -62,8 +65,10 @@ __global__ __launch_bounds__(1024) void cloud_info_kernel(const float* __restric
     ci.begin = begin; ci.end = begin + len; ci.bad = 0;
     float o[3];
     for (int c = 0; c < 3; ++c) {
-        // grid_subsampling.cpp:26  originCorner = floor(minCorner * (1 / sampleDl)) * sampleDl
-        o[c] = subsample_origin ? floorf(mn[c] * (1.0f / cell)) * cell : mn[c];
+        // CL_ORIGIN_KPCONV    grid_subsampling.cpp:26 (cpp_wrappers)  originCorner = floor(minCorner * (1 / sampleDl)) * sampleDl
+        // CL_ORIGIN_VISION3D  vision3d/csrc/cpu/grid_subsampling/grid_subsampling.cpp:32  origin = floor(min_corner / voxel_size) * voxel_size
+        o[c] = origin_mode == CL_ORIGIN_KPCONV ? floorf(mn[c] * (1.0f / cell)) * cell
+             : origin_mode == CL_ORIGIN_VISION3D ? floorf(mn[c] / cell) * cell : mn[c];
     }
     ci.ox = o[0]; ci.oy = o[1]; ci.oz = o[2];
     int lo[3] = {0, 0, 0};
@@ -300,93 +305,105 @@ __global__ __launch_bounds__(256) void cell_table_kernel(const unsigned long lon
     tab[slot].len = j - i;
 }
 
-struct NbArgs {
+// what the 27-cell sweep reads: the stacked queries, the cloud tables, the supports sorted by cell and their cell table
+struct BallArgs {
     const float* queries; int nq; const CloudInfo* q_info; const CloudInfo* s_info; int nb;
     const CellSlot* tab; unsigned mask; const float4* sorted; int ns;
-    float cell, r2; int limit; long long* out; int* max_count;
+    float cell, r2;
 };
+
+// the supports of query q's own cloud with d^2 < r^2, in sweep order: hit(d2, index into the stacked supports) per support.
+// Shared by the neighbour lists (radius_query_kernel) and the neighbour counts (radius_count_hist_kernel): one float32
+// expression, one strict comparison for both.
+template <class Hit>
+__device__ __forceinline__ void cl_sweep_ball(const BallArgs& A, int q, Hit&& hit) {
+    if (A.ns <= 0) return;
+    const int b = cl_cloud_of(A.q_info, A.nb, q);
+    const CloudInfo si = A.s_info[b];
+    const float qx = A.queries[(size_t)q * 3], qy = A.queries[(size_t)q * 3 + 1], qz = A.queries[(size_t)q * 3 + 2];
+    if (si.end <= si.begin) return;
+    const int m = (1 << CL_AXIS_BITS) - 1;
+    // cell of the query in the support cloud's grid (may lie outside it)
+    const long long cx = (long long)floorf((qx - si.ox) / A.cell) - si.lx + 1;
+    const long long cy = (long long)floorf((qy - si.oy) / A.cell) - si.ly + 1;
+    const long long cz = (long long)floorf((qz - si.oz) / A.cell) - si.lz + 1;
+    // per (y, z) row: three independent probes (x - 1, x, x + 1 are adjacent keys, so the cells that exist form ONE
+    // run of the sorted supports), then the sweep of that run
+#pragma unroll 1
+    for (int row = 0; row < 9; ++row) {
+        const long long y = cy + (row % 3) - 1, z = cz + (row / 3) - 1;
+        if (y < 0 || y > m || z < 0 || z > m) continue;
+        int lo = 0x7fffffff, hi = 0;
+#pragma unroll
+        for (int dx = -1; dx <= 1; ++dx) {
+            const long long x = cx + dx;
+            if (x < 0 || x > m) continue;
+            const unsigned long long k = cl_key(b, (int)x, (int)y, (int)z);
+            unsigned slot = cl_hash(k) & A.mask;
+            while (true) {
+                const unsigned long long tk = A.tab[slot].key;
+                if (tk == k) {
+                    const int s0 = A.tab[slot].start;
+                    lo = min(lo, s0); hi = max(hi, s0 + A.tab[slot].len);
+                    break;
+                }
+                if (tk == CL_PAD_KEY) break;
+                slot = (slot + 1) & A.mask;
+            }
+        }
+        // candidates eight at a time: the loads of a batch are independent and in flight together
+        for (int j0 = lo; j0 < hi; j0 += 8) {
+            float4 sv[8];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) sv[u] = A.sorted[min(j0 + u, hi - 1)];
+#pragma unroll
+            for (int u = 0; u < 8; ++u) {
+                if (j0 + u >= hi) break;
+                const float4 s = sv[u];
+                // nanoflann L2_Simple_Adaptor: result += diff * diff over the three axes, float
+                const float d0 = qx - s.x, d1 = qy - s.y, d2 = qz - s.z;
+                const float dd = ((0.f + d0 * d0) + d1 * d1) + d2 * d2;
+                if (dd < A.r2) hit(dd, __float_as_uint(s.w));
+            }
+        }
+    }
+}
+
+struct NbArgs { BallArgs ball; int limit; long long* out; int* max_count; };
 
 constexpr int NB_CAP = 64;              // candidates kept per query before the final ranking (>= limit)
 constexpr int NB_STRIDE = NB_CAP + 1;   // list stride in LDS (odd: the lanes' append positions fall into different banks)
 
-__global__ __launch_bounds__(64) void radius_query_kernel(NbArgs A) {
+__global__ __launch_bounds__(64) void radius_query_kernel(NbArgs N) {
     // one list per lane, list-major: entry e of lane L at [L * NB_STRIDE + e]
     __shared__ float s_d[64 * NB_STRIDE];
     __shared__ unsigned s_i[64 * NB_STRIDE];
+    const BallArgs& A = N.ball;
     const int lane = threadIdx.x, q = blockIdx.x * 64 + lane;
     int cnt = 0, kept = 0;
     float* my_d = s_d + lane * NB_STRIDE;
     unsigned* my_i = s_i + lane * NB_STRIDE;
     if (q < A.nq) {
-        const int b = cl_cloud_of(A.q_info, A.nb, q);
-        const CloudInfo si = A.s_info[b];
-        const float qx = A.queries[(size_t)q * 3], qy = A.queries[(size_t)q * 3 + 1], qz = A.queries[(size_t)q * 3 + 2];
-        if (si.end > si.begin) {
-            const int m = (1 << CL_AXIS_BITS) - 1;
-            // cell of the query in the support cloud's grid (may lie outside it)
-            const long long cx = (long long)floorf((qx - si.ox) / A.cell) - si.lx + 1;
-            const long long cy = (long long)floorf((qy - si.oy) / A.cell) - si.ly + 1;
-            const long long cz = (long long)floorf((qz - si.oz) / A.cell) - si.lz + 1;
-            // per (y, z) row: three independent probes (x - 1, x, x + 1 are adjacent keys, so the cells that exist form ONE
-            // run of the sorted supports), then the sweep of that run
-#pragma unroll 1
-            for (int row = 0; row < 9; ++row) {
-                const long long y = cy + (row % 3) - 1, z = cz + (row / 3) - 1;
-                if (y < 0 || y > m || z < 0 || z > m) continue;
-                int lo = 0x7fffffff, hi = 0;
-#pragma unroll
-                for (int dx = -1; dx <= 1; ++dx) {
-                    const long long x = cx + dx;
-                    if (x < 0 || x > m) continue;
-                    const unsigned long long k = cl_key(b, (int)x, (int)y, (int)z);
-                    unsigned slot = cl_hash(k) & A.mask;
-                    while (true) {
-                        const unsigned long long tk = A.tab[slot].key;
-                        if (tk == k) {
-                            const int s0 = A.tab[slot].start;
-                            lo = min(lo, s0); hi = max(hi, s0 + A.tab[slot].len);
-                            break;
-                        }
-                        if (tk == CL_PAD_KEY) break;
-                        slot = (slot + 1) & A.mask;
-                    }
+        cl_sweep_ball(A, q, [&](float dd, unsigned id) {
+            ++cnt;
+            // APPEND, unsorted (sorting on arrival made every candidate step of the wave pay the longest
+            // shift of any lane: 530 us of a 590 us launch); the lists are ranked once, cooperatively, below
+            if (kept < NB_CAP) {
+                my_d[kept] = dd; my_i[kept] = id;
+                ++kept;
+            } else {          // more than NB_CAP points in the ball: the farthest kept one makes room
+                int far = 0;
+                float fd = my_d[0]; unsigned fi = my_i[0];
+                for (int e = 1; e < NB_CAP; ++e) {
+                    const float ed = my_d[e]; const unsigned ei = my_i[e];
+                    if (ed > fd || (ed == fd && ei > fi)) { far = e; fd = ed; fi = ei; }
                 }
-                // candidates eight at a time: the loads of a batch are independent and in flight together
-                for (int j0 = lo; j0 < hi; j0 += 8) {
-                    float4 sv[8];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) sv[u] = A.sorted[min(j0 + u, hi - 1)];
-#pragma unroll
-                    for (int u = 0; u < 8; ++u) {
-                        if (j0 + u >= hi) break;
-                        const float4 s = sv[u];
-                        // nanoflann L2_Simple_Adaptor: result += diff * diff over the three axes, float
-                        const float d0 = qx - s.x, d1 = qy - s.y, d2 = qz - s.z;
-                        const float dd = ((0.f + d0 * d0) + d1 * d1) + d2 * d2;
-                        if (!(dd < A.r2)) continue;
-                        ++cnt;
-                        const unsigned id = __float_as_uint(s.w);
-                        // APPEND, unsorted (sorting on arrival made every candidate step of the wave pay the longest
-                        // shift of any lane: 530 us of a 590 us launch); the lists are ranked once, cooperatively, below
-                        if (kept < NB_CAP) {
-                            my_d[kept] = dd; my_i[kept] = id;
-                            ++kept;
-                        } else {          // more than NB_CAP points in the ball: the farthest kept one makes room
-                            int far = 0;
-                            float fd = my_d[0]; unsigned fi = my_i[0];
-                            for (int e = 1; e < NB_CAP; ++e) {
-                                const float ed = my_d[e]; const unsigned ei = my_i[e];
-                                if (ed > fd || (ed == fd && ei > fi)) { far = e; fd = ed; fi = ei; }
-                            }
-                            if (dd < fd || (dd == fd && id < fi)) { my_d[far] = dd; my_i[far] = id; }
-                        }
-                    }
-                }
+                if (dd < fd || (dd == fd && id < fi)) { my_d[far] = dd; my_i[far] = id; }
             }
-        }
+        });
     }
     const int mx = wave_max(cnt);
-    if (lane == 0 && mx > 0) atomicMax(A.max_count, mx);
+    if (lane == 0 && mx > 0) atomicMax(N.max_count, mx);
     __syncthreads();
     // rank the 64 lists one after the other with the whole wave: lane i owns entry i of list L and counts the entries that
     // precede it in (distance, index) order (broadcast reads); entry -> column `rank` of the row, columns >= n padded
@@ -396,7 +413,7 @@ __global__ __launch_bounds__(64) void radius_query_kernel(NbArgs A) {
         const int n = __shfl(kept, L);
         const float* ld = s_d + L * NB_STRIDE;
         const unsigned* li = s_i + L * NB_STRIDE;
-        long long* o = A.out + (size_t)qL * A.limit;
+        long long* o = N.out + (size_t)qL * N.limit;
         if (lane < n) {
             const float di = ld[lane]; const unsigned ii = li[lane];
             int rank = 0;
@@ -407,12 +424,40 @@ __global__ __launch_bounds__(64) void radius_query_kernel(NbArgs A) {
 #pragma unroll
                 for (int u = 0; u < 8; ++u) rank += (j + u < n && (dj[u] < di || (dj[u] == di && ij[u] < ii))) ? 1 : 0;
             }
-            if (rank < A.limit) o[rank] = (long long)ii;
+            if (rank < N.limit) o[rank] = (long long)ii;
         }
-        if (lane >= n && lane < A.limit) o[lane] = (long long)A.ns;                 // pad: neighbors.cpp:325
+        if (lane >= n && lane < N.limit) o[lane] = (long long)A.ns;                 // pad: neighbors.cpp:325
     }
 }
 
+
+// ------------------------------------------------------------------------------------------------------------
+// neighbour-count histogram (the calibration of the 2D-3D loader's neighbour limits, vision3d/utils/dataloader.py:42-67): the
+// sweep above with a counter in place of the list, so a count has no upper limit.  Counts are binned in LDS per workgroup,
+// the non-empty bins go to global memory with integer atomic adds (any order gives the same sums: two runs are bit-equal).
+// ------------------------------------------------------------------------------------------------------------
+constexpr int CH_BLOCK = 256;
+constexpr int CH_MAX_BINS = 4096;       // 16 KB of LDS
+
+struct CountArgs { BallArgs ball; int hist_n; int* hist; int* counts; };
+
+__global__ __launch_bounds__(CH_BLOCK) void radius_count_hist_kernel(CountArgs C) {
+    __shared__ int s_h[CH_MAX_BINS];
+    const int t = threadIdx.x, q = blockIdx.x * CH_BLOCK + t;
+    for (int i = t; i < C.hist_n; i += CH_BLOCK) s_h[i] = 0;
+    __syncthreads();
+    if (q < C.ball.nq) {
+        int cnt = 0;
+        cl_sweep_ball(C.ball, q, [&](float, unsigned) { ++cnt; });
+        if (C.counts) C.counts[q] = cnt;
+        if (cnt < C.hist_n) atomicAdd(&s_h[cnt], 1);          // count >= hist_n: not recorded (np.bincount(c)[:hist_n])
+    }
+    __syncthreads();
+    for (int i = t; i < C.hist_n; i += CH_BLOCK) {
+        const int v = s_h[i];
+        if (v) atomicAdd(C.hist + i, v);
+    }
+}
 
 }  // namespace dr
 
@@ -427,9 +472,9 @@ size_t dr_grid_subsample_workspace_bytes(int n, int nb) {
     return align256(sizeof(CloudInfo) * nb) + align256(8ull * n_pad) + align256(4ull * n_pad) + align256(4ull * nblk);
 }
 
-int dr_grid_subsample_f32(int n, int nb, const float* points, const int32_t* lengths, float dl, float* out_points,
-                          int32_t* out_lengths, int32_t* out_total, int32_t* status, void* workspace, size_t workspace_bytes,
-                          void* stream) {
+static int grid_subsample_impl(int origin_mode, int n, int nb, const float* points, const int32_t* lengths, float dl, float* out_points,
+                               int32_t* out_lengths, int32_t* out_total, int32_t* status, void* workspace, size_t workspace_bytes,
+                               void* stream) {
     if (n < 0 || nb <= 0 || nb >= (1 << 15) || !(dl > 0.f)) return DR_EINVAL;
     if (!lengths || !out_lengths || !out_total || !status) return DR_EINVAL;
     hipStream_t st = (hipStream_t)stream;
@@ -446,7 +491,7 @@ int dr_grid_subsample_f32(int n, int nb, const float* points, const int32_t* len
     unsigned long long* keys = (unsigned long long*)w; w += align256(8ull * n_pad);
     unsigned* vals = (unsigned*)w; w += align256(4ull * n_pad);
     int* block_off = (int*)w;
-    hipLaunchKernelGGL(cloud_info_kernel, dim3(nb), dim3(1024), 0, st, points, lengths, nb, dl, 1, info, status);
+    hipLaunchKernelGGL(cloud_info_kernel, dim3(nb), dim3(1024), 0, st, points, lengths, nb, dl, origin_mode, info, status);
     DR_LAUNCH_CHECK();
     hipLaunchKernelGGL(point_key_kernel, dim3((n_pad + 255) / 256), dim3(256), 0, st, points, n, n_pad, info, nb, dl, keys, vals);
     DR_LAUNCH_CHECK();
@@ -461,11 +506,57 @@ int dr_grid_subsample_f32(int n, int nb, const float* points, const int32_t* len
     return DR_OK;
 }
 
+int dr_grid_subsample_f32(int n, int nb, const float* points, const int32_t* lengths, float dl, float* out_points,
+                          int32_t* out_lengths, int32_t* out_total, int32_t* status, void* workspace, size_t workspace_bytes,
+                          void* stream) {
+    return grid_subsample_impl(CL_ORIGIN_KPCONV, n, nb, points, lengths, dl, out_points, out_lengths, out_total, status, workspace,
+                               workspace_bytes, stream);
+}
+
+int dr_grid_subsample_vision3d_f32(int n, int nb, const float* points, const int32_t* lengths, float voxel_size, float* out_points,
+                                   int32_t* out_lengths, int32_t* out_total, int32_t* status, void* workspace, size_t workspace_bytes,
+                                   void* stream) {
+    return grid_subsample_impl(CL_ORIGIN_VISION3D, n, nb, points, lengths, voxel_size, out_points, out_lengths, out_total, status,
+                               workspace, workspace_bytes, stream);
+}
+
 size_t dr_radius_neighbors_workspace_bytes(int nq, int ns, int nb) {
     if (ns <= 0 || nb <= 0) return 0;
     const int n_pad = next_pow2(ns);
     return 2 * align256(sizeof(CloudInfo) * nb) + align256(8ull * n_pad) + align256(4ull * n_pad) + align256(16ull * ns) +
            align256(sizeof(CellSlot) * 2ull * n_pad);
+}
+
+// the supports sorted by cell and their cell table in `workspace` (dr_radius_neighbors_workspace_bytes; ns > 0) -> *B
+static int build_ball_index(int nq, int ns, int nb, const float* queries, const float* supports, const int32_t* q_lengths,
+                            const int32_t* s_lengths, float radius, int32_t* status, void* workspace, hipStream_t st, BallArgs* B) {
+    const int n_pad = next_pow2(ns);
+    char* w = (char*)workspace;
+    CloudInfo* q_info = (CloudInfo*)w; w += align256(sizeof(CloudInfo) * nb);
+    CloudInfo* s_info = (CloudInfo*)w; w += align256(sizeof(CloudInfo) * nb);
+    unsigned long long* keys = (unsigned long long*)w; w += align256(8ull * n_pad);
+    unsigned* vals = (unsigned*)w; w += align256(4ull * n_pad);
+    float4* sorted = (float4*)w; w += align256(16ull * ns);
+    CellSlot* tab = (CellSlot*)w;
+    const unsigned tab_size = 2u * (unsigned)n_pad;
+    const float cell = radius * (1.0f + 1.0f / 128.0f);
+    B->queries = queries; B->nq = nq; B->q_info = q_info; B->s_info = s_info; B->nb = nb; B->tab = tab; B->mask = tab_size - 1;
+    B->sorted = sorted; B->ns = ns; B->cell = cell; B->r2 = radius * radius;
+    // (the query table only provides the cloud boundaries of the stacked queries)
+    hipLaunchKernelGGL(cloud_info_kernel, dim3(nb), dim3(1024), 0, st, queries, q_lengths, nb, cell, CL_ORIGIN_MIN, q_info, status);
+    DR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(cloud_info_kernel, dim3(nb), dim3(1024), 0, st, supports, s_lengths, nb, cell, CL_ORIGIN_MIN, s_info, status);
+    DR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(point_key_kernel, dim3((n_pad + 255) / 256), dim3(256), 0, st, supports, ns, n_pad, s_info, nb, cell, keys, vals);
+    DR_LAUNCH_CHECK();
+    int rc = launch_bitonic_sort(keys, vals, n_pad, st);
+    if (rc != DR_OK) return rc;
+    hipLaunchKernelGGL(gather_sorted_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, vals, ns, supports, sorted);
+    DR_LAUNCH_CHECK();
+    DR_HIP_CHECK(hipMemsetAsync(tab, 0xFF, sizeof(CellSlot) * (size_t)tab_size, st));
+    hipLaunchKernelGGL(cell_table_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, keys, ns, tab, tab_size - 1);
+    DR_LAUNCH_CHECK();
+    return DR_OK;
 }
 
 int dr_radius_neighbors_f32(int nq, int ns, int nb, const float* queries, const float* supports, const int32_t* q_lengths,
@@ -478,38 +569,38 @@ int dr_radius_neighbors_f32(int nq, int ns, int nb, const float* queries, const 
     DR_HIP_CHECK(hipMemsetAsync(status, 0, sizeof(int32_t), st));
     if (nq == 0) return DR_OK;
     if (!queries || !out || (ns > 0 && !supports)) return DR_EINVAL;
-    if (ns > 0 && (!workspace || workspace_bytes < dr_radius_neighbors_workspace_bytes(nq, ns, nb))) return DR_EWORKSPACE;
-    const int n_pad = next_pow2(ns > 0 ? ns : 1);
-    char* w = (char*)workspace;
-    CloudInfo* q_info = (CloudInfo*)w; w += align256(sizeof(CloudInfo) * nb);
-    CloudInfo* s_info = (CloudInfo*)w; w += align256(sizeof(CloudInfo) * nb);
-    unsigned long long* keys = (unsigned long long*)w; w += align256(8ull * n_pad);
-    unsigned* vals = (unsigned*)w; w += align256(4ull * n_pad);
-    float4* sorted = (float4*)w; w += align256(16ull * (ns > 0 ? ns : 1));
-    CellSlot* tab = (CellSlot*)w;
-    const unsigned tab_size = 2u * (unsigned)n_pad;
-    const float cell = radius * (1.0f + 1.0f / 128.0f);
+    if (ns == 0) return DR_OK;
+    if (!workspace || workspace_bytes < dr_radius_neighbors_workspace_bytes(nq, ns, nb)) return DR_EWORKSPACE;
     NbArgs A{};
-    A.queries = queries; A.nq = nq; A.q_info = q_info; A.s_info = s_info; A.nb = nb; A.tab = tab; A.mask = tab_size - 1; A.sorted = sorted; A.ns = ns;
-    A.cell = cell; A.r2 = radius * radius; A.limit = limit; A.out = (long long*)out; A.max_count = max_count;
+    A.limit = limit; A.out = (long long*)out; A.max_count = max_count;
+    int rc = build_ball_index(nq, ns, nb, queries, supports, q_lengths, s_lengths, radius, status, workspace, st, &A.ball);
+    if (rc != DR_OK) return rc;
+    hipLaunchKernelGGL(radius_query_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, A);
+    DR_LAUNCH_CHECK();
+    return DR_OK;
+}
+
+size_t dr_radius_count_hist_workspace_bytes(int nq, int ns, int nb) { return dr_radius_neighbors_workspace_bytes(nq, ns, nb); }
+
+int dr_radius_count_hist_f32(int nq, int ns, int nb, const float* queries, const float* supports, const int32_t* q_lengths,
+                             const int32_t* s_lengths, float radius, int hist_n, int32_t* hist, int32_t* counts, int32_t* status,
+                             void* workspace, size_t workspace_bytes, void* stream) {
+    if (nq < 0 || ns < 0 || nb <= 0 || nb >= (1 << 15) || !(radius > 0.f) || hist_n < 1 || hist_n > CH_MAX_BINS) return DR_EINVAL;
+    if (!q_lengths || !s_lengths || !hist || !status) return DR_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    DR_HIP_CHECK(hipMemsetAsync(status, 0, sizeof(int32_t), st));
+    if (nq == 0) return DR_OK;
+    if (!queries || (ns > 0 && !supports)) return DR_EINVAL;
+    if (ns > 0 && (!workspace || workspace_bytes < dr_radius_count_hist_workspace_bytes(nq, ns, nb))) return DR_EWORKSPACE;
+    CountArgs C{};
+    C.hist_n = hist_n; C.hist = hist; C.counts = counts;
+    C.ball.nq = nq; C.ball.ns = 0;           // ns = 0: the sweep reads nothing, every count is 0
     if (ns > 0) {
-        // (the query table only provides the cloud boundaries of the stacked queries)
-        hipLaunchKernelGGL(cloud_info_kernel, dim3(nb), dim3(1024), 0, st, queries, q_lengths, nb, cell, 0, q_info, status);
-        DR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(cloud_info_kernel, dim3(nb), dim3(1024), 0, st, supports, s_lengths, nb, cell, 0, s_info, status);
-        DR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(point_key_kernel, dim3((n_pad + 255) / 256), dim3(256), 0, st, supports, ns, n_pad, s_info, nb, cell, keys, vals);
-        DR_LAUNCH_CHECK();
-        int rc = launch_bitonic_sort(keys, vals, n_pad, st);
+        int rc = build_ball_index(nq, ns, nb, queries, supports, q_lengths, s_lengths, radius, status, workspace, st, &C.ball);
         if (rc != DR_OK) return rc;
-        hipLaunchKernelGGL(gather_sorted_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, vals, ns, supports, sorted);
-        DR_LAUNCH_CHECK();
-        DR_HIP_CHECK(hipMemsetAsync(tab, 0xFF, sizeof(CellSlot) * (size_t)tab_size, st));
-        hipLaunchKernelGGL(cell_table_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, keys, ns, tab, tab_size - 1);
-        DR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(radius_query_kernel, dim3((nq + 63) / 64), dim3(64), 0, st, A);
-        DR_LAUNCH_CHECK();
     }
+    hipLaunchKernelGGL(radius_count_hist_kernel, dim3((nq + CH_BLOCK - 1) / CH_BLOCK), dim3(CH_BLOCK), 0, st, C);
+    DR_LAUNCH_CHECK();
     return DR_OK;
 }
 

@@ -258,6 +258,9 @@ SIGNATURES.update({
     "dr_registration_recall_f64": (c_int, [c_int] + [c_void_p] * 5 + [c_double, c_void_p, c_void_p, c_void_p]),
     "dr_grid_subsample_workspace_bytes": (c_size_t, [c_int, c_int]),
     "dr_grid_subsample_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_float] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "dr_grid_subsample_vision3d_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_float] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+    "dr_radius_count_hist_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dr_radius_count_hist_f32": (c_int, [c_int, c_int, c_int] + [c_void_p] * 4 + [c_float, c_int] + [c_void_p] * 4 + [c_size_t, c_void_p]),
     "dr_radius_neighbors_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
     "dr_radius_neighbors_f32": (c_int, [c_int, c_int, c_int] + [c_void_p] * 4 + [c_float, c_int] + [c_void_p] * 4 + [c_size_t, c_void_p]),
     "dr_mutual_topk_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
@@ -1904,9 +1907,10 @@ def rows_normalize_chw_backward(feats, grad_out, rows=None):
 # ------------------------------------------------------------------------------------------------
 # collate-time ops: stacked clouds [n,3] float32 + lengths int32 [nb], all on the device
 # ------------------------------------------------------------------------------------------------
-def grid_subsample(points, lengths, dl):
+def grid_subsample(points, lengths, dl, vision3d=False):
     """-> (sub_points [n,3] buffer, sub_lengths [nb] int32, total [1] int32, status [1] int32), asynchronous; the first
-    total[0] rows of the buffer are valid (cpp_subsampling.subsample_batch, grid_subsampling.cpp:4-211)"""
+    total[0] rows of the buffer are valid (cpp_subsampling.subsample_batch, grid_subsampling.cpp:4-211; vision3d = True: the
+    2D-3D loader's vision3d/csrc/cpu/grid_subsampling/grid_subsampling.cpp, whose grid origin is floor(min / dl) * dl)"""
     points = points.to(torch.float32).contiguous()
     lengths = lengths.to(device=points.device, dtype=torch.int32).contiguous()
     n, nb = points.shape[0], lengths.shape[0]
@@ -1917,8 +1921,8 @@ def grid_subsample(points, lengths, dl):
     status = torch.empty(1, dtype=torch.int32, device=dev)
     wsb = _lib.dr_grid_subsample_workspace_bytes(n, nb)
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-    check(_lib.dr_grid_subsample_f32(n, nb, ptr(points), ptr(lengths), float(dl), ptr(out), ptr(ol), ptr(tot), ptr(status), ptr(ws),
-                                     wsb, stream_of(points)))
+    entry = _lib.dr_grid_subsample_vision3d_f32 if vision3d else _lib.dr_grid_subsample_f32
+    check(entry(n, nb, ptr(points), ptr(lengths), float(dl), ptr(out), ptr(ol), ptr(tot), ptr(status), ptr(ws), wsb, stream_of(points)))
     return out, ol, tot, status
 
 
@@ -1939,6 +1943,29 @@ def radius_neighbors(queries, supports, q_lengths, s_lengths, radius, limit):
     check(_lib.dr_radius_neighbors_f32(nq, ns, nb, ptr(queries), ptr(supports), ptr(ql), ptr(sl), float(radius), int(limit), ptr(out),
                                        ptr(mc), ptr(status), ptr(ws), wsb, stream_of(queries)))
     return out, mc, status
+
+
+def radius_count_hist(queries, supports, q_lengths, s_lengths, radius, hist, counts=None):
+    """hist int32 [hist_n] (device, accumulated in place): hist[c] += 1 for every query with c < hist_n supports of its own cloud at
+    d^2 < radius^2; counts int32 [nq] (optional) receives every c.  -> status [1] int32, asynchronous.  The allocations are torch's
+    caching allocator's: the call can be captured in a graph (calibrate_neighbors_pack_mode, vision3d/utils/dataloader.py:42-67)."""
+    queries = queries.to(torch.float32).contiguous()
+    supports = supports.to(torch.float32).contiguous()
+    dev = queries.device
+    ql = q_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    sl = s_lengths.to(device=dev, dtype=torch.int32).contiguous()
+    nq, ns, nb = queries.shape[0], supports.shape[0], ql.shape[0]
+    if hist.dtype != torch.int32 or hist.dim() != 1 or not hist.is_contiguous() or hist.device != dev:
+        raise ValueError("radius_count_hist: hist must be a contiguous int32 vector on the queries' device")
+    if counts is not None and (counts.dtype != torch.int32 or counts.shape != (nq,) or not counts.is_contiguous() or counts.device != dev):
+        raise ValueError("radius_count_hist: counts must be a contiguous int32 [nq] vector on the queries' device")
+    status = torch.empty(1, dtype=torch.int32, device=dev)
+    wsb = _lib.dr_radius_count_hist_workspace_bytes(nq, ns, nb)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    check(_lib.dr_radius_count_hist_f32(nq, ns, nb, ptr(queries), ptr(supports), ptr(ql), ptr(sl), float(radius), int(hist.shape[0]),
+                                        ptr(hist), ptr(counts) if counts is not None else None, ptr(status), ptr(ws), wsb,
+                                        stream_of(queries)))
+    return status
 
 
 def batch_mutual_topk_select(score_mat, k, row_masks=None, col_masks=None, largest=True, threshold=None, mutual=True):

@@ -102,6 +102,17 @@ depth_head=True as well, everything from the transformed image tensor to the dep
 
     accelerate(model, depth_encoder=True, depth_head=True)
 
+pyramid=dict(num_stages=4, voxel_size=0.025, search_radius=0.0625, neighbor_limits=[...]): the graph pyramid the point backbone reads (`points`,
+`lengths`, `neighbors`, `subsampling`, `upsampling`) is built on the device (diffreg_hip/pyramid2d3d.py on csrc/collate.hip: vision3d's grid
+subsampling bit for bit up to the order of a stage's points, its radius search index for index on those points) instead of on the data loader's CPU
+workers by GraphPyramid2D3DRegistrationCollateFn.  `model.forward` is re-bound on the instance: a `data_dict` whose `points` is still the stacked
+[N, 3] tensor of a pyramid-less collate (with `lengths`; one cloud when absent) gets the five lists before the model's own forward runs; a dict that
+already carries the lists passes through untouched.  `remove()` restores `forward`.  A neighbour limit above 64 raises NotImplementedError here,
+before any site is bound.  The limits themselves come from pyramid2d3d.calibrate_neighbors_pack_mode, which needs no compiled vision3d extension
+either.  The flag is opt-in (default None) and combines with every other flag.
+
+    accelerate(model, backbone=True, pyramid=dict(num_stages=4, voxel_size=0.025, search_radius=0.0625, neighbor_limits=limits))
+
 What then stays the reference's code in a training step: the host-side Resize / NormalizeImage transform in front of Depth-Anything, the encoder's CNN
 branch (`encoder.cnn`, whose outputs MATR2D3D.forward discards) and `dino_2_u`, the inline GT retry ladder and the other inline glue of
 MATR2D3D.forward.
@@ -117,8 +128,12 @@ from .engine import DenoiseEngine2D3D
 
 class LoopOverlay2D3D:
     def __init__(self, model, n_head=4, engine_kwargs=None, training=False, partition=False, backbone=False, noising=False, front=False,
-                 image_backbone=False, image_backbone_grad=False, dino=False, depth_head=False, depth_encoder=False):
+                 image_backbone=False, image_backbone_grad=False, dino=False, depth_head=False, depth_encoder=False, pyramid=None):
         self.model = model
+        self.pyramid = None
+        if pyramid is not None:             # first: a neighbour limit above 64 raises NotImplementedError here, before any site is bound
+            from . import pyramid2d3d
+            self.pyramid = pyramid2d3d.GraphPyramid2D3DCollate(**pyramid)
         self.dino = bool(dino)
         self.depth_head = bool(depth_head)
         self.depth_encoder = bool(depth_encoder)
@@ -176,9 +191,19 @@ class LoopOverlay2D3D:
             from . import front2d3d as f
             self._bind_globals({name: getattr(f, name) for name in ("back_project", "render", "create_meshgrid")})
             model.back_project_depth = f.back_project_depth
+        if self.pyramid is not None:
+            self._orig.update(forward=model.forward)
+            model.forward = self._forward
         model._dr_overlay = self
 
     _MISSING = object()
+
+    def _forward(self, data_dict, *args, **kwargs):
+        """pyramid=...: a dict whose `points` is still the stacked [N, 3] tensor of a pyramid-less collate gets the five lists here, on the device;
+        a dict that already carries the lists passes through untouched"""
+        if torch.is_tensor(data_dict.get("points")):
+            self.pyramid(data_dict)
+        return self._orig["forward"](data_dict, *args, **kwargs)
 
     def _unbind_front_modules(self):
         """a later bind refused: take off what the earlier flags of this constructor bound, so that a refusal leaves no site bound"""
@@ -217,6 +242,8 @@ class LoopOverlay2D3D:
             sites += [(m, "back_project_depth")]
         if self.image_backbone:
             sites += [(m.img_backbone, "forward")]
+        if self.pyramid is not None:
+            sites += [(m, "forward")]
         if self.dino:
             self.dino_binding.remove()
         if self.depth_head:
@@ -327,7 +354,7 @@ class LoopOverlay2D3D:
 
 
 def accelerate(model, n_head=4, training=False, partition=False, backbone=False, noising=False, front=False, image_backbone=False,
-               image_backbone_grad=False, dino=False, depth_head=False, depth_encoder=False, **engine_kwargs):
+               image_backbone_grad=False, dino=False, depth_head=False, depth_encoder=False, pyramid=None, **engine_kwargs):
     """install the overlay on a MATR2D3D instance (see the module docstring); returns the LoopOverlay2D3D (`.remove()` undoes it).
     training=True: the training branch's four coarse modules run on the device under model.train() as well.
     partition=True: the patch partition and GT patch overlaps (and, with training, the GT search) run on the device as well.
@@ -341,10 +368,12 @@ def accelerate(model, n_head=4, training=False, partition=False, backbone=False,
     depth_head=True: model.depth_model.depth_head (Depth-Anything's DPT decoder) runs on the device in float32 (eval mode under torch.no_grad();
     otherwise its own code).
     depth_encoder=True: model.depth_model.pretrained.get_intermediate_layers (Depth-Anything's float32 ViT-L/14) runs on the device in exact fp32
-    products (eval mode under torch.no_grad() with a CUDA float32 batch; otherwise its own code)."""
+    products (eval mode under torch.no_grad() with a CUDA float32 batch; otherwise its own code).
+    pyramid=dict(num_stages=, voxel_size=, search_radius=, neighbor_limits=): model.forward builds the graph pyramid on the device when
+    data_dict["points"] is the stacked tensor of a pyramid-less collate (diffreg_hip/pyramid2d3d.py); None (the default) touches nothing."""
     return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs, training=training, partition=partition, backbone=backbone,
                            noising=noising, front=front, image_backbone=image_backbone, image_backbone_grad=image_backbone_grad,
-                           dino=dino, depth_head=depth_head, depth_encoder=depth_encoder)
+                           dino=dino, depth_head=depth_head, depth_encoder=depth_encoder, pyramid=pyramid)
 
 
 def accelerate_loss(loss_module, fine=False):

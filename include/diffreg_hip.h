@@ -60,7 +60,9 @@ extern "C" {
  *   0.7.0, seventh set (same rule)  the Depth-Anything DPT head's forward on token rows: dr_conv2d_rows_act_f32,
  *          dr_conv_transpose2d_rows_f32, dr_conv2d_rows_project_f32 (new entries only; nothing older changed).
  *   0.7.0, eighth set (same rule)  Depth-Anything's float32 ViT encoder forward: dr_gemm_rows_f32, dr_patch_rows_f32, dr_vit_forward_f32 with
- *          dr_vit_workspace_bytes_f32 (new entries only; nothing older changed). */
+ *          dr_vit_workspace_bytes_f32 (new entries only; nothing older changed).
+ *   0.7.0, ninth set (same rule)  the 2D-3D loader's graph pyramid and neighbour-limit calibration: dr_grid_subsample_vision3d_f32,
+ *          dr_radius_count_hist_f32 with dr_radius_count_hist_workspace_bytes (new entries only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1341,6 +1343,42 @@ int dr_gemm_rows_f32(const dr_gemm_rows_f32_args* args, void* stream);
 int dr_patch_rows_f32(int H, int W, int p, const float* img, float* out, int ldo, void* stream);
 size_t dr_vit_workspace_bytes_f32(int H, int W, int p, int D, int Dh);
 int dr_vit_forward_f32(const dr_vit_config_f32* cfg, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, ninth set (detected by symbol like the fourth to eighth sets): the collate-time native code of the 2D-3D loader
+ * (GraphPyramid2D3DRegistrationCollateFn, vision3d/utils/collate.py:265-310 -> vision3d/array_ops/graph_pyramid.py:9-70 -> the two functions of
+ * vision3d/csrc/cpu/) and the calibration of its neighbour limits (calibrate_neighbors_pack_mode, vision3d/utils/dataloader.py:42-67).
+ * csrc/collate.hip; DESIGN 5s.  Lengths are int32 [nb] on the device as for the other collate entries; `status` has their meaning; nothing
+ * synchronises, nothing allocates, every entry can be captured in a graph.
+ *
+ * vision3d's two functions against the KPConv forms the older entries restate, expression by expression:
+ *   grid_subsampling.cpp:32   origin = floor(min_corner / voxel_size) * voxel_size     DIFFERS: KPConv multiplies by the float reciprocal,
+ *                             floor(min * (1 / dl)) * dl, which names another origin when min / voxel_size lies within a rounding of an
+ *                             integer -- hence dr_grid_subsample_vision3d_f32
+ *   grid_subsampling.cpp:39-41  floor((p - origin) / voxel_size) per axis               same
+ *   grid_subsampling.h:23-26  count += 1; point += p, in input order (cloud.h:50-55)    same
+ *   grid_subsampling.cpp:52   point * (1.0 / count): the double reciprocal narrowed to float by operator*(Point, const float) (cloud.h:76)   same
+ *   radius_neighbors.cpp:24-60  radius2 = radius * radius in float; nanoflann 1.3.0 L2_Simple_Adaptor (result += diff * diff per axis),
+ *                             RadiusResultSet::addPoint keeps dist < radius (strict), search_params.sorted = true   same
+ *   radius_neighbors.cpp:82-84  cloud-local index + the cloud's first support row; padding = the total number of supports   same
+ * so dr_radius_neighbors_f32 serves vision3d's radius_neighbors(...)[:, :limit] as it is (limits above 64 stay DR_EINVAL).
+ *
+ * dr_grid_subsample_vision3d_f32: dr_grid_subsample_f32 with vision3d's origin; same arguments, same output order (per cloud ascending
+ *   (iz, iy, ix); the reference emits std::unordered_map order), same workspace (dr_grid_subsample_workspace_bytes).  A cloud of length 0
+ *   yields length 0.
+ * dr_radius_count_hist_f32: per query the NUMBER of supports of its own cloud with d^2 < radius^2 -- the float32 expression and the sweep of
+ *   dr_radius_neighbors_f32, with a counter in place of the list: the count has no upper limit.  hist [hist_n] int32 is ACCUMULATED:
+ *   hist[count] += 1 when count < hist_n; counts >= hist_n are not recorded (np.bincount(c, minlength=hist_n)[:hist_n] of a matrix cut at
+ *   hist_n columns, dataloader.py:56-58).  The caller zeroes hist before the first call.  counts [nq] int32 or NULL receives every count.
+ *   1 <= hist_n <= 4096 (the bins of a workgroup live in LDS), else DR_EINVAL; ns = 0 records nq counts of 0.  Integer atomics only: two runs
+ *   are bit-equal.  Workspace: dr_radius_count_hist_workspace_bytes(nq, ns, nb), DR_EWORKSPACE when smaller. */
+int dr_grid_subsample_vision3d_f32(int n, int nb, const float* points, const int32_t* lengths, float voxel_size, float* out_points,
+                                   int32_t* out_lengths, int32_t* out_total, int32_t* status, void* workspace, size_t workspace_bytes,
+                                   void* stream);
+size_t dr_radius_count_hist_workspace_bytes(int nq, int ns, int nb);
+int dr_radius_count_hist_f32(int nq, int ns, int nb, const float* queries, const float* supports, const int32_t* q_lengths,
+                             const int32_t* s_lengths, float radius, int hist_n, int32_t* hist, int32_t* counts, int32_t* status,
+                             void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
