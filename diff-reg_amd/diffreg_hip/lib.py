@@ -388,6 +388,17 @@ SIGNATURES.update({
 })
 
 
+class ImageNorm(ctypes.Structure):
+    """dr_image_norm"""
+    _fields_ = [("mean", ctypes.c_double * 3), ("std", ctypes.c_double * 3)]
+
+
+SIGNATURES.update({
+    # added after ABI 0.7.0, tenth set: the input transform in front of Depth-Anything (csrc/image_transform.hip)
+    "dr_image_cubic_chw_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(ImageNorm), c_void_p, c_void_p]),
+})
+
+
 def _bind(table):
     for name, (res, args) in table.items():
         if not hasattr(_lib, name):          # the sets added under one ABI number are detected by symbol

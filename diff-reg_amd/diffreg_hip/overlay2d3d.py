@@ -86,7 +86,8 @@ depth_anything/dpt.py:103-136, reached through EXP/model.py:343-351) runs on the
 convolution with the pre-activation / two-addend epilogue, the transposed convolution as a GEMM with a pixel-shuffle store, the fused tail and the
 row resample of csrc/conv2d.hip): `depth_head.forward` is re-bound on the instance and `remove()` restores it.  The device path runs in eval mode
 under torch.no_grad() with CUDA float32 inputs of batch 1; otherwise the bound forward calls the module's own code unchanged.  The trailing
-F.interpolate + relu of DPT_DINOv2.forward (dpt.py:163-164) and the host-side Resize transform stay as they are.  A head the kernels do not cover
+F.interpolate + relu of DPT_DINOv2.forward (dpt.py:163-164) and the host-side Resize transform stay as they are (depth_transform=True, below, moves
+both).  A head the kernels do not cover
 (use_clstoken, nclass > 1, batch norm, ...) raises NotImplementedError here, before any site is bound.  The flag is opt-in and defaults off.
 
     accelerate(model, depth_head=True)
@@ -113,7 +114,21 @@ either.  The flag is opt-in (default None) and combines with every other flag.
 
     accelerate(model, backbone=True, pyramid=dict(num_stages=4, voxel_size=0.025, search_radius=0.0625, neighbor_limits=limits))
 
-What then stays the reference's code in a training step: the host-side Resize / NormalizeImage transform in front of Depth-Anything, the encoder's CNN
+With `depth_transform=True` (implies depth_encoder=True, depth_head=True; any combination of the flags above) the input transform in front of
+Depth-Anything (EXP/model.py:339-342: the device-to-host copy, Resize with cv2.INTER_CUBIC, NormalizeImage, PrepareForNet, the copy back) runs on
+the device as one launch (diffreg_hip/depth_transform2d3d.py, csrc/image_transform.hip) and the whole depth branch becomes one engine
+(diffreg_hip/depth_branch2d3d.py), in eval and in train mode, under its own torch.no_grad().  Three sites are re-bound: `model.forward` on the
+instance stashes `data_dict["image"]` (composed with the pyramid's wrapper when both are set); `model.transform` on the instance returns
+`{"image": <zero-size float32 ndarray>}` while an image is stashed; `predict_depth` in the globals of the model's defining module runs the engine
+on the stashed device image when that zero-size image arrives and calls the original `predict_depth` on a real image.  `remove()` restores all
+three.  In an unmodified file the inline `image.squeeze(0).squeeze(0).cpu().numpy()` of line 339 still executes, so ONE device-to-host copy (and
+its stream drain) remains; the one-line edit of model.py:339-342 that calls `model._dr_overlay.depth(image)` removes it.
+`depth_transform=dict(graph=True)` replays the branch as one captured graph (the depth map is then the graph's static output, valid until the next
+forward); other keys of the dict go to DeviceTransform.  The flag is opt-in and defaults off.
+
+    accelerate(model, depth_transform=True)
+
+What then stays the reference's code in a training step: the encoder's CNN
 branch (`encoder.cnn`, whose outputs MATR2D3D.forward discards) and `dino_2_u`, the inline GT retry ladder and the other inline glue of
 MATR2D3D.forward.
 """
@@ -128,8 +143,18 @@ from .engine import DenoiseEngine2D3D
 
 class LoopOverlay2D3D:
     def __init__(self, model, n_head=4, engine_kwargs=None, training=False, partition=False, backbone=False, noising=False, front=False,
-                 image_backbone=False, image_backbone_grad=False, dino=False, depth_head=False, depth_encoder=False, pyramid=None):
+                 image_backbone=False, image_backbone_grad=False, dino=False, depth_head=False, depth_encoder=False, pyramid=None,
+                 depth_transform=False):
         self.model = model
+        self._attr_saved = []
+        self.depth_transform = depth_transform is not None and depth_transform is not False
+        self.depth_branch, self._depth_image = None, None
+        if self.depth_transform:            # first: a transform that cannot be built raises here, before any site is bound
+            from .depth_transform2d3d import DeviceTransform
+            opts = dict(depth_transform) if isinstance(depth_transform, dict) else {}
+            self._depth_graph = bool(opts.pop("graph", False))
+            self._depth_device_transform = DeviceTransform(**opts)
+            depth_head = depth_encoder = True
         self.pyramid = None
         if pyramid is not None:             # first: a neighbour limit above 64 raises NotImplementedError here, before any site is bound
             from . import pyramid2d3d
@@ -162,6 +187,9 @@ class LoopOverlay2D3D:
             except NotImplementedError:
                 self._unbind_front_modules()
                 raise
+        if self.depth_transform:            # both are bound: the engine reuses them and has nothing left to refuse
+            from .depth_branch2d3d import DepthBranch2D3D
+            self.depth_branch = DepthBranch2D3D(model.depth_model, transform=self._depth_device_transform)
         self._globals_saved = {}
         self.n_head = n_head
         self.engine_kwargs = dict(engine_kwargs or {})
@@ -191,9 +219,13 @@ class LoopOverlay2D3D:
             from . import front2d3d as f
             self._bind_globals({name: getattr(f, name) for name in ("back_project", "render", "create_meshgrid")})
             model.back_project_depth = f.back_project_depth
-        if self.pyramid is not None:
+        if self.pyramid is not None or self.depth_transform:
             self._orig.update(forward=model.forward)
-            model.forward = self._forward
+            self._bind_attr(model, "forward", self._forward)
+        if self.depth_transform:
+            self._orig.update(transform=model.transform)
+            self._bind_attr(model, "transform", self._transform)
+            self._bind_globals({"predict_depth": self._predict_depth})
         model._dr_overlay = self
 
     _MISSING = object()
@@ -201,9 +233,52 @@ class LoopOverlay2D3D:
     def _forward(self, data_dict, *args, **kwargs):
         """pyramid=...: a dict whose `points` is still the stacked [N, 3] tensor of a pyramid-less collate gets the five lists here, on the device;
         a dict that already carries the lists passes through untouched"""
-        if torch.is_tensor(data_dict.get("points")):
+        if self.pyramid is not None and torch.is_tensor(data_dict.get("points")):
             self.pyramid(data_dict)
-        return self._orig["forward"](data_dict, *args, **kwargs)
+        if not self.depth_transform:
+            return self._orig["forward"](data_dict, *args, **kwargs)
+        self._depth_image = self._device_image(data_dict.get("image"))       # depth_transform: what the depth branch of this forward reads
+        try:
+            return self._orig["forward"](data_dict, *args, **kwargs)
+        finally:
+            self._depth_image = None
+
+    # ---- depth_transform: the three sites of EXP/model.py:339-342 ----------------------------------------------------------------------------
+    @staticmethod
+    def _device_image(image):
+        """data_dict["image"] ([1, H, W, 3] on the device) as the [H, W, 3] view the transform reads, or None when it is anything else"""
+        if not (torch.is_tensor(image) and image.is_cuda and image.dtype == torch.float32 and image.dim() >= 3 and image.shape[-1] == 3):
+            return None
+        if any(n != 1 for n in image.shape[:-3]):
+            return None
+        return image.detach().reshape(image.shape[-3:])
+
+    def depth(self, image):
+        """the depth map [1, h, w] of a device image ([H, W, 3] behind any number of leading 1s): what `predict_depth(self.depth_model,
+        transform(image))` returns, with no host copy (INTEGRATION.md gives the one-line edit of model.py:339-342 that calls this)"""
+        img = self._device_image(image)
+        if img is None:
+            raise TypeError("overlay depth: a CUDA float32 [..., H, W, 3] tensor with leading dimensions of 1; there is no CPU path")
+        return self.depth_branch(img, graph=self._depth_graph)
+
+    def _transform(self, sample):
+        """model.transform: with a device image stashed by forward the host transform has nothing to do (a zero-size image goes through
+        torch.from_numpy(...).unsqueeze(0).cuda() and tells _predict_depth to read the stash); anything else is the reference's own transform"""
+        if self._depth_image is not None:
+            import numpy as np
+            return {"image": np.zeros((3, 0, 0), dtype=np.float32)}
+        return self._orig["transform"](sample)
+
+    def _predict_depth(self, depth_model, image):
+        """predict_depth in the model's globals: the engine on the stashed device image (eval or train mode, under its own no_grad) when the
+        zero-size image of _transform arrives; the original predict_depth on a real image"""
+        if self._depth_image is not None and depth_model is self.model.depth_model and torch.is_tensor(image) and image.numel() == 0:
+            return self.depth_branch(self._depth_image, graph=self._depth_graph)
+        orig = self._globals_saved.get("predict_depth", self._MISSING)
+        if orig is self._MISSING:
+            with torch.no_grad():
+                return depth_model(image)
+        return orig(depth_model, image)
 
     def _unbind_front_modules(self):
         """a later bind refused: take off what the earlier flags of this constructor bound, so that a refusal leaves no site bound"""
@@ -221,6 +296,11 @@ class LoopOverlay2D3D:
         if self.training:
             names += ["get_correspondences", "to_o3d_pcd"]
         self._bind_globals({name: getattr(p, name) for name in names})
+
+    def _bind_attr(self, obj, name, value):
+        """set an instance attribute and remember what the instance's own __dict__ held before (nothing, for a method of the class)"""
+        self._attr_saved.append((obj, name, obj.__dict__.get(name, self._MISSING)))
+        setattr(obj, name, value)
 
     def _bind_globals(self, table):
         g = vars(sys.modules[type(self.model).__module__])
@@ -242,8 +322,8 @@ class LoopOverlay2D3D:
             sites += [(m, "back_project_depth")]
         if self.image_backbone:
             sites += [(m.img_backbone, "forward")]
-        if self.pyramid is not None:
-            sites += [(m, "forward")]
+        if self.depth_branch is not None:    # (binds nothing of its own here: the two flags above did; this drops its graphs)
+            self.depth_branch.remove()
         if self.dino:
             self.dino_binding.remove()
         if self.depth_head:
@@ -253,6 +333,12 @@ class LoopOverlay2D3D:
         for obj, name in sites:
             if name in obj.__dict__:
                 del obj.__dict__[name]
+        for obj, name, old in reversed(self._attr_saved):
+            if old is self._MISSING:
+                obj.__dict__.pop(name, None)
+            else:
+                obj.__dict__[name] = old
+        self._attr_saved = []
         if self._globals_saved:
             g = vars(sys.modules[type(m).__module__])
             for name, old in self._globals_saved.items():
@@ -266,6 +352,8 @@ class LoopOverlay2D3D:
     def refresh(self):
         """call after the weights changed (load_state_dict, .to()): the engine holds its own device copy"""
         self.engine = None
+        if self.depth_branch is not None:
+            self.depth_branch.refresh()
 
     # ---- engine from the model's own weights and hyper-parameters ------------------------------------------------------------
     def _build(self, device):
@@ -354,7 +442,8 @@ class LoopOverlay2D3D:
 
 
 def accelerate(model, n_head=4, training=False, partition=False, backbone=False, noising=False, front=False, image_backbone=False,
-               image_backbone_grad=False, dino=False, depth_head=False, depth_encoder=False, pyramid=None, **engine_kwargs):
+               image_backbone_grad=False, dino=False, depth_head=False, depth_encoder=False, pyramid=None, depth_transform=False,
+               **engine_kwargs):
     """install the overlay on a MATR2D3D instance (see the module docstring); returns the LoopOverlay2D3D (`.remove()` undoes it).
     training=True: the training branch's four coarse modules run on the device under model.train() as well.
     partition=True: the patch partition and GT patch overlaps (and, with training, the GT search) run on the device as well.
@@ -370,10 +459,13 @@ def accelerate(model, n_head=4, training=False, partition=False, backbone=False,
     depth_encoder=True: model.depth_model.pretrained.get_intermediate_layers (Depth-Anything's float32 ViT-L/14) runs on the device in exact fp32
     products (eval mode under torch.no_grad() with a CUDA float32 batch; otherwise its own code).
     pyramid=dict(num_stages=, voxel_size=, search_radius=, neighbor_limits=): model.forward builds the graph pyramid on the device when
-    data_dict["points"] is the stacked tensor of a pyramid-less collate (diffreg_hip/pyramid2d3d.py); None (the default) touches nothing."""
+    data_dict["points"] is the stacked tensor of a pyramid-less collate (diffreg_hip/pyramid2d3d.py); None (the default) touches nothing.
+    depth_transform=True (implies depth_encoder and depth_head): Depth-Anything's input transform runs on the device and the depth branch reads
+    data_dict["image"] where it lies (diffreg_hip/depth_branch2d3d.py); depth_transform=dict(graph=True) replays the branch as one captured graph
+    (other keys go to DeviceTransform)."""
     return LoopOverlay2D3D(model, n_head=n_head, engine_kwargs=engine_kwargs, training=training, partition=partition, backbone=backbone,
                            noising=noising, front=front, image_backbone=image_backbone, image_backbone_grad=image_backbone_grad,
-                           dino=dino, depth_head=depth_head, depth_encoder=depth_encoder, pyramid=pyramid)
+                           dino=dino, depth_head=depth_head, depth_encoder=depth_encoder, pyramid=pyramid, depth_transform=depth_transform)
 
 
 def accelerate_loss(loss_module, fine=False):

@@ -62,7 +62,9 @@ extern "C" {
  *   0.7.0, eighth set (same rule)  Depth-Anything's float32 ViT encoder forward: dr_gemm_rows_f32, dr_patch_rows_f32, dr_vit_forward_f32 with
  *          dr_vit_workspace_bytes_f32 (new entries only; nothing older changed).
  *   0.7.0, ninth set (same rule)  the 2D-3D loader's graph pyramid and neighbour-limit calibration: dr_grid_subsample_vision3d_f32,
- *          dr_radius_count_hist_f32 with dr_radius_count_hist_workspace_bytes (new entries only; nothing older changed). */
+ *          dr_radius_count_hist_f32 with dr_radius_count_hist_workspace_bytes (new entries only; nothing older changed).
+ *   0.7.0, tenth set (same rule)  the input transform in front of Depth-Anything: dr_image_cubic_chw_f32 with the new struct dr_image_norm
+ *          (new entry only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1379,6 +1381,29 @@ size_t dr_radius_count_hist_workspace_bytes(int nq, int ns, int nb);
 int dr_radius_count_hist_f32(int nq, int ns, int nb, const float* queries, const float* supports, const int32_t* q_lengths,
                              const int32_t* s_lengths, float radius, int hist_n, int32_t* hist, int32_t* counts, int32_t* status,
                              void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, tenth set (detected by symbol like the fourth to ninth sets): the input transform in front of Depth-Anything,
+ * depth_anything/util/transform.py:168-178, 219-222, 232-234 (Resize.__call__ with cv2.INTER_CUBIC, NormalizeImage.__call__,
+ * PrepareForNet.__call__), which EXP/model.py:339-342 runs on the host on every forward.  csrc/image_transform.hip; DESIGN 5t.
+ *
+ * dr_image_cubic_chw_f32: src_hwc [Hs, Ws, 3] float32 with ld_src >= 3 Ws floats per source row -> out_chw [3, Hd, Wd] float32, contiguous.
+ *   The resample is OpenCV's INTER_CUBIC for CV_32F as csrc/cubic_index.h states it: per axis scale = (double)in / out; for destination d,
+ *   f = (float)((d + 0.5) scale - 0.5), s = floor(f), t = f - s in float; the Keys weights with A = -0.75 in float, the fourth as
+ *   1 - c0 - c1 - c2; taps s-1 .. s+2 clamped to [0, in-1]; no antialiasing; the 16-term blend columns first, then rows, in double on the
+ *   float32 texels, rounded once to float32 (OpenCV's float32 output).  With `normalize` non-zero each channel c then becomes
+ *   (float)(((double)v - mean[c]) / std[c]): numpy's float64 arithmetic narrowed by PrepareForNet's astype(float32).  `norm` is a HOST struct,
+ *   read when the call is enqueued and passed as kernel arguments (a captured graph keeps the values of the capture); NULL is allowed when
+ *   `normalize` is 0.  `stream` is a hipStream_t.
+ *   One launch; no workspace, no atomics, no scratch; two runs are bit-equal; nothing synchronises, so the call can be captured in a graph.
+ *   DR_EINVAL, with the output untouched: Hs, Ws, Hd or Wd < 1; ld_src < 3 Ws; a NULL src_hwc or out_chw; `normalize` with a NULL norm or a
+ *   std[c] == 0. */
+typedef struct {
+    double mean[3];
+    double std[3];
+} dr_image_norm;
+int dr_image_cubic_chw_f32(int Hs, int Ws, int ld_src, const float* src_hwc, int Hd, int Wd, int normalize, const dr_image_norm* norm,
+                           float* out_chw, void* stream);
 
 #ifdef __cplusplus
 }
