@@ -397,6 +397,12 @@ SIGNATURES.update({
     # added after ABI 0.7.0, tenth set: the input transform in front of Depth-Anything (csrc/image_transform.hip)
     "dr_image_cubic_chw_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_int, c_int, c_int, ctypes.POINTER(ImageNorm), c_void_p, c_void_p]),
 })
+SIGNATURES.update({
+    # added after ABI 0.7.0, eleventh set: the ground-truth half of the 3D / 4D training collate (csrc/collate_gt.hip)
+    "dr_blend_flow_knn3_f32": (c_int, [c_int, c_int, c_int] + [c_void_p] * 8),
+    "dr_coarse_gt_matches_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dr_coarse_gt_matches_f32": (c_int, [c_int, c_int, c_int] + [c_void_p] * 7 + [c_float] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+})
 
 
 def _bind(table):
@@ -1977,6 +1983,72 @@ def radius_count_hist(queries, supports, q_lengths, s_lengths, radius, hist, cou
                                         ptr(hist), ptr(counts) if counts is not None else None, ptr(status), ptr(ws), wsb,
                                         stream_of(queries)))
     return status
+
+
+def _offsets_i32(offsets, n_pairs, dev, name):
+    o = offsets.to(device=dev, dtype=torch.int32).contiguous()
+    if o.dim() != 1 or (n_pairs is not None and o.shape[0] != n_pairs + 1):
+        raise ValueError("%s: offsets must be a vector of P + 1 entries" % name)
+    return o
+
+
+def blend_flow_knn3(query, q_offsets, reference, reference_flow, r_offsets):
+    """-> (flow [nq, 3] float32, status [P] int32), asynchronous: blend_scene_flow(query, reference, reference_flow, knn=3) of
+    3D/datasets/utils.py:43-59 for P pairs at once; pair p's queries / references are rows [offsets[p], offsets[p + 1]) of the stacked arrays
+    (int32 device vectors of P + 1 entries).  status[p]: 0, 1 (fewer than 4 references: its rows of `flow` are zero) or 2 (bad offsets)."""
+    ensure_init()
+    query = query.to(torch.float32).contiguous()
+    dev = query.device
+    reference = reference.to(device=dev, dtype=torch.float32).contiguous()
+    reference_flow = reference_flow.to(device=dev, dtype=torch.float32).contiguous()
+    qo = _offsets_i32(q_offsets, None, dev, "blend_flow_knn3")
+    P = qo.shape[0] - 1
+    ro = _offsets_i32(r_offsets, P, dev, "blend_flow_knn3")
+    nq, nr = query.shape[0], reference.shape[0]
+    if query.shape != (nq, 3) or reference.shape != (nr, 3) or reference_flow.shape != (nr, 3):
+        raise ValueError("blend_flow_knn3: query [nq, 3], reference and reference_flow [nr, 3]")
+    out = torch.zeros(nq, 3, device=dev)
+    status = torch.empty(max(P, 0), dtype=torch.int32, device=dev)
+    check(_lib.dr_blend_flow_knn3_f32(P, nq, nr, ptr(query) if nq else None, ptr(qo), ptr(reference) if nr else None,
+                                      ptr(reference_flow) if nr else None, ptr(ro), ptr(out) if nq else None, ptr(status) if P else None,
+                                      stream_of(query)))
+    return out, status
+
+
+def coarse_gt_matches(src, s_offsets, tgt, t_offsets, rot, trn, radius, src_flow=None):
+    """-> (out_src [ns] int64, out_tgt [ns] int64, counts [P] int32, status [P] int32), asynchronous: the `get match at coarse level` block of
+    collate_fn_3dmatch / collate_fn_4dmatch (dataloader.py:253-257, 512-520) for P pairs at once.  src [ns, 3] / tgt [nt, 3] hold the pairs'
+    coarse clouds stacked each on its own, rows [offsets[p], offsets[p + 1]); rot [P, 3, 3], trn [P, 3] (or [P, 3, 1]); src_flow [ns, 3] or None.
+    Pair p's matches are out_*[s_offsets[p] : s_offsets[p] + counts[p]], pair-local indices in ascending source order.  status[p]: 0, 1 (a cloud
+    of fewer than 2 points: count 0) or 2 (bad offsets)."""
+    ensure_init()
+    src = src.to(torch.float32).contiguous()
+    dev = src.device
+    tgt = tgt.to(device=dev, dtype=torch.float32).contiguous()
+    so = _offsets_i32(s_offsets, None, dev, "coarse_gt_matches")
+    P = so.shape[0] - 1
+    to = _offsets_i32(t_offsets, P, dev, "coarse_gt_matches")
+    ns, nt = src.shape[0], tgt.shape[0]
+    rot = rot.to(device=dev, dtype=torch.float32).contiguous()
+    trn = trn.to(device=dev, dtype=torch.float32).reshape(-1, 3).contiguous()
+    if src.shape != (ns, 3) or tgt.shape != (nt, 3) or rot.shape != (P, 3, 3) or trn.shape != (P, 3):
+        raise ValueError("coarse_gt_matches: src [ns, 3], tgt [nt, 3], rot [P, 3, 3], trn [P, 3]")
+    flow = None
+    if src_flow is not None:
+        flow = src_flow.to(device=dev, dtype=torch.float32).contiguous()
+        if flow.shape != (ns, 3):
+            raise ValueError("coarse_gt_matches: src_flow must be [ns, 3]")
+    out_src = torch.empty(ns, dtype=torch.int64, device=dev)
+    out_tgt = torch.empty(ns, dtype=torch.int64, device=dev)
+    counts = torch.empty(max(P, 0), dtype=torch.int32, device=dev)
+    status = torch.empty(max(P, 0), dtype=torch.int32, device=dev)
+    wsb = _lib.dr_coarse_gt_matches_workspace_bytes(ns, nt)
+    ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
+    check(_lib.dr_coarse_gt_matches_f32(P, ns, nt, ptr(src) if ns else None, ptr(so), ptr(tgt) if nt else None, ptr(to),
+                                        ptr(flow) if (flow is not None and ns) else None, ptr(rot) if P else None, ptr(trn) if P else None,
+                                        float(radius), ptr(out_src) if ns else None, ptr(out_tgt) if ns else None, ptr(counts) if P else None,
+                                        ptr(status) if P else None, ptr(ws), wsb, stream_of(src)))
+    return out_src, out_tgt, counts, status
 
 
 def batch_mutual_topk_select(score_mat, k, row_masks=None, col_masks=None, largest=True, threshold=None, mutual=True):

@@ -64,7 +64,9 @@ extern "C" {
  *   0.7.0, ninth set (same rule)  the 2D-3D loader's graph pyramid and neighbour-limit calibration: dr_grid_subsample_vision3d_f32,
  *          dr_radius_count_hist_f32 with dr_radius_count_hist_workspace_bytes (new entries only; nothing older changed).
  *   0.7.0, tenth set (same rule)  the input transform in front of Depth-Anything: dr_image_cubic_chw_f32 with the new struct dr_image_norm
- *          (new entry only; nothing older changed). */
+ *          (new entry only; nothing older changed).
+ *   0.7.0, eleventh set (same rule)  the ground-truth half of the 3D / 4D training collate: dr_blend_flow_knn3_f32, dr_coarse_gt_matches_f32 with
+ *          dr_coarse_gt_matches_workspace_bytes (new entries only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1404,6 +1406,39 @@ typedef struct {
 } dr_image_norm;
 int dr_image_cubic_chw_f32(int Hs, int Ws, int ld_src, const float* src_hwc, int Hd, int Wd, int normalize, const dr_image_norm* norm,
                            float* out_chw, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, eleventh set (detected by symbol like the fourth to tenth sets): the ground-truth half of the 3D / 4D training
+ * collate, 3D/datasets/dataloader.py:236-259, 495-523 with 3D/datasets/utils.py:23-80, which the reference runs per pair on its loader's CPU
+ * workers.  csrc/collate_gt.hip, indices in csrc/collate_gt_index.h; DESIGN 5u.
+ *
+ * Both entries are ragged over P pairs in one call: pair p's rows of a stacked [n, 3] float32 array are [offsets[p], offsets[p + 1]) of an int32
+ * DEVICE array of P + 1 entries.  They are asynchronous on `stream` (a hipStream_t), read nothing back to the host, allocate nothing and use no
+ * atomics: two runs are bit-equal, and a call can be captured in a graph.  All float32 arithmetic is unfused, operation by operation as numpy
+ * performs it; d^2 = ((dx dx + dy dy) + dz dz) with d = reference - query; sqrtf and the divisions are correctly rounded.
+ * status [P] int32 receives per pair 0, or bit 0 (1): too few points, where the reference's np.argpartition raises; bit 1 (2): the pair's offsets
+ * are not 0 <= lo <= hi <= n.  A pair with a non-zero status is neither read nor computed.  P = 0 is a no-op; a negative size or a NULL pointer
+ * that a non-empty array needs is DR_EINVAL; n * 3 or the grid beyond 2^31 - 1 is DR_ENOSUP.
+ *
+ * dr_blend_flow_knn3_f32: blend_scene_flow(query, reference, reference_flow, knn=3) of utils.py:43-59.  Per query the three references of its
+ *   pair with the smallest d^2, in ascending d^2; EQUAL d^2 go to the LOWEST index (the reference's np.argpartition leaves the order of equal
+ *   distances unspecified).  dist = max(sqrtf(d^2), 1e-10f), w = 1 / dist, w_k /= (w0 + w1) + w2, out_flow = (f0 w0 + f1 w1) + f2 w2 per
+ *   component.  A pair with fewer than 4 references gets status bit 0 and its rows of out_flow stay untouched (np.argpartition(kth=3) raises).
+ * dr_coarse_gt_matches_f32: the `get match at coarse level` block.  src [ns, 3] / tgt [nt, 3]: the pairs' coarse source / target clouds, stacked
+ *   each on its own; src_flow [ns, 3] or NULL (4DMatch: p' = p + flow first); rot [P, 3, 3], trn [P, 3]: w = ((r0 x + r1 y) + r2 z) + t per row
+ *   (the reference's matmul may round differently by an ulp where a BLAS fuses; this entry does not imitate that).  Then
+ *   multual_nn_correspondence(w, tgt, radius, knn=1): nearest target j of every source i and nearest source of every target, equal d^2 to the
+ *   lowest index; i is kept when the nearest source of j is i and sqrtf(d^2) < radius.  Pair p's kept (i, j), pair-local, in ascending i, are
+ *   written to out_src / out_tgt [ns] int64 from row s_offsets[p]; counts [P] int32 receives their number.  Rows behind a pair's count are not
+ *   written.  A pair whose source or target cloud has fewer than 2 points gets count 0 and status bit 0 (np.argpartition(kth=1) raises).
+ *   Workspace: dr_coarse_gt_matches_workspace_bytes(ns, nt), 4-byte aligned; DR_EWORKSPACE when missing or smaller.  The size query and the entry
+ *   share one carve function. */
+int dr_blend_flow_knn3_f32(int P, int nq, int nr, const float* query, const int32_t* q_offsets, const float* reference,
+                           const float* reference_flow, const int32_t* r_offsets, float* out_flow, int32_t* status, void* stream);
+size_t dr_coarse_gt_matches_workspace_bytes(int ns, int nt);
+int dr_coarse_gt_matches_f32(int P, int ns, int nt, const float* src, const int32_t* s_offsets, const float* tgt, const int32_t* t_offsets,
+                             const float* src_flow, const float* rot, const float* trn, float radius, int64_t* out_src, int64_t* out_tgt,
+                             int32_t* counts, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

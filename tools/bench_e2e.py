@@ -42,7 +42,7 @@ def stage_times(reps):
     ts = dict(collate=0.0, backbone=0.0, loop=0.0, harness=0.0)
     for _ in range(reps):
         torch.cuda.synchronize(); t0 = time.perf_counter()
-        d = collate_fn_device([(Ad, Bd, rot, trn)], kc, limits)
+        d = collate_fn_device([(Ad, Bd, rot, trn)], kc, limits, training=False)      # the inference half: what this stage has always timed
         torch.cuda.synchronize(); t1 = time.perf_counter()
         feats = bb.forward(d)
         torch.cuda.synchronize(); t2 = time.perf_counter()
