@@ -405,6 +405,32 @@ SIGNATURES.update({
 })
 
 
+class OptimTensor(ctypes.Structure):
+    """dr_optim_tensor"""
+    _fields_ = [("param", c_void_p), ("grad", c_void_p), ("state0", c_void_p), ("state1", c_void_p), ("numel", c_size_t)]
+
+
+class SgdOptions(ctypes.Structure):
+    """dr_sgd_options"""
+    _fields_ = [("lr", c_double), ("weight_decay", c_double), ("momentum", c_double), ("dampening", c_double),
+                ("nesterov", c_int), ("maximize", c_int), ("zero_grads", c_int)]
+
+
+class AdamOptions(ctypes.Structure):
+    """dr_adam_options"""
+    _fields_ = [("lr", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double), ("weight_decay", c_double),
+                ("decoupled", c_int), ("maximize", c_int), ("zero_grads", c_int)]
+
+
+SIGNATURES.update({
+    # added after ABI 0.7.0, twelfth set: the gradient gate and the SGD / Adam update (csrc/optim.hip)
+    "dr_grads_finite_multi_f32": (c_int, [c_void_p, c_size_t, c_void_p, c_void_p]),
+    "dr_sgd_step_multi_f32": (c_int, [c_void_p, c_size_t, ctypes.POINTER(SgdOptions), c_void_p, c_void_p, c_void_p]),
+    "dr_adam_step_multi_f32": (c_int, [c_void_p, c_size_t, ctypes.POINTER(AdamOptions), c_void_p, c_void_p, c_void_p]),
+    "dr_optim_finish": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+})
+
+
 def _bind(table):
     for name, (res, args) in table.items():
         if not hasattr(_lib, name):          # the sets added under one ABI number are detected by symbol

@@ -66,7 +66,10 @@ extern "C" {
  *   0.7.0, tenth set (same rule)  the input transform in front of Depth-Anything: dr_image_cubic_chw_f32 with the new struct dr_image_norm
  *          (new entry only; nothing older changed).
  *   0.7.0, eleventh set (same rule)  the ground-truth half of the 3D / 4D training collate: dr_blend_flow_knn3_f32, dr_coarse_gt_matches_f32 with
- *          dr_coarse_gt_matches_workspace_bytes (new entries only; nothing older changed). */
+ *          dr_coarse_gt_matches_workspace_bytes (new entries only; nothing older changed).
+ *   0.7.0, twelfth set (same rule)  the gradient gate and the optimizer update: dr_grads_finite_multi_f32, dr_sgd_step_multi_f32,
+ *          dr_adam_step_multi_f32, dr_optim_finish with the new structs dr_optim_tensor, dr_sgd_options, dr_adam_options (new entries only;
+ *          nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1439,6 +1442,69 @@ size_t dr_coarse_gt_matches_workspace_bytes(int ns, int nt);
 int dr_coarse_gt_matches_f32(int P, int ns, int nt, const float* src, const int32_t* s_offsets, const float* tgt, const int32_t* t_offsets,
                              const float* src_flow, const float* rot, const float* trn, float radius, int64_t* out_src, int64_t* out_tgt,
                              int32_t* counts, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, twelfth set (detected by symbol like the fourth to eleventh sets): the closing leg of a training iteration -- the
+ * gradient gate and the SGD / Adam / AdamW update.  csrc/optim.hip, indices in csrc/optim_index.h; DESIGN 5v.
+ *
+ * A parameter set is a HOST array of `count` descriptors; every pointer in a descriptor is a DEVICE pointer to contiguous float32 values that
+ * needs only 4-byte alignment, and the pointers of one tensor may sit at different offsets from a 16-byte boundary.  The entries copy the
+ * descriptors by value into the argument blocks of their launches (64 tensors per launch, as many launches as the set needs): the host array
+ * is not read after the call returns.  They are asynchronous on `stream` (a hipStream_t), never synchronise the host, read nothing back,
+ * allocate nothing, use no scratch and no atomic other than the integer OR into the status word: two runs are bit-equal and the sequence
+ * finite -> step (per group) -> finish can be captured on one stream.  A descriptor with numel == 0 is skipped (its pointers are not looked
+ * at); a 0-d tensor is numel == 1.  A NULL or misaligned pointer that a non-empty tensor needs, or an option outside torch's own argument
+ * checks, is DR_EINVAL, reported before the first launch.
+ *
+ * status word: one int32 on the device, owned by the caller, zero before the first sweep.  step counter / skipped counter: one int32 each.
+ *
+ * dr_grads_finite_multi_f32: validate_gradient(model), 3D/lib/utils.py:96-106 (one isnan().any() and one isinf().any() with a host read each,
+ *   per parameter tensor, called at lib/trainer.py:195), and check_gradients, 2D-3D vision3d/engine/base_trainer.py:311-325.  Sweeps `grad`
+ *   of every descriptor (the other pointers are not looked at) and ORs DR_GRAD_NAN / DR_GRAD_POS_INF / DR_GRAD_NEG_INF into *status_word.  The
+ *   word is NOT reset: the sweeps of several parameter groups accumulate into one.
+ * dr_sgd_step_multi_f32: optimizer.step() of torch.optim.SGD (3D/main.py:90-96 builds it; lib/trainer.py:197-199 steps it and zeroes the
+ *   gradients), per element in float32, in the order of torch's single-tensor statement; fma(a, b, c) = a b + c with one rounding, where
+ *   torch's own elementwise kernel for `self + alpha * other` has one, and nothing else fused:
+ *     g = maximize ? -g : g;  if (weight_decay != 0) g = fma(wd, p, g);
+ *     if (momentum != 0) { buf = (*step_counter == 0) ? g : fma(1 - dampening, g, buf momentum);  g = nesterov ? fma(momentum, buf, g) : buf; }
+ *     p = fma(-lr, g, p)
+ *   state0 = momentum_buffer; with momentum == 0 state0 is not looked at and may be NULL.  state1 is not looked at.  The scalars are rounded to
+ *   float32 once, (1 - dampening) in double first, as torch's kernels receive them.
+ * dr_adam_step_multi_f32: optimizer.step() of torch.optim.Adam / AdamW (3D/main.py:97-103; 2D-3D vision3d/utils/optimizer.py:134-141, stepped
+ *   at vision3d/engine/base_trainer.py:253-254); amsgrad is not provided.  state0 = exp_avg, state1 = exp_avg_sq.  With t = *step_counter + 1:
+ *     g = maximize ? -g : g;  if (weight_decay != 0) { decoupled ? p = p (1 - lr wd) : g = fma(wd, p, g); }
+ *     m = lerp(m, g, 1 - beta1) = fma(w, g - m, m) for w < 0.5;  v = fma(1 - beta2, g g, v beta2);
+ *     p = fma(-(lr / (1 - beta1^t)), m / (sqrtf(v) r + eps), p) with r = 1.f / (float)sqrt(1 - beta2^t)
+ *   The bias corrections are computed in the kernel, in double, from the device counter (the host does not know whether a gated step was
+ *   taken) and rounded to float32 where torch rounds them.
+ *   Both updates are gated: when *status_word != 0 no parameter and no state is written.  zero_grads != 0: the same pass writes 0 into every
+ *   gradient (zero_grad(set_to_none=False)), also when gated off, as the reference zeroes them either way.
+ * dr_optim_finish: one workgroup.  *status_word == 0: ++*step_counter; otherwise ++*skipped_counter (may be NULL).  Then *status_word = 0, and
+ *   the new step count is written as float32 into step_mirror[0 .. n_mirror) (torch's per-parameter Adam `step` entries; may be NULL / 0). */
+#define DR_GRAD_NAN 0x1
+#define DR_GRAD_POS_INF 0x2
+#define DR_GRAD_NEG_INF 0x4
+typedef struct dr_optim_tensor {
+    void* param;
+    void* grad;
+    void* state0;
+    void* state1;
+    size_t numel;
+} dr_optim_tensor;
+typedef struct dr_sgd_options {
+    double lr, weight_decay, momentum, dampening;
+    int nesterov, maximize, zero_grads;
+} dr_sgd_options;
+typedef struct dr_adam_options {
+    double lr, beta1, beta2, eps, weight_decay;
+    int decoupled, maximize, zero_grads;
+} dr_adam_options;
+int dr_grads_finite_multi_f32(const dr_optim_tensor* tensors, size_t count, int32_t* status_word, void* stream);
+int dr_sgd_step_multi_f32(const dr_optim_tensor* tensors, size_t count, const dr_sgd_options* options, const int32_t* status_word,
+                          const int32_t* step_counter, void* stream);
+int dr_adam_step_multi_f32(const dr_optim_tensor* tensors, size_t count, const dr_adam_options* options, const int32_t* status_word,
+                           const int32_t* step_counter, void* stream);
+int dr_optim_finish(int32_t* status_word, int32_t* step_counter, int32_t* skipped_counter, float* step_mirror, size_t n_mirror, void* stream);
 
 #ifdef __cplusplus
 }
