@@ -429,6 +429,17 @@ SIGNATURES.update({
     "dr_adam_step_multi_f32": (c_int, [c_void_p, c_size_t, ctypes.POINTER(AdamOptions), c_void_p, c_void_p, c_void_p]),
     "dr_optim_finish": (c_int, [c_void_p, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
 })
+_ITEM_ARGS = [c_int, c_int, c_int, c_void_p, c_double, c_double, c_void_p, c_void_p, c_int, c_void_p, c_double, c_double]
+SIGNATURES.update({
+    # added after ABI 0.7.0, thirteenth set: the pixel-point ground truth of a 2D-3D dataset item (csrc/item2d3d.hip)
+    "dr_corr_2d3d_mutual_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dr_corr_2d3d_mutual_f64": (c_int, _ITEM_ARGS + [ctypes.c_longlong] + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    "dr_corr_2d3d_radius_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dr_corr_2d3d_radius_f64": (c_int, _ITEM_ARGS + [ctypes.c_longlong] + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    "dr_overlap_2d3d_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dr_overlap_2d3d_f64": (c_int, _ITEM_ARGS + [ctypes.c_longlong] * 2 + [c_void_p] * 4 + [c_size_t, c_void_p]),
+    "dr_column_mean_seq_f32": (c_int, [c_int, c_void_p, c_void_p, c_void_p]),
+})
 
 
 def _bind(table):
@@ -2075,6 +2086,78 @@ def coarse_gt_matches(src, s_offsets, tgt, t_offsets, rot, trn, radius, src_flow
                                         float(radius), ptr(out_src) if ns else None, ptr(out_tgt) if ns else None, ptr(counts) if P else None,
                                         ptr(status) if P else None, ptr(ws), wsb, stream_of(src)))
     return out_src, out_tgt, counts, status
+
+
+def _item_inputs(name, depth, points, intrinsics, transform):
+    """the common operands of the thirteenth set on depth's device: depth float32 [H, W], points float32 / float64 [N, 3] (float64 is kept),
+    intrinsics float64 [9], transform float64 [16]"""
+    ensure_init()
+    dev = depth.device
+    depth = depth.to(torch.float32).contiguous()
+    points = points.to(device=dev, dtype=torch.float64 if points.dtype == torch.float64 else torch.float32).contiguous()
+    K = torch.as_tensor(intrinsics).to(device=dev, dtype=torch.float64).contiguous().reshape(-1)
+    T = torch.as_tensor(transform).to(device=dev, dtype=torch.float64).contiguous().reshape(-1)
+    if depth.dim() != 2 or points.dim() != 2 or points.shape[1] != 3 or K.numel() != 9 or T.numel() != 16:
+        raise ValueError("%s: depth [H, W], points [N, 3], intrinsics [3, 3], transform [4, 4]" % name)
+    return depth, points, K, T
+
+
+def _item_call(fn, size_fn, depth, points, K, T, scaling_factor, depth_limit, radius_2d, radius_3d, caps, outs, counts):
+    H, W = depth.shape
+    N = points.shape[0]
+    wsb = size_fn(H, W, N)
+    ws = torch.empty(max(wsb, 32), dtype=torch.uint8, device=depth.device)
+    check(fn(H, W, N, ptr(depth) if H * W else None, float(scaling_factor), float("inf") if depth_limit is None else float(depth_limit), ptr(K),
+             ptr(points) if N else None, 1 if points.dtype == torch.float64 else 0, ptr(T), float(radius_2d), float(radius_3d), *caps,
+             *[ptr(o) if o.numel() else None for o in outs], ptr(counts), ptr(ws), wsb, stream_of(depth)))
+
+
+def corr_2d3d(depth, points, intrinsics, transform, radius_2d, radius_3d, depth_limit=6.0, scaling_factor=1000.0, method="mutual_nearest",
+              cap=None):
+    """-> (img_corr_pixels [cap, 2] int64, pcd_corr_indices [cap] int64, counts [2] int32 = (written, found)), asynchronous:
+    get_2d3d_correspondences_mutual / _radius of vision3d/array_ops/registration_utils.py:30-89 on dr_corr_2d3d_mutual_f64 /
+    dr_corr_2d3d_radius_f64.  cap: rows of the outputs (mutual: min(H W, N) by default, which always suffices; radius: required)."""
+    depth, points, K, T = _item_inputs("corr_2d3d", depth, points, intrinsics, transform)
+    if method not in ("mutual_nearest", "radius"):
+        raise ValueError("corr_2d3d: method is 'mutual_nearest' or 'radius'")
+    mutual = method == "mutual_nearest"
+    if cap is None:
+        if not mutual:
+            raise ValueError("corr_2d3d: the radius variant needs cap (count first with cap=0)")
+        cap = min(depth.numel(), points.shape[0])
+    dev = depth.device
+    pix = torch.empty(cap, 2, dtype=torch.int64, device=dev)
+    idx = torch.empty(cap, dtype=torch.int64, device=dev)
+    counts = torch.empty(2, dtype=torch.int32, device=dev)
+    fn, size_fn = ((_lib.dr_corr_2d3d_mutual_f64, _lib.dr_corr_2d3d_mutual_workspace_bytes) if mutual else
+                   (_lib.dr_corr_2d3d_radius_f64, _lib.dr_corr_2d3d_radius_workspace_bytes))
+    _item_call(fn, size_fn, depth, points, K, T, scaling_factor, depth_limit, radius_2d, radius_3d, [int(cap)], [pix, idx], counts)
+    return pix, idx, counts
+
+
+def overlap_2d3d(depth, points, intrinsics, transform, radius_2d, radius_3d, depth_limit=6.0, scaling_factor=1000.0):
+    """-> (img_overlap_indices [H W] int64, pcd_overlap_indices [N] int64, counts [4] int32 = (written, found) of either), asynchronous: the
+    sorted distinct pixel indices h W + w and point indices of the radius variant's pairs (sevenscenes_hard.py:184-196) on dr_overlap_2d3d_f64;
+    the first counts[1] / counts[3] rows are the lists."""
+    depth, points, K, T = _item_inputs("overlap_2d3d", depth, points, intrinsics, transform)
+    dev = depth.device
+    img = torch.empty(depth.numel(), dtype=torch.int64, device=dev)
+    pcd = torch.empty(points.shape[0], dtype=torch.int64, device=dev)
+    counts = torch.empty(4, dtype=torch.int32, device=dev)
+    _item_call(_lib.dr_overlap_2d3d_f64, _lib.dr_overlap_2d3d_workspace_bytes, depth, points, K, T, scaling_factor, depth_limit, radius_2d,
+               radius_3d, [img.numel(), pcd.numel()], [img, pcd], counts)
+    return img, pcd, counts
+
+
+def column_mean_seq(x):
+    """-> [3] float32: x.mean(axis=0) of a float32 [n, 3] array in numpy's order of additions (row after row), asynchronous"""
+    ensure_init()
+    x = x.to(torch.float32).contiguous()
+    if x.dim() != 2 or x.shape[1] != 3 or x.shape[0] < 1:
+        raise ValueError("column_mean_seq: x [n, 3] with n >= 1")
+    out = torch.empty(3, dtype=torch.float32, device=x.device)
+    check(_lib.dr_column_mean_seq_f32(x.shape[0], ptr(x), ptr(out), stream_of(x)))
+    return out
 
 
 def batch_mutual_topk_select(score_mat, k, row_masks=None, col_masks=None, largest=True, threshold=None, mutual=True):

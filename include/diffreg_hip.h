@@ -69,7 +69,9 @@ extern "C" {
  *          dr_coarse_gt_matches_workspace_bytes (new entries only; nothing older changed).
  *   0.7.0, twelfth set (same rule)  the gradient gate and the optimizer update: dr_grads_finite_multi_f32, dr_sgd_step_multi_f32,
  *          dr_adam_step_multi_f32, dr_optim_finish with the new structs dr_optim_tensor, dr_sgd_options, dr_adam_options (new entries only;
- *          nothing older changed). */
+ *          nothing older changed).
+ *   0.7.0, thirteenth set (same rule)  the pixel-point ground truth of a 2D-3D dataset item: dr_corr_2d3d_mutual_f64, dr_corr_2d3d_radius_f64,
+ *          dr_overlap_2d3d_f64 with their workspace size queries, dr_column_mean_seq_f32 (new entries only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1505,6 +1507,56 @@ int dr_sgd_step_multi_f32(const dr_optim_tensor* tensors, size_t count, const dr
 int dr_adam_step_multi_f32(const dr_optim_tensor* tensors, size_t count, const dr_adam_options* options, const int32_t* status_word,
                            const int32_t* step_counter, void* stream);
 int dr_optim_finish(int32_t* status_word, int32_t* step_counter, int32_t* skipped_counter, float* step_mirror, size_t n_mirror, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, thirteenth set (detected by symbol like the fourth to twelfth sets): the pixel-point ground truth of a 2D-3D dataset
+ * item, which the reference builds per item on a loader worker with two cKDTrees: get_2d3d_correspondences_mutual / _radius, 2D-3D
+ * vision3d/array_ops/registration_utils.py:30-60, 63-89, with back_project and render (array_ops/depth_image.py:9-65, 68-99), apply_transform
+ * (array_ops/se3.py:7-17) and mutual_select (array_ops/mutual_select.py:7-35); the np.unique lists of return_overlap_indices
+ * (datasets/registration/sevenscenes/sevenscenes_hard.py:184-196).  csrc/item2d3d.hip, indices in csrc/item2d3d_index.h; DESIGN 5w.
+ *
+ * Common to the three entries.  depth [H, W] float32 in raw units; intrinsics [9] and transform [16] float64 row-major, DEVICE pointers; points
+ * [N, 3] float32 (points_f64 == 0) or float64.  All arithmetic is float64 and unfused.  Image point of pixel (h, w): z = depth / scaling_factor,
+ * z > depth_limit -> 0 (pass +inf for the reference's depth_limit=None), kept when z > 0; x = (w - cx) z / fx; y = (v - cy) z / fy with
+ * v = (h W + w) / W, back_project's TRUE division -- v keeps the fraction w / W.  The reference's image-point index is the rank of the pixel
+ * among the kept ones in row-major order; the entries return pixels, so they order by h W + w, which is the same order.  Cloud point:
+ * q = ((x r0 + y r1) + z r2) + t per row of transform (apply_transform; a BLAS may round the reference's matmul differently by an ulp, which
+ * this entry does not imitate).  d^2 = ((dx dx + dy dy) + dz dz), 3D test sqrt(d^2) < radius_3d.  render(q) = (trunc(fy qy / qz + cy),
+ * trunc(fx qx / qz + cx)): array_ops.render TRUNCATES with .astype(int), unlike the vision3d.ops version dr_render_f32 restates.  2D test:
+ * sqrt(dh dh + dw dw) < radius_2d between the integer pixel and render(q); a render value that is not finite or reaches 2^30 passes no 2D test
+ * (numpy's cast is undefined there).
+ * The entries are asynchronous on `stream`, read nothing back, allocate nothing and use no atomics: two runs are bit-equal.  counts [2] int32
+ * receives (rows written = min(found, cap), rows found, saturated at 2^31 - 1); found > cap is never a silent cut: the caller reads counts.
+ * Rows behind counts[0] are not written.  H W <= 2^30 and N <= 2^28, else DR_ENOSUP.  Workspace: the entry's size query, 32-byte aligned;
+ * DR_EWORKSPACE when missing or smaller.  The three size queries share one carve function with the entries.
+ *
+ * dr_corr_2d3d_mutual_f64: pairs (pixel i, point j) with j the nearest cloud point of i, i the nearest image point of j, and both tests
+ *   passed; EQUAL d^2 go to the LOWEST index on either side (the reference's cKDTree leaves ties unspecified).  Ascending i (mutual_select's
+ *   order).  img_corr_pixels [cap, 2] int64 (h, w), pcd_corr_indices [cap] int64; cap = min(H W, N) always suffices.  Only pairs closer than
+ *   radius_3d survive, so a point's nearest pixel is searched inside the pixel window its radius_3d ball projects to (the whole image when
+ *   qz <= radius_3d, no pixel when qz <= -radius_3d), and the reverse check runs for those at most N pixels against the whole cloud.
+ * dr_corr_2d3d_radius_f64: all pairs that pass both tests, in ascending (i, j) (the reference's inner order is its KD-tree's).
+ * dr_overlap_2d3d_f64: np.unique of the radius variant's pixel indices h W + w and of its point indices, without building the pair list:
+ *   img_overlap_indices [cap_img] int64, pcd_overlap_indices [cap_pcd] int64, both ascending; counts [4] = (written, found) of either.
+ * dr_column_mean_seq_f32: out [3] = x.mean(axis=0) of a float32 [n, 3] array as numpy performs it (sevenscenes_hard.py:140, the centre of the
+ *   augmentation): the rows are added one after the other in float32 -- numpy's pairwise blocks apply to the inner axis only -- and the sum is
+ *   divided by (float)n.  A parallel sum rounds differently, and the difference would show in the item's float32 transform.  n >= 1. */
+int dr_column_mean_seq_f32(int n, const float* x, float* out, void* stream);
+size_t dr_corr_2d3d_mutual_workspace_bytes(int H, int W, int N);
+int dr_corr_2d3d_mutual_f64(int H, int W, int N, const float* depth, double scaling_factor, double depth_limit, const double* intrinsics,
+                            const void* points, int points_f64, const double* transform, double radius_2d, double radius_3d, long long cap,
+                            int64_t* img_corr_pixels, int64_t* pcd_corr_indices, int32_t* counts, void* workspace, size_t workspace_bytes,
+                            void* stream);
+size_t dr_corr_2d3d_radius_workspace_bytes(int H, int W, int N);
+int dr_corr_2d3d_radius_f64(int H, int W, int N, const float* depth, double scaling_factor, double depth_limit, const double* intrinsics,
+                            const void* points, int points_f64, const double* transform, double radius_2d, double radius_3d, long long cap,
+                            int64_t* img_corr_pixels, int64_t* pcd_corr_indices, int32_t* counts, void* workspace, size_t workspace_bytes,
+                            void* stream);
+size_t dr_overlap_2d3d_workspace_bytes(int H, int W, int N);
+int dr_overlap_2d3d_f64(int H, int W, int N, const float* depth, double scaling_factor, double depth_limit, const double* intrinsics,
+                        const void* points, int points_f64, const double* transform, double radius_2d, double radius_3d, long long cap_img,
+                        long long cap_pcd, int64_t* img_overlap_indices, int64_t* pcd_overlap_indices, int32_t* counts, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
