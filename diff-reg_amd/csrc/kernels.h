@@ -50,6 +50,7 @@ struct GemmBatch {
 int launch_gemm(const GemmBatch& g, hipStream_t st);
 int gemm_configure();
 int vit_f32_configure();      // vit_f32.hip: the dynamic LDS of the float32 rows GEMM's tiles
+int nonrigid_configure();     // nonrigid.hip: the dynamic LDS of the non-rigid ICP solver up to its node capacity
 void gemm_force_config(int c);
 
 // ---------------------------------------------------------------------------------------------

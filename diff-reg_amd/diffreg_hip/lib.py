@@ -442,6 +442,41 @@ SIGNATURES.update({
 })
 
 
+class NicpProblem(ctypes.Structure):
+    """dr_nicp_problem"""
+    _fields_ = [("P", c_int), ("n_corr", c_int), ("n_nodes", c_int), ("n_edges", c_int), ("K", c_int), ("max_nodes", c_int),
+                ("nodes", c_void_p), ("m_offsets", c_void_p), ("src_corr", c_void_p), ("tgt_corr", c_void_p), ("c_offsets", c_void_p),
+                ("anchor_indices", c_void_p), ("anchor_weights", c_void_p), ("edges", c_void_p), ("edge_weights", c_void_p),
+                ("e_offsets", c_void_p)]
+
+
+class NicpOptions(ctypes.Structure):
+    """dr_nicp_options"""
+    _fields_ = [("num_iterations", c_int), ("lr", c_double), ("gamma", c_double), ("beta1", c_double), ("beta2", c_double), ("eps", c_double),
+                ("w_landmark", c_double), ("w_arap", c_double), ("w_ortho", c_double)]
+
+
+class NicpState(ctypes.Structure):
+    """dr_nicp_state"""
+    _fields_ = [("rotations", c_void_p), ("translations", c_void_p), ("exp_avg_rot", c_void_p), ("exp_avg_trn", c_void_p),
+                ("exp_avg_sq_rot", c_void_p), ("exp_avg_sq_trn", c_void_p), ("step", c_void_p)]
+
+
+SIGNATURES.update({
+    # added after ABI 0.7.0, fourteenth set: non-rigid ICP on an embedded deformation graph (csrc/nonrigid.hip)
+    "dr_nicp_node_capacity": (c_int, []),
+    "dr_ed_graph_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dr_ed_graph_f32": (c_int, [c_int] * 5 + [c_void_p] * 4 + [c_double, c_double] + [c_void_p] * 5 + [ctypes.c_longlong] + [c_void_p] * 5
+                        + [c_size_t, c_void_p]),
+    "dr_ed_warp_f32": (c_int, [c_int] * 4 + [c_void_p] * 7 + [c_double] + [c_void_p] * 3),
+    "dr_nicp_workspace_bytes": (c_size_t, [c_int] * 5),
+    "dr_nicp_cost_grad_f32": (c_int, [ctypes.POINTER(NicpProblem), c_void_p, c_void_p, c_double, c_double, c_double] + [c_void_p] * 5
+                              + [c_size_t, c_void_p]),
+    "dr_nicp_adam_f32": (c_int, [ctypes.POINTER(NicpProblem), ctypes.POINTER(NicpOptions), ctypes.POINTER(NicpState), c_int] + [c_void_p] * 5
+                         + [c_size_t, c_void_p]),
+})
+
+
 def _bind(table):
     for name, (res, args) in table.items():
         if not hasattr(_lib, name):          # the sets added under one ABI number are detected by symbol

@@ -1,0 +1,363 @@
+"""Non-rigid ICP on an embedded deformation graph (fourteenth set after ABI 0.7.0, csrc/nonrigid.hip): the step from a 4DMatch match
+list to a deformation field.
+
+build_euclidean_deformation_graph, apply_deformation and non_rigid_icp_adam keep the names, argument order, defaults and return tuples of
+vision3d/ops/deformation_graph.py:26-103, embedded_deformation.py:31-66 and nonrigid_icp_adam.py:76-131; ed_graph, ed_warp, nicp_cost_grad and
+nicp_adam are the ragged entries underneath (P pairs per call through offset vectors); NonRigidRegistration chains them behind Pipeline.
+
+Refusals are raised at call time, before any launch: inputs that are not float32, index tensors that are not contiguous int64, a pair with more
+nodes than node_capacity().  One exception: when NonRigidRegistration subsamples the nodes itself, their number is known only after that launch,
+so the capacity is checked behind it, before the graph and the solver are launched.  There is no CPU path and no path above the capacity.
+The ragged entries return the device status vector (the bits are listed in include/diffreg_hip.h); the three vision3d names, whose return tuples
+have no place for it, discard it, and NonRigidRegistration hands it out as graph["status"]."""
+import ctypes
+
+import torch
+
+from . import lib
+from .lib import NicpOptions, NicpProblem, NicpState, check, ptr, stream_of
+
+MAX_ANCHORS = 8
+_raw = lib.raw()
+
+
+def node_capacity():
+    """the largest node count of one pair the solver accepts (its state lives in the LDS of one compute unit)"""
+    return int(_raw.dr_nicp_node_capacity())
+
+
+def _f32(name, t, shape_tail):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+        raise TypeError("%s must be a float32 tensor (got %s)" % (name, getattr(t, "dtype", type(t))))
+    if tuple(t.shape[1:]) != tuple(shape_tail):
+        raise ValueError("%s must be [n%s] (got %s)" % (name, "".join(", %d" % s for s in shape_tail), tuple(t.shape)))
+    return t.contiguous()
+
+
+def _i64(name, t, cols):
+    if not isinstance(t, torch.Tensor) or t.dtype != torch.int64:
+        raise TypeError("%s must be an int64 tensor (got %s)" % (name, getattr(t, "dtype", type(t))))
+    if t.dim() != 2 or t.shape[1] != cols:
+        raise ValueError("%s must be [n, %d] (got %s)" % (name, cols, tuple(t.shape)))
+    if not t.is_contiguous():
+        raise ValueError("%s must be contiguous" % name)
+    return t
+
+
+def _check_k(K):
+    if not 1 <= int(K) <= MAX_ANCHORS:
+        raise ValueError("num_anchors must be in 1 .. %d (got %s)" % (MAX_ANCHORS, K))
+    return int(K)
+
+
+def _offsets(lengths, dev):
+    """host lengths -> (int32 device vector of P + 1 offsets, total); no device read"""
+    o = [0]
+    for n in lengths:
+        o.append(o[-1] + int(n))
+    return torch.tensor(o, dtype=torch.int32, device=dev), o[-1]
+
+
+def _lengths_of(offsets_or_lengths, total):
+    """None -> one pair of `total` rows; a list / tuple of host ints -> lengths"""
+    if offsets_or_lengths is None:
+        return [int(total)]
+    lens = [int(n) for n in offsets_or_lengths]
+    if sum(lens) != total or min(lens, default=0) < 0:
+        raise ValueError("lengths %s do not add up to %d rows" % (lens, total))
+    return lens
+
+
+def _ws(nbytes, dev):
+    return torch.empty(max(int(nbytes), 16), dtype=torch.uint8, device=dev)
+
+
+# ------------------------------------------------------------------------------------------------ ragged entries
+def ed_graph(points, nodes, num_anchors, node_coverage, point_lengths=None, node_lengths=None, eps=1e-6, return_distance=False):
+    """dr_ed_graph_f32 for P pairs: points [n, 3] / nodes [m, 3] stacked, *_lengths host lists (None: one pair).  -> dict(anchor_indices [n, K]
+    int64 pair-local (-1 from column min(K, M) on), anchor_weights, anchor_distances?, edge_indices [E, 2] int64 pair-local, edge_weights,
+    edge_distances?, edge_lengths (host list), status [P]).  Reads the P edge counts back once, between the count pass and the write pass."""
+    points, nodes = _f32("points", points, (3,)), _f32("nodes", nodes, (3,))
+    K = _check_k(num_anchors)
+    if not float(node_coverage) > 0:
+        raise ValueError("node_coverage must be positive")
+    pl, ml = _lengths_of(point_lengths, points.shape[0]), _lengths_of(node_lengths, nodes.shape[0])
+    if len(pl) != len(ml):
+        raise ValueError("point_lengths and node_lengths must describe the same pairs")
+    lib.ensure_init()
+    dev, P, n, m = points.device, len(pl), points.shape[0], nodes.shape[0]
+    po, _ = _offsets(pl, dev)
+    mo, _ = _offsets(ml, dev)
+    ai = torch.full((n, K), -1, dtype=torch.int64, device=dev)      # a pair the device refuses (status 1 or 2) keeps -1 / 0 rows
+    aw = torch.zeros(n, K, device=dev)
+    ad = torch.zeros(n, K, device=dev) if return_distance else None
+    counts = torch.empty(P, dtype=torch.int32, device=dev)
+    status = torch.empty(P, dtype=torch.int32, device=dev)
+    mx = max(ml, default=0)
+    wsb = _raw.dr_ed_graph_workspace_bytes(m, mx)
+    ws = _ws(wsb, dev)
+    st = stream_of(points)
+    common = (P, n, m, mx, K, ptr(points) if n else None, ptr(po), ptr(nodes) if m else None, ptr(mo), float(node_coverage), float(eps))
+    check(_raw.dr_ed_graph_f32(*common, ptr(ai) if n else None, ptr(aw) if n else None, ptr(ad) if (n and return_distance) else None, ptr(counts),
+                               None, 0, None, None, None, ptr(status), ptr(ws), wsb, st))
+    el = [int(c) for c in counts.tolist()]                  # the one host read of the batch
+    eo, E = _offsets(el, dev)
+    ei = torch.empty(E, 2, dtype=torch.int64, device=dev)
+    ew = torch.empty(E, device=dev)
+    edist = torch.empty(E, device=dev) if return_distance else None
+    check(_raw.dr_ed_graph_f32(*common, None, None, None, None, ptr(eo), E, ptr(ei) if E else None, ptr(ew) if E else None,
+                               ptr(edist) if (E and return_distance) else None, ptr(status), ptr(ws), wsb, st))
+    out = dict(anchor_indices=ai, anchor_weights=aw, edge_indices=ei, edge_weights=ew, edge_lengths=el, status=status)
+    if return_distance:
+        out["anchor_distances"], out["edge_distances"] = ad, edist
+    return out
+
+
+def ed_warp(points, nodes, transforms, anchor_indices, anchor_weights, point_lengths=None, node_lengths=None, eps=1e-6):
+    """dr_ed_warp_f32 for P pairs -> (warped [n, 3], status [P])"""
+    points, nodes = _f32("points", points, (3,)), _f32("nodes", nodes, (3,))
+    transforms = _f32("transforms", transforms, (4, 4))
+    if anchor_indices.dim() != 2:
+        raise ValueError("anchor_indices must be [n, K]")
+    K = _check_k(anchor_indices.shape[1])
+    ai = _i64("anchor_indices", anchor_indices, K)
+    aw = _f32("anchor_weights", anchor_weights, (K,))
+    n, m = points.shape[0], nodes.shape[0]
+    if ai.shape[0] != n or aw.shape[0] != n or transforms.shape[0] != m:
+        raise ValueError("anchor_indices / anchor_weights need one row per point, transforms one per node")
+    pl, ml = _lengths_of(point_lengths, n), _lengths_of(node_lengths, m)
+    if len(pl) != len(ml):
+        raise ValueError("point_lengths and node_lengths must describe the same pairs")
+    lib.ensure_init()
+    dev, P = points.device, len(pl)
+    po, _ = _offsets(pl, dev)
+    mo, _ = _offsets(ml, dev)
+    out = torch.empty(n, 3, device=dev)
+    status = torch.empty(P, dtype=torch.int32, device=dev)
+    check(_raw.dr_ed_warp_f32(P, n, m, K, ptr(points) if n else None, ptr(po), ptr(nodes) if m else None, ptr(mo), ptr(transforms) if m else None,
+                              ptr(ai) if n else None, ptr(aw) if n else None, float(eps), ptr(out) if n else None, ptr(status), stream_of(points)))
+    return out, status
+
+
+class Problem:
+    """the inputs of the solver entries for P pairs, validated once: stacked tensors, host lengths, device offsets, the dr_nicp_problem struct"""
+
+    def __init__(self, src_nodes, src_corr_points, tgt_corr_points, anchor_indices, anchor_weights, node_edges, node_edge_weights,
+                 node_lengths=None, corr_lengths=None, edge_lengths=None):
+        self.nodes = _f32("src_nodes", src_nodes, (3,))
+        self.src = _f32("src_corr_points", src_corr_points, (3,))
+        self.tgt = _f32("tgt_corr_points", tgt_corr_points, (3,))
+        if anchor_indices.dim() != 2:
+            raise ValueError("anchor_indices must be [n, K]")
+        self.K = _check_k(anchor_indices.shape[1])
+        self.ai = _i64("anchor_indices", anchor_indices, self.K)
+        self.aw = _f32("anchor_weights", anchor_weights, (self.K,))
+        self.edges = _i64("node_edges", node_edges, 2)
+        self.ew = _f32("node_edge_weights", node_edge_weights, ())
+        self.m, self.n, self.e = self.nodes.shape[0], self.src.shape[0], self.edges.shape[0]
+        if self.tgt.shape[0] != self.n or self.ai.shape[0] != self.n or self.aw.shape[0] != self.n or self.ew.shape[0] != self.e:
+            raise ValueError("correspondence tensors need one row per correspondence, edge weights one per edge")
+        self.ml, self.cl, self.el = _lengths_of(node_lengths, self.m), _lengths_of(corr_lengths, self.n), _lengths_of(edge_lengths, self.e)
+        if not len(self.ml) == len(self.cl) == len(self.el):
+            raise ValueError("node_lengths, corr_lengths and edge_lengths must describe the same pairs")
+        self.P = len(self.ml)
+        self.max_nodes = max(self.ml, default=0)
+        if self.max_nodes > node_capacity():
+            raise ValueError("a pair has %d nodes; the solver holds at most %d (its state lives in one compute unit's LDS)"
+                             % (self.max_nodes, node_capacity()))
+        self.dev = self.nodes.device
+        for t in (self.src, self.tgt, self.ai, self.aw, self.edges, self.ew):
+            if t.device != self.dev:
+                raise ValueError("all tensors must be on one device")
+
+    def struct(self):
+        """built at the first call and kept: the offset vectors are uploaded once, so a later call can be captured in a graph"""
+        if getattr(self, "_struct", None) is None:
+            self._struct = self._build()
+        return self._struct
+
+    def _build(self):
+        dev = self.dev
+        self.mo, _ = _offsets(self.ml, dev)
+        self.co, _ = _offsets(self.cl, dev)
+        self.eo, _ = _offsets(self.el, dev)
+        v = lambda t, n: ptr(t).value if n else None
+        return NicpProblem(self.P, self.n, self.m, self.e, self.K, self.max_nodes, v(self.nodes, self.m), ptr(self.mo).value, v(self.src, self.n),
+                           v(self.tgt, self.n), ptr(self.co).value, v(self.ai, self.n), v(self.aw, self.n), v(self.edges, self.e),
+                           v(self.ew, self.e), ptr(self.eo).value)
+
+    def workspace(self):
+        wsb = _raw.dr_nicp_workspace_bytes(self.P, self.n, self.m, self.e, self.K)
+        return _ws(wsb, self.dev), wsb
+
+
+def nicp_cost_grad(problem, rotations, translations, weights=(1.0, 0.1, 0.1)):
+    """dr_nicp_cost_grad_f32 -> (cost [P, 3], grad_rot [m, 3, 3], grad_trn [m, 3], status [P])"""
+    rot, trn = _f32("rotations", rotations, (3, 3)), _f32("translations", translations, (3,))
+    if rot.shape[0] != problem.m or trn.shape[0] != problem.m:
+        raise ValueError("rotations / translations need one row per node")
+    lib.ensure_init()
+    dev = problem.dev
+    pb = problem.struct()
+    cost = torch.empty(problem.P, 3, device=dev)
+    g_r, g_t = torch.empty_like(rot), torch.empty_like(trn)
+    status = torch.empty(problem.P, dtype=torch.int32, device=dev)
+    ws, wsb = problem.workspace()
+    m = problem.m
+    check(_raw.dr_nicp_cost_grad_f32(ctypes.byref(pb), ptr(rot) if m else None, ptr(trn) if m else None, float(weights[0]), float(weights[1]),
+                                     float(weights[2]), ptr(cost), ptr(g_r) if m else None, ptr(g_t) if m else None, ptr(status), ptr(ws), wsb,
+                                     stream_of(problem.nodes)))
+    return cost, g_r, g_t, status
+
+
+STATE_NAMES = ("rotations", "translations", "exp_avg_rot", "exp_avg_trn", "exp_avg_sq_rot", "exp_avg_sq_trn", "step")
+
+
+def new_state(problem):
+    """an Adam state to run from and to resume: identity rotations, zero translations and moments, step 0"""
+    dev, m = problem.dev, problem.m
+    z = lambda *s: torch.zeros(*s, device=dev)
+    return dict(rotations=torch.eye(3, device=dev).repeat(m, 1, 1), translations=z(m, 3), exp_avg_rot=z(m, 3, 3), exp_avg_trn=z(m, 3),
+                exp_avg_sq_rot=z(m, 3, 3), exp_avg_sq_trn=z(m, 3), step=torch.zeros(problem.P, dtype=torch.int32, device=dev))
+
+
+def nicp_adam(problem, num_iterations=500, lr=0.5, gamma=0.999, beta1=0.9, beta2=0.999, eps=1e-8, weights=(1.0, 0.1, 0.1), state=None,
+              resume=False, trace=False, out=None):
+    """dr_nicp_adam_f32 -> (transforms [m, 4, 4], cost [P, 3], trace [P, num_iterations, 3] or None, status [P]).  state: a dict of STATE_NAMES
+    (new_state()); it receives the final state, and with resume=True the run starts from it.  out: (transforms, cost, trace, status, workspace) of
+    an earlier call to write into, so that a captured graph allocates nothing."""
+    if int(num_iterations) < 0:
+        raise ValueError("num_iterations must not be negative")
+    if resume and state is None:
+        raise ValueError("resume needs a state")
+    lib.ensure_init()
+    dev, m, P = problem.dev, problem.m, problem.P
+    st = NicpState()
+    if state is not None:
+        for k in STATE_NAMES:
+            t = state.get(k)
+            if t is None:
+                continue
+            want = torch.int32 if k == "step" else torch.float32
+            if t.dtype != want or not t.is_contiguous() or t.device != dev or t.numel() != (P if k == "step" else m * (9 if k.endswith("rot") or
+                                                                                                                     k == "rotations" else 3)):
+                raise ValueError("state[%r] must be a contiguous %s tensor of the problem's size on its device" % (k, want))
+            setattr(st, k, ptr(t).value if t.numel() else None)
+    pb = problem.struct()
+    op = NicpOptions(int(num_iterations), float(lr), float(gamma), float(beta1), float(beta2), float(eps), float(weights[0]), float(weights[1]),
+                     float(weights[2]))
+    if out is None:
+        ws, wsb = problem.workspace()
+        out = (torch.empty(m, 4, 4, device=dev), torch.empty(P, 3, device=dev),
+               torch.empty(P, int(num_iterations), 3, device=dev) if trace else None, torch.empty(P, dtype=torch.int32, device=dev), ws)
+    T, cost, tr, status, ws = out
+    wsb = _raw.dr_nicp_workspace_bytes(problem.P, problem.n, problem.m, problem.e, problem.K)
+    check(_raw.dr_nicp_adam_f32(ctypes.byref(pb), ctypes.byref(op), ctypes.byref(st), 1 if resume else 0, ptr(T) if m else None, ptr(cost),
+                                ptr(tr) if (tr is not None and tr.numel()) else None, ptr(status), ptr(ws), wsb, stream_of(problem.nodes)))
+    problem.last_out = out
+    return T, cost, tr, status
+
+
+# ------------------------------------------------------------------------------------------------ vision3d's three names
+def build_euclidean_deformation_graph(points, nodes, num_anchors, node_coverage, return_point_anchor=True, return_node_graph=True,
+                                      return_distance=False, return_adjacent_matrix=False, eps=1e-6):
+    """vision3d/ops/deformation_graph.py:26-103 for one pair; the anchor tensors have min(num_anchors, M) columns, as the reference's.  The
+    reference's tuple has no place for the device status word, so it is DISCARDED here (ed_graph returns it): with points but no nodes the anchors
+    are -1 / weight 0, and a NaN / Inf coordinate leaves -1 columns where the reference returns NaN weights."""
+    if return_adjacent_matrix:
+        raise NotImplementedError("return_adjacent_matrix=True: the device builds the edge list, not the dense matrices")
+    g = ed_graph(points, nodes, num_anchors, node_coverage, eps=eps, return_distance=return_distance)
+    ke = min(int(num_anchors), nodes.shape[0])
+    cut = (lambda t: t[:, :ke].contiguous()) if ke < int(num_anchors) else (lambda t: t)
+    out = []
+    if return_point_anchor:
+        out += [cut(g["anchor_indices"]), cut(g["anchor_weights"])]
+        if return_distance:
+            out.append(cut(g["anchor_distances"]))
+    if return_node_graph:
+        out += [g["edge_indices"], g["edge_weights"]]
+        if return_distance:
+            out.append(g["edge_distances"])
+    return tuple(out)
+
+
+def apply_deformation(points, nodes, transforms, anchor_indices, anchor_weights, eps=1e-6):
+    """vision3d/ops/embedded_deformation.py:31-66 for one pair; the status word is discarded (ed_warp returns it): an anchor outside [-1, M) is
+    treated as absent where the reference raises an IndexError"""
+    return ed_warp(points, nodes, transforms, anchor_indices, anchor_weights, eps=eps)[0]
+
+
+def non_rigid_icp_adam(src_nodes, src_corr_points, tgt_corr_points, anchor_indices, anchor_weights, node_edges, node_edge_weights,
+                       num_iterations=500):
+    """vision3d/ops/nonrigid_icp_adam.py:76-131 for one pair -> transforms [M, 4, 4]; the status word is discarded (nicp_adam returns it)"""
+    pb = Problem(src_nodes, src_corr_points, tgt_corr_points, anchor_indices, anchor_weights, node_edges, node_edge_weights)
+    return nicp_adam(pb, num_iterations=num_iterations)[0]
+
+
+# ------------------------------------------------------------------------------------------------ after Pipeline on a 4DMatch pair
+class NonRigidRegistration:
+    """graph -> solver -> warp of the whole source cloud, for one pair or a list of pairs in one call.
+
+    __call__(src_points, tgt_points, matches, nodes=None): src_points [n, 3] / tgt_points [n', 3] float32, matches [k, 2] int64 (source row,
+    target row) as Pipeline returns them per pair -- or lists of those, one entry per pair.  nodes: given per pair, or grid-subsampled from the
+    source cloud with cell = node_coverage (dr_grid_subsample_f32).  -> (warped_src, transforms, graph) per pair (lists for a list).
+    graph["status"] is the pair's device status word (a 0-d int32 DEVICE tensor, not read here: 0, or the bits include/diffreg_hip.h lists --
+    8: a non-finite coordinate left points without their full anchors; 4: an index out of range was treated as absent)."""
+
+    def __init__(self, num_anchors=6, node_coverage=0.08, num_iterations=500, lr=0.5, gamma=0.999, weights=(1.0, 0.1, 0.1), eps=1e-6):
+        self.num_anchors, self.node_coverage, self.num_iterations = _check_k(num_anchors), float(node_coverage), int(num_iterations)
+        self.lr, self.gamma, self.weights, self.eps = float(lr), float(gamma), tuple(weights), float(eps)
+
+    def subsample_nodes(self, src_list):
+        """per-pair node sets: one grid-subsample call over the stacked clouds, one host read of the P lengths"""
+        dev = src_list[0].device
+        lengths = torch.tensor([s.shape[0] for s in src_list], dtype=torch.int32, device=dev)
+        pts, sub_len, _, _ = lib.grid_subsample(torch.cat(src_list), lengths, self.node_coverage)
+        out, lo = [], 0
+        for n in sub_len.tolist():
+            out.append(pts[lo:lo + n].contiguous())
+            lo += n
+        return out
+
+    def __call__(self, src_points, tgt_points, matches, nodes=None):
+        single = isinstance(src_points, torch.Tensor)
+        src_l = [src_points] if single else list(src_points)
+        tgt_l = [tgt_points] if single else list(tgt_points)
+        mat_l = [matches] if single else list(matches)
+        nod_l = None if nodes is None else ([nodes] if single else list(nodes))
+        if not len(src_l) == len(tgt_l) == len(mat_l) or (nod_l is not None and len(nod_l) != len(src_l)):
+            raise ValueError("one source cloud, target cloud, match list (and node set) per pair")
+        src_l = [_f32("src_points", s, (3,)) for s in src_l]
+        tgt_l = [_f32("tgt_points", t, (3,)) for t in tgt_l]
+        mat_l = [_i64("matches", m, 2) for m in mat_l]
+        if nod_l is not None:
+            nod_l = [_f32("nodes", g, (3,)) for g in nod_l]
+            if max(g.shape[0] for g in nod_l) > node_capacity():
+                raise ValueError("a pair has %d nodes; the solver holds at most %d" % (max(g.shape[0] for g in nod_l), node_capacity()))
+        else:
+            nod_l = self.subsample_nodes(src_l)      # a launch: only now is the node count known, so the capacity is checked here,
+            if max(g.shape[0] for g in nod_l) > node_capacity():                     # before the graph and the solver are launched
+                raise ValueError("the grid subsample gave a pair %d nodes; the solver holds at most %d: raise node_coverage or pass nodes"
+                                 % (max(g.shape[0] for g in nod_l), node_capacity()))
+        pl, ml, cl = [s.shape[0] for s in src_l], [g.shape[0] for g in nod_l], [m.shape[0] for m in mat_l]
+        src, nod = torch.cat(src_l), torch.cat(nod_l)
+        g = ed_graph(src, nod, self.num_anchors, self.node_coverage, point_lengths=pl, node_lengths=ml, eps=self.eps)
+        rows, lo = [], 0
+        for s, m in zip(src_l, mat_l):                      # the correspondences' rows of the stacked source cloud
+            rows.append(m[:, 0] + lo)
+            lo += s.shape[0]
+        rows = torch.cat(rows)
+        src_corr = src[rows]
+        tgt_corr = torch.cat([t[m[:, 1]] for t, m in zip(tgt_l, mat_l)])
+        pb = Problem(nod, src_corr, tgt_corr, g["anchor_indices"][rows].contiguous(), g["anchor_weights"][rows].contiguous(), g["edge_indices"],
+                     g["edge_weights"], node_lengths=ml, corr_lengths=cl, edge_lengths=g["edge_lengths"])
+        T, _, _, st_solver = nicp_adam(pb, num_iterations=self.num_iterations, lr=self.lr, gamma=self.gamma, weights=self.weights)
+        warped, st_warp = ed_warp(src, nod, T, g["anchor_indices"], g["anchor_weights"], point_lengths=pl, node_lengths=ml, eps=self.eps)
+        res, p0, m0, e0 = [], 0, 0, 0
+        for p, m, e in zip(pl, ml, g["edge_lengths"]):
+            graph = dict(nodes=nod[m0:m0 + m], anchor_indices=g["anchor_indices"][p0:p0 + p], anchor_weights=g["anchor_weights"][p0:p0 + p],
+                         edge_indices=g["edge_indices"][e0:e0 + e], edge_weights=g["edge_weights"][e0:e0 + e],
+                         status=(g["status"] | st_solver | st_warp)[len(res)])
+            res.append((warped[p0:p0 + p], T[m0:m0 + m], graph))
+            p0, m0, e0 = p0 + p, m0 + m, e0 + e
+        return res[0] if single else ([r[0] for r in res], [r[1] for r in res], [r[2] for r in res])

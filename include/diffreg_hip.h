@@ -1558,6 +1558,101 @@ int dr_overlap_2d3d_f64(int H, int W, int N, const float* depth, double scaling_
                         long long cap_pcd, int64_t* img_overlap_indices, int64_t* pcd_overlap_indices, int32_t* counts, void* workspace,
                         size_t workspace_bytes, void* stream);
 
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, fourteenth set (detected by symbol like the fourth to thirteenth sets): non-rigid ICP on an embedded deformation graph,
+ * the step from a 4DMatch match list to a deformation field.  2D-3D vision3d/ops/deformation_graph.py:26-103, vision3d/ops/
+ * embedded_deformation.py:31-66, vision3d/ops/nonrigid_icp_adam.py:9-131.  csrc/nonrigid.hip, indices in csrc/nonrigid_index.h; DESIGN 5x.
+ *
+ * All entries are ragged over P pairs: pair p's rows of a stacked array are [offsets[p], offsets[p + 1]) of an int32 DEVICE array of P + 1 entries
+ * (p_offsets: points, m_offsets: nodes, c_offsets: correspondences, e_offsets: edges).  Node indices (anchors, edge endpoints) are PAIR-LOCAL
+ * int64.  The entries are asynchronous on `stream` (a hipStream_t), allocate nothing, read nothing back to the host and use no floating-point
+ * atomic: two runs are bit-equal and every entry can be captured in a graph (dr_init sets the solver's LDS attribute, outside any capture).
+ * status [P] int32 receives per pair 0 or a sum of: 1, the pair has points but no node (dr_ed_graph_f32) or more nodes than max_nodes;
+ * 2, the pair's offsets are not 0 <= lo <= hi <= total; 4, an anchor outside [-1, M) or an edge endpoint outside [0, M) was met and treated as
+ * absent; 8 (dr_ed_graph_f32), a NaN or Inf coordinate of a point or a node left a point with fewer than min(K, M) anchors; 16
+ * (dr_nicp_adam_f32), a negative resumed step count was taken as 0.  A pair with bit 1 or 2 is neither read nor computed: its rows of the
+ * outputs are not written.  max_nodes is an upper bound of every pair's node count known to the HOST.  1 <= K <= 8.  P = 0 is a no-op; a negative size, a K out of range or a NULL pointer that a non-empty array needs is DR_EINVAL, a
+ * product of sizes beyond 2^31 - 1 DR_ENOSUP, a missing or short workspace DR_EWORKSPACE (16-byte aligned, else DR_EINVAL): all reported before
+ * the first launch, with every output untouched.
+ *
+ * dr_ed_graph_f32: build_euclidean_deformation_graph (deformation_graph.py:26-103).  Anchors: the min(K, M) nearest nodes of each point by brute
+ *   force in float64 on the float32 coordinates, d^2 = (dx dx + dy dy) + dz dz, ascending by d^2 and by the LOWEST index on equal d^2 (KeOps'
+ *   Kmin_argKmin leaves ties unspecified); columns from min(K, M) on receive index -1, weight 0, distance 0.  Only a FINITE d^2 makes an
+ *   anchor: a point or node with a NaN or Inf coordinate anchors nothing, the point's remaining columns are -1 / 0 / 0, its weights are
+ *   normalised over the anchors it has, no bit of the map is touched for the missing ones, and the pair gets status bit 8.  anchor_distances (or NULL) =
+ *   sqrt(d^2); anchor_weights = exp(-d^2 / (2 c^2)) divided by the row's sum (:22, :70-71), each rounded once to float32.  Two nodes are adjacent
+ *   when they anchor the same point (self edges included, :80-83): an M x M bit map in the workspace, filled with integer OR.  The edge list is
+ *   torch.nonzero's (:95): row-major ascending.  edge_distances (or NULL) = sqrt(max(|a|^2 - 2 a.b + |b|^2, 0) + 1e-8), pairwise_distance's
+ *   non-strict form (pairwise_distance.py:51-58; a self edge is 1e-4, not 0); edge_weights = its skinning weight over max(row sum, eps) (:85-87).
+ *   TWO calls: with e_offsets == NULL the entry writes the anchors, fills the bit map and writes edge_counts [P]; the caller turns the counts into
+ *   e_offsets [P + 1] (the one host read of a batch, or a device cumsum) and calls again with e_offsets != NULL and the SAME workspace, which
+ *   writes pair p's edges from row e_offsets[p]; rows at or behind min(e_offsets[p + 1], edge_cap) are not written.  node_coverage > 0.
+ *   Workspace: dr_ed_graph_workspace_bytes(n_nodes, max_nodes): n_nodes rows of ceil(max_nodes / 32) words, plus 12 bytes per node.
+ *   0 <= max_nodes <= n_nodes, else DR_EINVAL.
+ * dr_ed_warp_f32: apply_deformation (embedded_deformation.py:31-66) for any point set: out = sum_k w_k (R_k (p - g_k) + t_k + g_k) over the
+ *   anchors k != -1, w_k = anchor_weights_k / (sum over ALL K columns + eps) (:53), in float64, rounded once.  A point whose anchors are all -1
+ *   warps to zero (:63-65).  One thread per point.  transforms [n_nodes, 4, 4] row-major.
+ * dr_nicp_node_capacity: the largest node count of one pair the two solver entries accept: rotations, translations and both Adam moments of a
+ *   pair live in the LDS of one compute unit (csrc/nonrigid_index.h states the carve); at least 512.  There is no global-memory path above it.
+ * dr_nicp_cost_grad_f32: compute_cost_function (nonrigid_icp_adam.py:9-73) at the given rotations [n_nodes, 3, 3] / translations [n_nodes, 3]:
+ *   cost [P, 3] = (landmark: mean over the pair's N correspondences, :18; ARAP: mean over ALL its E edges, self edges counted, :36; orthogonality:
+ *   mean over its M nodes, :50-51), and grad_rot / grad_trn = the gradient of w_landmark landmark + w_arap arap + w_ortho ortho.  An empty mean is
+ *   NaN, as torch's.  Gradients reach a node by gather through node-major lists built in the workspace, each summed in float64 in a fixed order
+ *   and rounded once.  problem->max_nodes: an upper bound of every pair's node count known to the HOST, <= dr_nicp_node_capacity(), else
+ *   DR_EINVAL; it sizes the LDS of the launch.
+ * dr_nicp_adam_f32: non_rigid_icp_adam (nonrigid_icp_adam.py:76-131): options->num_iterations iterations of (cost, backward, Adam step,
+ *   ExponentialLR step) in ONE launch, one workgroup per pair.  Adam is torch's single-tensor statement as dr_adam_step_multi_f32 restates it
+ *   (no weight decay, no amsgrad), evaluated in float64 on the float32 state with each of parameter, exp_avg and exp_avg_sq rounded once per
+ *   iteration; the bias corrections are float64 from the step count; lr is multiplied by gamma once per iteration in float64,
+ *   step times before the first iteration when resuming (a negative step is taken as 0: status bit 16).  state: NULL, or a struct of DEVICE pointers (each may be NULL): with resume != 0 the run
+ *   starts from them (a NULL moment is zero, a NULL step 0; rotations / translations are required), otherwise from identity rotations, zero
+ *   translations and moments, step 0; non-NULL members receive the final state either way (step [P] += num_iterations).  transforms
+ *   [n_nodes, 4, 4] and cost [P, 3] (the three terms at the FINAL state; may be NULL) are always written; num_iterations == 0 returns the
+ *   starting state.  trace (or NULL) [P, num_iterations, 3] receives the three terms each iteration's backward started from.
+ *   Workspace of both: dr_nicp_workspace_bytes(P, n_corr, n_nodes, n_edges, K); the size query and the entries share one carve. */
+typedef struct dr_nicp_problem {
+    int P, n_corr, n_nodes, n_edges, K, max_nodes;
+    const float* nodes;               /* [n_nodes, 3] */
+    const int32_t* m_offsets;
+    const float* src_corr;            /* [n_corr, 3] */
+    const float* tgt_corr;            /* [n_corr, 3] */
+    const int32_t* c_offsets;
+    const int64_t* anchor_indices;    /* [n_corr, K] */
+    const float* anchor_weights;      /* [n_corr, K] */
+    const int64_t* edges;             /* [n_edges, 2] */
+    const float* edge_weights;        /* [n_edges] */
+    const int32_t* e_offsets;
+} dr_nicp_problem;
+typedef struct dr_nicp_options {
+    int num_iterations;                                   /* 500 */
+    double lr, gamma, beta1, beta2, eps;                  /* 0.5, 0.999, 0.9, 0.999, 1e-8 */
+    double w_landmark, w_arap, w_ortho;                   /* 1.0, 0.1, 0.1 */
+} dr_nicp_options;
+typedef struct dr_nicp_state {
+    float* rotations;                 /* [n_nodes, 3, 3] */
+    float* translations;              /* [n_nodes, 3] */
+    float* exp_avg_rot;
+    float* exp_avg_trn;
+    float* exp_avg_sq_rot;
+    float* exp_avg_sq_trn;
+    int32_t* step;                    /* [P] */
+} dr_nicp_state;
+int dr_nicp_node_capacity(void);
+size_t dr_ed_graph_workspace_bytes(int n_nodes, int max_nodes);
+int dr_ed_graph_f32(int P, int n_points, int n_nodes, int max_nodes, int K, const float* points, const int32_t* p_offsets, const float* nodes,
+                    const int32_t* m_offsets, double node_coverage, double eps, int64_t* anchor_indices, float* anchor_weights,
+                    float* anchor_distances, int32_t* edge_counts, const int32_t* e_offsets, long long edge_cap, int64_t* edge_indices,
+                    float* edge_weights, float* edge_distances, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int dr_ed_warp_f32(int P, int n_points, int n_nodes, int K, const float* points, const int32_t* p_offsets, const float* nodes,
+                   const int32_t* m_offsets, const float* transforms, const int64_t* anchor_indices, const float* anchor_weights, double eps,
+                   float* out, int32_t* status, void* stream);
+size_t dr_nicp_workspace_bytes(int P, int n_corr, int n_nodes, int n_edges, int K);
+int dr_nicp_cost_grad_f32(const dr_nicp_problem* problem, const float* rotations, const float* translations, double w_landmark, double w_arap,
+                          double w_ortho, float* cost, float* grad_rot, float* grad_trn, int32_t* status, void* workspace,
+                          size_t workspace_bytes, void* stream);
+int dr_nicp_adam_f32(const dr_nicp_problem* problem, const dr_nicp_options* options, const dr_nicp_state* state, int resume,
+                     float* transforms, float* cost, float* trace, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
