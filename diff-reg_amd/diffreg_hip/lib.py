@@ -477,6 +477,25 @@ SIGNATURES.update({
 })
 
 
+class Item3dArgs(ctypes.Structure):
+    """dr_item3d_args"""
+    _fields_ = [("P", c_int), ("n_src_raw", c_int), ("n_tgt_raw", c_int), ("n_src", c_int), ("n_tgt", c_int),
+                ("src_raw", c_void_p), ("s_raw_offsets", c_void_p), ("tgt_raw", c_void_p), ("t_raw_offsets", c_void_p), ("flow_raw", c_void_p),
+                ("src_sel", c_void_p), ("tgt_sel", c_void_p), ("s_offsets", c_void_p), ("t_offsets", c_void_p), ("rot_ab", c_void_p),
+                ("coin", c_void_p), ("src_jitter", c_void_p), ("tgt_jitter", c_void_p), ("noise", c_double), ("recompute_flow", c_int),
+                ("rot", c_void_p), ("trans", c_void_p), ("src_out", c_void_p), ("tgt_out", c_void_p), ("flow_out", c_void_p),
+                ("rot_out", c_void_p), ("trans_out", c_void_p), ("tsfm_out", c_void_p), ("status", c_void_p)]
+
+
+SIGNATURES.update({
+    # added after ABI 0.7.0, fifteenth set: the 3D / 4D dataset item (csrc/item3d.hip)
+    "dr_item3d_prepare_f32": (c_int, [ctypes.POINTER(Item3dArgs), c_void_p]),
+    "dr_radius_pairs_ragged_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dr_radius_pairs_ragged_f32": (c_int, [c_int, c_int, c_int] + [c_void_p] * 5 + [c_float, c_void_p, ctypes.c_longlong] + [c_void_p] * 5
+                                   + [c_size_t, c_void_p]),
+})
+
+
 def _bind(table):
     for name, (res, args) in table.items():
         if not hasattr(_lib, name):          # the sets added under one ABI number are detected by symbol
@@ -2120,6 +2139,93 @@ def coarse_gt_matches(src, s_offsets, tgt, t_offsets, rot, trn, radius, src_flow
                                         ptr(flow) if (flow is not None and ns) else None, ptr(rot) if P else None, ptr(trn) if P else None,
                                         float(radius), ptr(out_src) if ns else None, ptr(out_tgt) if ns else None, ptr(counts) if P else None,
                                         ptr(status) if P else None, ptr(ws), wsb, stream_of(src)))
+    return out_src, out_tgt, counts, status
+
+
+def item3d_prepare(src_raw, s_raw_offsets, tgt_raw, t_raw_offsets, rot, trans, *, s_offsets=None, t_offsets=None, src_sel=None, tgt_sel=None,
+                   flow_raw=None, recompute_flow=False, rot_ab=None, coin=None, src_jitter=None, tgt_jitter=None, noise=0.0):
+    """dr_item3d_prepare_f32, asynchronous -> dict(src, tgt [n, 3] float32, flow [n_src_raw, 3] or None, rot [P, 3, 3], trans [P, 3],
+    tsfm [P, 3, 4] float32, status [P] int32).  The clouds are stacked float32 device tensors with int32 offsets of P + 1 entries; a selection is
+    a contiguous int64 device vector of pair-local raw rows, one per output row, with the outputs' offsets next to it; rot_ab [P, 3, 3], coin [P]
+    and the jitter draws are float64."""
+    ensure_init()
+    dev = src_raw.device
+    for name, t in (("src_raw", src_raw), ("tgt_raw", tgt_raw), ("flow_raw", flow_raw)):
+        if t is not None and (t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous()):
+            raise ValueError("item3d_prepare: %s must be a contiguous float32 [n, 3] tensor" % name)
+    for name, t in (("src_sel", src_sel), ("tgt_sel", tgt_sel)):
+        if t is not None and (t.dtype != torch.int64 or t.dim() != 1 or not t.is_contiguous()):
+            raise ValueError("item3d_prepare: %s must be a contiguous int64 vector" % name)
+    sro = _offsets_i32(s_raw_offsets, None, dev, "item3d_prepare")
+    P = sro.shape[0] - 1
+    tro = _offsets_i32(t_raw_offsets, P, dev, "item3d_prepare")
+    so = sro if src_sel is None else _offsets_i32(s_offsets, P, dev, "item3d_prepare")
+    to = tro if tgt_sel is None else _offsets_i32(t_offsets, P, dev, "item3d_prepare")
+    n_sr, n_tr = src_raw.shape[0], tgt_raw.shape[0]
+    n_s = n_sr if src_sel is None else src_sel.shape[0]
+    n_t = n_tr if tgt_sel is None else tgt_sel.shape[0]
+    if flow_raw is not None and flow_raw.shape[0] != n_sr:
+        raise ValueError("item3d_prepare: flow_raw has one row per raw source point")
+    if flow_raw is not None and recompute_flow and n_s != n_sr:
+        raise ValueError("item3d_prepare: a selection shorter than the cloud leaves no flow to recompute (the reference raises on "
+                         "`src_pcd_deformed - src_pcd`)")
+    f64 = lambda t, shape, name: None if t is None else _shaped(t.to(device=dev, dtype=torch.float64).contiguous(), shape, name)
+    rot = f64(rot, (P, 3, 3), "rot")
+    trans = f64(trans.reshape(P, 3), (P, 3), "trans")
+    rot_ab = f64(rot_ab, (P, 3, 3), "rot_ab")
+    coin = f64(coin, (P,), "coin")
+    if rot_ab is not None and coin is None:
+        raise ValueError("item3d_prepare: rot_ab needs coin")
+    src_jitter, tgt_jitter = f64(src_jitter, (n_s, 3), "src_jitter"), f64(tgt_jitter, (n_t, 3), "tgt_jitter")
+    out = dict(src=torch.empty(n_s, 3, device=dev), tgt=torch.empty(n_t, 3, device=dev),
+               flow=None if flow_raw is None else torch.empty(n_sr, 3, device=dev), rot=torch.empty(P, 3, 3, device=dev),
+               trans=torch.empty(P, 3, device=dev), tsfm=torch.empty(P, 3, 4, device=dev),
+               status=torch.empty(P, dtype=torch.int32, device=dev))
+    opt = lambda t, n=1: ptr(t) if (t is not None and n) else None
+    a = Item3dArgs(P, n_sr, n_tr, n_s, n_t, opt(src_raw, n_sr), ptr(sro), opt(tgt_raw, n_tr), ptr(tro), opt(flow_raw, n_sr), opt(src_sel, n_s),
+                   opt(tgt_sel, n_t), ptr(so), ptr(to), opt(rot_ab, P), opt(coin, P), opt(src_jitter, n_s), opt(tgt_jitter, n_t), float(noise),
+                   1 if recompute_flow else 0, opt(rot, P), opt(trans, P), opt(out["src"], n_s), opt(out["tgt"], n_t), opt(out["flow"], n_sr),
+                   opt(out["rot"], P), opt(out["trans"], P), opt(out["tsfm"], P), opt(out["status"], P))
+    check(_lib.dr_item3d_prepare_f32(ctypes.byref(a), stream_of(src_raw)))
+    return out
+
+
+def _shaped(t, shape, name):
+    if tuple(t.shape) != tuple(shape):
+        raise ValueError("item3d: %s must have shape %s (got %s)" % (name, tuple(shape), tuple(t.shape)))
+    return t
+
+
+def radius_pairs_ragged(src, s_offsets, tgt, t_offsets, transforms, radius, c_offsets=None, capacity=0):
+    """dr_radius_pairs_ragged_f32, asynchronous -> (out_src, out_tgt int64 [capacity], counts int32 [P, 2] = (written, found), status int32 [P]).
+    src [ns, 3] / tgt [nt, 3] contiguous float32, stacked by int32 offsets of P + 1 entries; transforms [P, 3, 4] float32 or None; c_offsets int64
+    [P + 1] on the device: pair p's room in the list.  capacity = 0 counts only."""
+    ensure_init()
+    dev = src.device
+    for name, t in (("src", src), ("tgt", tgt)):
+        if t.dtype != torch.float32 or t.dim() != 2 or t.shape[1] != 3 or not t.is_contiguous():
+            raise ValueError("radius_pairs_ragged: %s must be a contiguous float32 [n, 3] tensor" % name)
+    so = _offsets_i32(s_offsets, None, dev, "radius_pairs_ragged")
+    P = so.shape[0] - 1
+    to = _offsets_i32(t_offsets, P, dev, "radius_pairs_ragged")
+    ns, nt = src.shape[0], tgt.shape[0]
+    T = None if transforms is None else _shaped(transforms.to(device=dev, dtype=torch.float32).contiguous(), (P, 3, 4), "transforms")
+    capacity = int(capacity)
+    co = None
+    if capacity > 0:
+        co = c_offsets.to(device=dev, dtype=torch.int64).contiguous()
+        if co.shape != (P + 1,):
+            raise ValueError("radius_pairs_ragged: c_offsets must be a vector of P + 1 entries")
+    out_src = torch.empty(capacity, dtype=torch.int64, device=dev)
+    out_tgt = torch.empty(capacity, dtype=torch.int64, device=dev)
+    counts = torch.zeros(P, 2, dtype=torch.int32, device=dev)
+    status = torch.zeros(P, dtype=torch.int32, device=dev)
+    wsb = _lib.dr_radius_pairs_ragged_workspace_bytes(P, ns, nt)
+    ws = torch.empty(max(wsb, 256), dtype=torch.uint8, device=dev)
+    check(_lib.dr_radius_pairs_ragged_f32(P, ns, nt, ptr(src) if ns else None, ptr(so), ptr(tgt) if nt else None, ptr(to), ptr(T) if P else None,
+                                          float(radius), ptr(co), capacity, ptr(out_src) if capacity else None,
+                                          ptr(out_tgt) if capacity else None, ptr(counts) if P else None, ptr(status) if P else None, ptr(ws),
+                                          wsb, stream_of(src)))
     return out_src, out_tgt, counts, status
 
 

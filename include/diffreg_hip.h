@@ -71,7 +71,11 @@ extern "C" {
  *          dr_adam_step_multi_f32, dr_optim_finish with the new structs dr_optim_tensor, dr_sgd_options, dr_adam_options (new entries only;
  *          nothing older changed).
  *   0.7.0, thirteenth set (same rule)  the pixel-point ground truth of a 2D-3D dataset item: dr_corr_2d3d_mutual_f64, dr_corr_2d3d_radius_f64,
- *          dr_overlap_2d3d_f64 with their workspace size queries, dr_column_mean_seq_f32 (new entries only; nothing older changed). */
+ *          dr_overlap_2d3d_f64 with their workspace size queries, dr_column_mean_seq_f32 (new entries only; nothing older changed).
+ *   0.7.0, fourteenth set (same rule)  non-rigid ICP on an embedded deformation graph: dr_ed_graph_f32, dr_ed_warp_f32, dr_nicp_cost_grad_f32,
+ *          dr_nicp_adam_f32 with their size queries (new entries only; nothing older changed).
+ *   0.7.0, fifteenth set (same rule)  the 3D / 4D dataset item: dr_item3d_prepare_f32 with the new struct dr_item3d_args,
+ *          dr_radius_pairs_ragged_f32 with dr_radius_pairs_ragged_workspace_bytes (new entries only; dr_radius_pairs_f32 is unchanged). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1652,6 +1656,83 @@ int dr_nicp_cost_grad_f32(const dr_nicp_problem* problem, const float* rotations
                           size_t workspace_bytes, void* stream);
 int dr_nicp_adam_f32(const dr_nicp_problem* problem, const dr_nicp_options* options, const dr_nicp_state* state, int resume,
                      float* transforms, float* cost, float* trace, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, fifteenth set (detected by symbol like the fourth to fourteenth sets): the 3D / 4D dataset item, what
+ * _3DMatch.__getitem__ (3D/datasets/_3dmatch.py:55-135) and _4DMatch.__getitem__ (3D/datasets/_4dmatch.py:58-146) compute behind their file
+ * reads.  csrc/item3d.hip, indices in csrc/item3d_index.h; DESIGN 5y.
+ *
+ * Both entries are ragged over P pairs: pair p's rows of a stacked array are [offsets[p], offsets[p + 1]) of an int32 DEVICE array of P + 1
+ * entries.  They are asynchronous on `stream` (a hipStream_t), allocate nothing, read nothing back to the host and use no floating-point atomic
+ * (the status words take integer ORs): two runs are bit-equal and both can be captured on one stream.  status [P] int32 receives per pair 0 or a
+ * sum of: 2, the pair's offsets are not 0 <= lo <= hi <= total (the pair is neither read nor written); 4, a selection index outside the pair's
+ * raw cloud was met (its output row is zero); 8, the flow is recomputed but the pair's selected and raw source counts differ.  P = 0 is a no-op;
+ * Rows of a stacked array that lie in no pair's slice (in front of offsets[0], behind offsets[P], or in a pair with status bit 2) are allowed:
+ * dr_item3d_prepare_f32 writes such output rows as zero, dr_radius_pairs_ragged_f32 pairs them with nothing.
+ * a negative size or a NULL pointer that a non-empty array needs is DR_EINVAL, P > 256 (every thread scans the offsets: P is a batch size) or more than 2^28 stacked rows DR_ENOSUP, a missing or
+ * short workspace DR_EWORKSPACE (16-byte aligned, else DR_EINVAL): all reported before the first launch.
+ *
+ * dr_item3d_prepare_f32: per pair, in the reference's order --
+ *   subsample (_3dmatch.py:71-76, _4dmatch.py:86-91): output row i of a side is raw row src_sel[i] / tgt_sel[i] (PAIR-LOCAL int64, stacked like
+ *     the outputs: the first max_points entries of a permutation); a NULL selection is the identity and needs n_src == n_src_raw;
+ *   rotate (_3dmatch.py:95-103): rot_ab [P, 3, 3] float64 (Rotation.from_euler('zyx', .)) turns the source when coin[p] > 0.5, else the target:
+ *     cloud' = rot_ab cloud; rot' = rot rot_ab^T (source) or rot' = rot_ab rot, trans' = rot_ab trans (target).  NULL: no rotation;
+ *   jitter (_3dmatch.py:105-106): cloud' += (u - 0.5) noise with u = src_jitter [n_src, 3] / tgt_jitter [n_tgt, 3] float64 draws in [0, 1);
+ *     NULL: no jitter;
+ *   flow (_4dmatch.py:77, 115, 124; flow_raw != NULL and recompute_flow != 0): flow' = rot_ab (src + flow) - src', the deformed copy built in
+ *     float32 from the loaded arrays, turned with the source when the source is turned, and NOT jittered, minus the jittered source.
+ *   The reference computes a turned cloud in float64 (numpy promotes through rot_ab) and adds the jitter to an unturned float32 cloud in place;
+ *   the collate casts to float32.  So every output is evaluated in double on the float32 inputs and rounded once; a row that is neither turned
+ *   nor jittered is copied.  rot / trans [P, 3, 3] / [P, 3] are float64 inputs; rot_out / trans_out float32; tsfm_out [P, 3, 4] float32 = (rot' |
+ *   trans'), the `transforms` of dr_radius_pairs_ragged_f32 (to_tsfm, _3dmatch.py:109).
+ *   The 4DMatch subsample indexes src_pcd ONLY: src_pcd_deformed and s2t_flow keep their loaded row count (_4dmatch.py:77, 86-88).  flow_out is
+ *   therefore [n_src_raw, 3], stacked by s_raw_offsets: with recompute_flow == 0 it is flow_raw unchanged -- UNSELECTED, whatever src_sel says,
+ *   as the reference returns it -- and with recompute_flow != 0 row i of the deformed copy meets row i of the selected source.  The reference
+ *   raises there when the selection is shorter than the cloud (`src_pcd_deformed - src_pcd`, shapes differ): flow_raw with recompute_flow and
+ *   n_src != n_src_raw is DR_EINVAL (per pair: status bit 8). */
+typedef struct dr_item3d_args {
+    int P, n_src_raw, n_tgt_raw, n_src, n_tgt;
+    const float* src_raw;             /* [n_src_raw, 3] */
+    const int32_t* s_raw_offsets;
+    const float* tgt_raw;             /* [n_tgt_raw, 3] */
+    const int32_t* t_raw_offsets;
+    const float* flow_raw;            /* [n_src_raw, 3] or NULL */
+    const int64_t* src_sel;           /* [n_src] or NULL */
+    const int64_t* tgt_sel;           /* [n_tgt] or NULL */
+    const int32_t* s_offsets;         /* [P + 1] rows of the outputs */
+    const int32_t* t_offsets;
+    const double* rot_ab;             /* [P, 3, 3] or NULL */
+    const double* coin;               /* [P]; required with rot_ab */
+    const double* src_jitter;         /* [n_src, 3] or NULL */
+    const double* tgt_jitter;         /* [n_tgt, 3] or NULL */
+    double noise;                     /* augment_noise */
+    int recompute_flow;               /* data_augmentation of _4dmatch.py:109 */
+    const double* rot;                /* [P, 3, 3] */
+    const double* trans;              /* [P, 3] */
+    float* src_out;                   /* [n_src, 3] */
+    float* tgt_out;                   /* [n_tgt, 3] */
+    float* flow_out;                  /* [n_src_raw, 3]; required with flow_raw */
+    float* rot_out;                   /* [P, 3, 3] */
+    float* trans_out;                 /* [P, 3] */
+    float* tsfm_out;                  /* [P, 3, 4] */
+    int32_t* status;                  /* [P] */
+} dr_item3d_args;
+int dr_item3d_prepare_f32(const dr_item3d_args* args, void* stream);
+
+/* dr_radius_pairs_ragged_f32: get_correspondences / KDTree_corr (3D/lib/benchmark_utils.py:166-185, K = None) for P pairs at once: per pair all
+ *   (i, j), PAIR-LOCAL, with |T_p src_i - tgt_j| < radius, in ascending (i, j) (Open3D's search_radius_vector_3d returns a row's partners in
+ *   ascending distance).  The float32 expressions are dr_radius_pairs_f32's: q = x T0 + y T1 + z T2 + T3 per row of transforms [P, 3, 4] (NULL:
+ *   identity), d^2 = dx dx + dy dy + dz dz, d^2 < radius^2.  The targets are sorted by (pair, cell of edge radius (1 + 2^-7) counted from the
+ *   pair's min corner) and a row sweeps its 27 cells, so the work follows the number of close points, not ns x nt; a row may have any number of
+ *   partners.  Cell coordinates are clamped to [0, 65535]: a source outside the target's grid, or a cloud wider than 65536 cells, only tests more
+ *   candidates.  Pair p's list goes to rows [c_offsets[p], min(c_offsets[p + 1], capacity)) of out_src / out_tgt [capacity] (c_offsets: int64
+ *   DEVICE array of P + 1 entries); counts [P, 2] int32 = (written, found), found exact and saturated at 2^31 - 1, written = min(found, room);
+ *   nothing is written behind a pair's room, and the entries kept are the first in (i, j) order.  capacity == 0 (c_offsets and the outputs may be
+ *   NULL) counts only.  radius > 0.  Workspace: dr_radius_pairs_ragged_workspace_bytes(P, ns, nt); the size query and the entry share one carve. */
+size_t dr_radius_pairs_ragged_workspace_bytes(int P, int ns, int nt);
+int dr_radius_pairs_ragged_f32(int P, int ns, int nt, const float* src, const int32_t* s_offsets, const float* tgt, const int32_t* t_offsets,
+                               const float* transforms, float radius, const int64_t* c_offsets, long long capacity, int64_t* out_src,
+                               int64_t* out_tgt, int32_t* counts, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
