@@ -250,7 +250,7 @@ __global__ __launch_bounds__(1024) void top1_union_kernel(const T* __restrict__ 
         for (int j = lane; j < M; j += 64) {
             if (tm && !tm[j]) continue;
             const T v = c[(size_t)i * M + j];
-            if (v > best || (v == best && j < bj) || bj == 0x7fffffff) { best = v; bj = j; }
+            if (v > best || bj == 0x7fffffff) { best = v; bj = j; }   // (a lane's j only grows: an equal value never replaces its pick)
         }
         for (int m = 32; m >= 1; m >>= 1) {
             const T ov = __shfl_xor(best, m); const int oj = __shfl_xor(bj, m);
@@ -292,7 +292,7 @@ __global__ __launch_bounds__(1024) void top1_block_kernel(const T* __restrict__ 
                 for (int j = lane; j < M; j += 64) {
                     if (tm && !tm[j]) continue;
                     const T v = c[(size_t)i * M + j];
-                    if (v > best || (v == best && j < bj) || bj == 0x7fffffff) { best = v; bj = j; }
+                    if (v > best || bj == 0x7fffffff) { best = v; bj = j; }   // (a lane's j only grows: an equal value never replaces its pick)
                 }
                 for (int m = 32; m >= 1; m >>= 1) {
                     const T ov = __shfl_xor(best, m); const int oj = __shfl_xor(bj, m);
