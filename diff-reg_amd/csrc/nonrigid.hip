@@ -14,21 +14,12 @@
 // enter it), in float64 and in list order, rounds it once, and applies Adam to its own parameter -- reading the state of this iteration from one
 // copy and writing the next into the other.  An iteration therefore has TWO barriers: after the per-correspondence residuals are written (they
 // live in the workspace), and after the update.
-#include "common.h"
-#include "nonrigid_index.h"
-#include "../../include/diffreg_hip.h"
+#include "nonrigid_lists.h"      // status bits, NrPair, NrAdj and the set-up pass shared with nonrigid_gn.hip
 
 // the float64 sums below are written operation by operation; nothing becomes an FMA behind the statement
 #pragma clang fp contract(off)
 
 namespace dr {
-
-constexpr int NR_ST_NODES = 1;    // status bit: points without nodes (graph) / more nodes than max_nodes (solver): nothing is computed
-constexpr int NR_ST_OFFSETS = 2;  // status bit: the pair's offsets do not describe a slice of the stacked array: nothing is read
-constexpr int NR_ST_INDEX = 4;    // status bit: an anchor / edge endpoint out of range was treated as absent
-constexpr int NR_ST_NONFINITE = 8;   // status bit (graph): a non-finite coordinate left a point with fewer than min(K, M) anchors
-constexpr int NR_ST_STEP = 16;       // status bit (solver): a negative resumed step count was taken as 0
-constexpr double NR_WARP_EPS = 1e-6;   // apply_deformation's default eps, which compute_landmark_cost does not override
 
 // exp(-d^2 / (2 c^2)), compute_skinning_weights (deformation_graph.py:22)
 __device__ __forceinline__ double nr_skin(double d, double c) { return exp(-(d * d) / (2.0 * (c * c))); }
@@ -299,11 +290,6 @@ __global__ __launch_bounds__(NR_TILE) void ed_warp_kernel(WarpArgs A) {
 }
 
 // ------------------------------------------------------------------------------------------------ solver
-struct NrAdj {
-    int other;
-    float weight;
-};
-
 struct NicpArgs {
     dr_nicp_problem pb;
     // workspace
@@ -332,11 +318,6 @@ struct NicpArgs {
     int32_t* status;
     int grad_only;                    // dr_nicp_cost_grad_f32: one gradient at the given state, no update
     NrLdsCarve lds;
-};
-
-// what a pair's workgroup keeps in registers about its slices
-struct NrPair {
-    int m0, M, c0, N, e0, E, K;
 };
 
 // the warped correspondence c minus its target (compute_landmark_cost's difference), float64 on the LDS state `par`
@@ -513,72 +494,12 @@ __global__ __launch_bounds__(NR_SOLVER_BLOCK) void nicp_kernel(NicpArgs A) {
         cur[it] = p; mo[it] = m; vo[it] = v;
     }
     __syncthreads();
-    bool bad = false;
-    for (int c = t; c < S.N; c += NR_SOLVER_BLOCK) {
-        const size_t r = (size_t)(S.c0 + c) * S.K;
-        double sum = 0.0;
-        for (int k = 0; k < S.K; ++k) sum = sum + (double)A.pb.anchor_weights[r + k];
-        sum = sum + NR_WARP_EPS;
-        for (int k = 0; k < S.K; ++k) {
-            const long long a = A.pb.anchor_indices[r + k];
-            const bool ok = a >= 0 && a < S.M;
-            bad = bad || (!ok && a != -1);
-            A.anchor[r + k] = ok ? (int)a : -1;
-            A.weight[r + k] = (float)((double)A.pb.anchor_weights[r + k] / sum);
-        }
+    // ---- set-up: the anchors, weights and node-major lists of the workspace (nonrigid_lists.h).  The counts and row starts pass through the LDS
+    // of the second parameter copy, which no one reads before an iteration has written all of it: 3 (M + 1) <= 12 M ints for M >= 1.
+    {
+        const NrLists L = {A.anchor, A.weight, A.lm_ptr, A.lm_corr, A.lm_pw, A.out_ptr, A.out_adj, A.in_ptr, A.in_adj};
+        nr_setup_lists(A.pb, L, S, pair, (int*)nxt, s_status);
     }
-    __syncthreads();
-
-    // ---- set-up: the node-major lists.  Node i's thread counts its entries, a prefix over the nodes gives the rows, the same walk fills them:
-    // every list is in ascending entry order.  The counts and row starts pass through the LDS of the second parameter copy, which no one reads
-    // before an iteration has written all of it.
-    int* cnt = (int*)nxt;                                   // three arrays of M + 1 ints: 3 (M + 1) <= 12 M for M >= 1
-    const int32_t* anc = A.anchor + (size_t)S.c0 * S.K;
-    const long long* edg = (const long long*)A.pb.edges + (size_t)S.e0 * 2;
-    const size_t row0 = (size_t)S.m0 + pair;
-    for (int i = t; i < S.M; i += NR_SOLVER_BLOCK) {
-        int co = 0, ci = 0;
-        for (int e = 0; e < S.E; ++e) {
-            const long long u = edg[2 * e], v = edg[2 * e + 1];
-            const bool ok = u >= 0 && u < S.M && v >= 0 && v < S.M;
-            bad = bad || !ok;
-            co += (ok && u == i) ? 1 : 0;
-            ci += (ok && v == i) ? 1 : 0;
-        }
-        cnt[i] = nr_csr_count(anc, S.N * S.K, 1, i);
-        cnt[(S.M + 1) + i] = co;
-        cnt[2 * (S.M + 1) + i] = ci;
-    }
-    if (bad) atomicOr(s_status, NR_ST_INDEX);
-    __syncthreads();
-    if (t < 3 && S.M > 0) nr_csr_prefix(cnt + t * (S.M + 1), S.M);
-    __syncthreads();
-    for (int i = t; i <= S.M && S.M > 0; i += NR_SOLVER_BLOCK) {
-        A.lm_ptr[row0 + i] = cnt[i];
-        A.out_ptr[row0 + i] = cnt[(S.M + 1) + i];
-        A.in_ptr[row0 + i] = cnt[2 * (S.M + 1) + i];
-    }
-    for (int i = t; i < S.M; i += NR_SOLVER_BLOCK) {
-        int at = cnt[i];
-        const size_t base = (size_t)S.c0 * S.K;
-        for (int e = 0; e < S.N * S.K; ++e) {
-            if (anc[e] != i) continue;
-            const int c = e / S.K;
-            const float* p = A.pb.src_corr + (size_t)(S.c0 + c) * 3;
-            A.lm_corr[base + at] = c;
-            A.lm_pw[base + at] = make_float4(p[0], p[1], p[2], A.weight[base + e]);
-            ++at;
-        }
-        int ao = cnt[(S.M + 1) + i], ai = cnt[2 * (S.M + 1) + i];
-        for (int e = 0; e < S.E; ++e) {
-            const long long u = edg[2 * e], v = edg[2 * e + 1];
-            if (!(u >= 0 && u < S.M && v >= 0 && v < S.M)) continue;
-            const float w = A.pb.edge_weights[S.e0 + e];
-            if (u == i) { A.out_adj[S.e0 + ao].other = (int)v; A.out_adj[S.e0 + ao].weight = w; ++ao; }
-            if (v == i) { A.in_adj[S.e0 + ai].other = (int)u; A.in_adj[S.e0 + ai].weight = w; ++ai; }
-        }
-    }
-    __syncthreads();
 
     if (A.grad_only) {
         for (int c = t; c < S.N; c += NR_SOLVER_BLOCK) {

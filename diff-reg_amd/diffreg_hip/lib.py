@@ -496,6 +496,21 @@ SIGNATURES.update({
 })
 
 
+class NicpGnOptions(ctypes.Structure):
+    """dr_nicp_gn_options"""
+    _fields_ = [("num_iterations", c_int), ("corr_lambda", c_double), ("arap_lambda", c_double), ("lm_lambda", c_double)]
+
+
+SIGNATURES.update({
+    # added after ABI 0.7.0, sixteenth set: Gauss-Newton non-rigid ICP and the batched SPD factor-and-solve (csrc/nonrigid_gn.hip)
+    "dr_nicp_gn_workspace_bytes": (c_size_t, [c_int] * 6),
+    "dr_nicp_gn_f32": (c_int, [ctypes.POINTER(NicpProblem), ctypes.POINTER(NicpGnOptions), c_void_p, ctypes.POINTER(NicpState), c_int]
+                       + [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "dr_nicp_gn_normal_f32": (c_int, [ctypes.POINTER(NicpProblem), ctypes.POINTER(NicpGnOptions)] + [c_void_p] * 7 + [c_size_t, c_void_p]),
+    "dr_spd_solve_f64": (c_int, [c_int, c_int] + [c_void_p] * 5),
+})
+
+
 def _bind(table):
     for name, (res, args) in table.items():
         if not hasattr(_lib, name):          # the sets added under one ABI number are detected by symbol

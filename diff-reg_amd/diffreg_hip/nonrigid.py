@@ -9,7 +9,11 @@ Refusals are raised at call time, before any launch: inputs that are not float32
 nodes than node_capacity().  One exception: when NonRigidRegistration subsamples the nodes itself, their number is known only after that launch,
 so the capacity is checked behind it, before the graph and the solver are launched.  There is no CPU path and no path above the capacity.
 The ragged entries return the device status vector (the bits are listed in include/diffreg_hip.h); the three vision3d names, whose return tuples
-have no place for it, discard it, and NonRigidRegistration hands it out as graph["status"]."""
+have no place for it, discard it, and NonRigidRegistration hands it out as graph["status"].
+
+The Gauss-Newton solver (sixteenth set, csrc/nonrigid_gn.hip) sits next to the Adam one: non_rigid_icp_gauss_newton and the layer
+NonRigidICP keep the signatures of vision3d/layers/nonrigid_icp.py:18-207, nicp_gauss_newton / nicp_gn_normal / spd_solve are the ragged entries,
+and NonRigidRegistration(solver="gauss_newton") selects it (the default stays Adam).  It is inference only: an input that requires grad raises."""
 import ctypes
 
 import torch
@@ -258,6 +262,131 @@ def nicp_adam(problem, num_iterations=500, lr=0.5, gamma=0.999, beta1=0.9, beta2
     return T, cost, tr, status
 
 
+# ------------------------------------------------------------------------------------------------ Gauss-Newton (sixteenth set)
+PIVOT_FAILED = 32        # status bit of the Gauss-Newton entries: a pivot of the factorisation was not finite or not > 0; the pair stopped
+
+
+def _no_grad(*tensors):
+    """the device path is inference only: an input that requires grad is refused before any launch"""
+    for t in tensors:
+        if isinstance(t, torch.Tensor) and t.requires_grad:
+            raise RuntimeError("the device Gauss-Newton solver has no backward pass: an input requires grad (detach it)")
+
+
+def _gn_problem(problem, corr_weights):
+    _no_grad(problem.nodes, problem.src, problem.tgt, problem.aw, problem.ew, corr_weights)
+    if corr_weights is not None:
+        corr_weights = _f32("corr_weights", corr_weights, ())
+        if corr_weights.shape[0] != problem.n or corr_weights.device != problem.dev:
+            raise ValueError("corr_weights needs one entry per correspondence, on the problem's device")
+    return corr_weights
+
+
+def _gn_workspace_bytes(problem):
+    return _raw.dr_nicp_gn_workspace_bytes(problem.P, problem.n, problem.m, problem.e, problem.K, problem.max_nodes)
+
+
+def gn_buffers(problem):
+    """(transforms [m, 4, 4], status [P], workspace) for nicp_gauss_newton(..., out=): allocate once, outside a graph capture or a loop.  The
+    workspace is (6 max_nodes)^2 doubles per pair (75 MB at 512 nodes); it lives as long as the caller keeps the tuple."""
+    dev = problem.dev
+    return (torch.empty(problem.m, 4, 4, device=dev), torch.empty(problem.P, dtype=torch.int32, device=dev),
+            _ws(_gn_workspace_bytes(problem), dev))
+
+
+def _gn_struct(problem, unit_edge_weights):
+    """the dr_nicp_problem of a call; edge_weights=None of the reference is a NULL pointer (weight 1)"""
+    pb = problem.struct()
+    if not unit_edge_weights:
+        return pb
+    pb2 = lib.NicpProblem()
+    ctypes.memmove(ctypes.byref(pb2), ctypes.byref(pb), ctypes.sizeof(pb))
+    pb2.edge_weights = None
+    return pb2
+
+
+def new_gn_state(problem):
+    """a Gauss-Newton state to run from and to resume: identity rotations, zero translations"""
+    return dict(rotations=torch.eye(3, device=problem.dev).repeat(problem.m, 1, 1), translations=torch.zeros(problem.m, 3, device=problem.dev))
+
+
+def nicp_gauss_newton(problem, num_iterations=5, corr_lambda=1.0, arap_lambda=0.1, lm_lambda=0.1, corr_weights=None, state=None, resume=False,
+                      unit_edge_weights=False, out=None):
+    """dr_nicp_gn_f32 -> (transforms [m, 4, 4], status [P]).  state: a dict with "rotations" [m, 3, 3] and "translations" [m, 3]
+    (new_gn_state()); it receives the final state, and with resume=True the run starts from it.  unit_edge_weights: the reference's
+    edge_weights=None.  out: gn_buffers(problem) to write into, so that a captured graph or a loop allocates nothing.
+    Inference only: an input that requires grad raises before any launch."""
+    if int(num_iterations) < 0:
+        raise ValueError("num_iterations must not be negative")
+    if resume and state is None:
+        raise ValueError("resume needs a state")
+    cw = _gn_problem(problem, corr_weights)
+    lib.ensure_init()
+    dev, m, P = problem.dev, problem.m, problem.P
+    st = NicpState()
+    if state is not None:
+        for k, per in (("rotations", 9), ("translations", 3)):
+            t = state.get(k)
+            if t is None:
+                continue
+            if t.dtype != torch.float32 or not t.is_contiguous() or t.device != dev or t.numel() != m * per:
+                raise ValueError("state[%r] must be a contiguous float32 tensor of the problem's size on its device" % k)
+            _no_grad(t)
+            setattr(st, k, ptr(t).value if t.numel() else None)
+    pb = _gn_struct(problem, unit_edge_weights)
+    op = lib.NicpGnOptions(int(num_iterations), float(corr_lambda), float(arap_lambda), float(lm_lambda))
+    wsb = _gn_workspace_bytes(problem)
+    T, status, ws = gn_buffers(problem) if out is None else out
+    if ws.numel() < wsb or T.shape[0] != m or status.numel() != P:
+        raise ValueError("out must be gn_buffers() of this problem")
+    check(_raw.dr_nicp_gn_f32(ctypes.byref(pb), ctypes.byref(op), ptr(cw) if (cw is not None and problem.n) else None, ctypes.byref(st),
+                              1 if resume else 0, ptr(T) if m else None, ptr(status), ptr(ws), wsb, stream_of(problem.nodes)))
+    return T, status
+
+
+def nicp_gn_normal(problem, rotations, translations, corr_lambda=1.0, arap_lambda=0.1, lm_lambda=0.1, corr_weights=None,
+                   unit_edge_weights=False):
+    """dr_nicp_gn_normal_f32 -> (A [P, 6 max_nodes, 6 max_nodes] float64, b [P, 6 max_nodes] float64, status [P]): the normal equations of ONE
+    iteration at the given state; pair p's system is the leading 6 M_p corner of its slot"""
+    rot, trn = _f32("rotations", rotations, (3, 3)), _f32("translations", translations, (3,))
+    if rot.shape[0] != problem.m or trn.shape[0] != problem.m:
+        raise ValueError("rotations / translations need one row per node")
+    cw = _gn_problem(problem, corr_weights)
+    _no_grad(rot, trn)
+    lib.ensure_init()
+    dev, m, P, ld = problem.dev, problem.m, problem.P, 6 * problem.max_nodes
+    pb = _gn_struct(problem, unit_edge_weights)
+    op = lib.NicpGnOptions(1, float(corr_lambda), float(arap_lambda), float(lm_lambda))
+    A = torch.empty(P, ld, ld, dtype=torch.float64, device=dev)
+    b = torch.empty(P, ld, dtype=torch.float64, device=dev)
+    status = torch.empty(P, dtype=torch.int32, device=dev)
+    wsb = _gn_workspace_bytes(problem)
+    ws = _ws(wsb, dev)
+    check(_raw.dr_nicp_gn_normal_f32(ctypes.byref(pb), ctypes.byref(op), ptr(cw) if (cw is not None and problem.n) else None,
+                                     ptr(rot) if m else None, ptr(trn) if m else None, ptr(A) if A.numel() else None,
+                                     ptr(b) if b.numel() else None, ptr(status), ptr(ws), wsb, stream_of(problem.nodes)))
+    return A, b, status
+
+
+def spd_solve(A, b, sizes=None):
+    """dr_spd_solve_f64, IN PLACE: A [P, n_max, n_max] float64 (lower triangle read; receives the Cholesky factor), b [P, n_max] float64
+    (receives the solution); sizes: int32 device tensor [P] of each system's n (None: all n_max).  -> status [P] (32: a pivot was not > 0)"""
+    if A.dtype != torch.float64 or b.dtype != torch.float64 or A.dim() != 3 or A.shape[1] != A.shape[2] or tuple(b.shape) != tuple(A.shape[:2]):
+        raise ValueError("A must be [P, n, n] float64 and b [P, n] float64")
+    if not (A.is_contiguous() and b.is_contiguous()) or A.device != b.device:
+        raise ValueError("A and b must be contiguous and on one device")
+    lib.ensure_init()
+    P, n = A.shape[0], A.shape[1]
+    if sizes is None:
+        sizes = torch.full((P,), n, dtype=torch.int32, device=A.device)
+    if sizes.dtype != torch.int32 or sizes.numel() != P or sizes.device != A.device or not sizes.is_contiguous():
+        raise ValueError("sizes must be a contiguous int32 tensor [P] on A's device")
+    status = torch.empty(P, dtype=torch.int32, device=A.device)
+    check(_raw.dr_spd_solve_f64(P, n, ptr(sizes) if P else None, ptr(A) if A.numel() else None, ptr(b) if b.numel() else None,
+                                ptr(status) if P else None, stream_of(A)))
+    return status
+
+
 # ------------------------------------------------------------------------------------------------ vision3d's three names
 def build_euclidean_deformation_graph(points, nodes, num_anchors, node_coverage, return_point_anchor=True, return_node_graph=True,
                                       return_distance=False, return_adjacent_matrix=False, eps=1e-6):
@@ -294,6 +423,37 @@ def non_rigid_icp_adam(src_nodes, src_corr_points, tgt_corr_points, anchor_indic
     return nicp_adam(pb, num_iterations=num_iterations)[0]
 
 
+def non_rigid_icp_gauss_newton(src_nodes, src_corr_points, tgt_corr_points, anchor_indices, anchor_weights, edge_indices, corr_weights=None,
+                               edge_weights=None, corr_lambda=1.0, arap_lambda=0.1, lm_lambda=0.1, num_iterations=5):
+    """vision3d/layers/nonrigid_icp.py:18-154 for one pair -> transforms [M, 4, 4]; the status word is discarded (nicp_gauss_newton returns it).
+    Inference only: an input that requires grad raises.  A row that names one node in two columns keeps the later column's Jacobian block."""
+    _no_grad(src_nodes, src_corr_points, tgt_corr_points, anchor_weights, corr_weights, edge_weights)
+    unit = edge_weights is None
+    if unit:
+        edge_weights = torch.ones(edge_indices.shape[0], device=src_nodes.device)
+    pb = Problem(src_nodes, src_corr_points, tgt_corr_points, anchor_indices, anchor_weights, edge_indices, edge_weights)
+    return nicp_gauss_newton(pb, num_iterations=num_iterations, corr_lambda=corr_lambda, arap_lambda=arap_lambda, lm_lambda=lm_lambda,
+                             corr_weights=corr_weights, unit_edge_weights=unit)[0]
+
+
+class NonRigidICP(torch.nn.Module):
+    """vision3d/layers/nonrigid_icp.py:157-207: the Gauss-Newton solver as a layer (inference only)"""
+
+    def __init__(self, corr_lambda=1.0, arap_lambda=1.0, lm_lambda=0.01, num_iterations=5):
+        super().__init__()
+        self.corr_lambda, self.arap_lambda, self.lm_lambda, self.num_iterations = corr_lambda, arap_lambda, lm_lambda, num_iterations
+
+    def forward(self, src_nodes, src_corr_points, tgt_corr_points, anchor_indices, anchor_weights, edge_indices, corr_weights=None,
+                edge_weights=None):
+        return non_rigid_icp_gauss_newton(src_nodes, src_corr_points, tgt_corr_points, anchor_indices, anchor_weights, edge_indices,
+                                          corr_weights=corr_weights, edge_weights=edge_weights, corr_lambda=self.corr_lambda,
+                                          arap_lambda=self.arap_lambda, lm_lambda=self.lm_lambda, num_iterations=self.num_iterations)
+
+    def extra_repr(self):
+        return ", ".join(["corr_lambda=%g" % self.corr_lambda, "arap_lambda=%g" % self.arap_lambda, "lm_lambda=%g" % self.lm_lambda,
+                          "num_iterations=%d" % self.num_iterations])
+
+
 # ------------------------------------------------------------------------------------------------ after Pipeline on a 4DMatch pair
 class NonRigidRegistration:
     """graph -> solver -> warp of the whole source cloud, for one pair or a list of pairs in one call.
@@ -304,9 +464,17 @@ class NonRigidRegistration:
     graph["status"] is the pair's device status word (a 0-d int32 DEVICE tensor, not read here: 0, or the bits include/diffreg_hip.h lists --
     8: a non-finite coordinate left points without their full anchors; 4: an index out of range was treated as absent)."""
 
-    def __init__(self, num_anchors=6, node_coverage=0.08, num_iterations=500, lr=0.5, gamma=0.999, weights=(1.0, 0.1, 0.1), eps=1e-6):
+    def __init__(self, num_anchors=6, node_coverage=0.08, num_iterations=None, lr=0.5, gamma=0.999, weights=(1.0, 0.1, 0.1), eps=1e-6,
+                 solver="adam", corr_lambda=1.0, arap_lambda=0.1, lm_lambda=0.1):
+        """solver="gauss_newton": dr_nicp_gn_f32 with the three lambdas in place of the Adam solver; __call__ then takes match_weights,
+        per-match weights handed on as corr_weights.  num_iterations=None is each solver's reference default: 500 (Adam), 5 (Gauss-Newton)."""
+        if solver not in ("adam", "gauss_newton"):
+            raise ValueError("solver must be 'adam' or 'gauss_newton' (got %r)" % (solver,))
+        if num_iterations is None:
+            num_iterations = 500 if solver == "adam" else 5
         self.num_anchors, self.node_coverage, self.num_iterations = _check_k(num_anchors), float(node_coverage), int(num_iterations)
         self.lr, self.gamma, self.weights, self.eps = float(lr), float(gamma), tuple(weights), float(eps)
+        self.solver, self.corr_lambda, self.arap_lambda, self.lm_lambda = solver, float(corr_lambda), float(arap_lambda), float(lm_lambda)
 
     def subsample_nodes(self, src_list):
         """per-pair node sets: one grid-subsample call over the stacked clouds, one host read of the P lengths"""
@@ -319,8 +487,10 @@ class NonRigidRegistration:
             lo += n
         return out
 
-    def __call__(self, src_points, tgt_points, matches, nodes=None):
+    def __call__(self, src_points, tgt_points, matches, nodes=None, match_weights=None):
         single = isinstance(src_points, torch.Tensor)
+        if match_weights is not None and self.solver != "gauss_newton":
+            raise ValueError("match_weights are the Gauss-Newton solver's corr_weights: construct with solver='gauss_newton'")
         src_l = [src_points] if single else list(src_points)
         tgt_l = [tgt_points] if single else list(tgt_points)
         mat_l = [matches] if single else list(matches)
@@ -351,7 +521,17 @@ class NonRigidRegistration:
         tgt_corr = torch.cat([t[m[:, 1]] for t, m in zip(tgt_l, mat_l)])
         pb = Problem(nod, src_corr, tgt_corr, g["anchor_indices"][rows].contiguous(), g["anchor_weights"][rows].contiguous(), g["edge_indices"],
                      g["edge_weights"], node_lengths=ml, corr_lengths=cl, edge_lengths=g["edge_lengths"])
-        T, _, _, st_solver = nicp_adam(pb, num_iterations=self.num_iterations, lr=self.lr, gamma=self.gamma, weights=self.weights)
+        if self.solver == "gauss_newton":
+            cw = None
+            if match_weights is not None:
+                cw_l = [match_weights] if single else list(match_weights)
+                if len(cw_l) != len(mat_l) or any(w.shape[0] != m.shape[0] for w, m in zip(cw_l, mat_l)):
+                    raise ValueError("one weight per match")
+                cw = torch.cat([_f32("match_weights", w, ()) for w in cw_l])
+            T, st_solver = nicp_gauss_newton(pb, num_iterations=self.num_iterations, corr_lambda=self.corr_lambda,
+                                             arap_lambda=self.arap_lambda, lm_lambda=self.lm_lambda, corr_weights=cw)
+        else:
+            T, _, _, st_solver = nicp_adam(pb, num_iterations=self.num_iterations, lr=self.lr, gamma=self.gamma, weights=self.weights)
         warped, st_warp = ed_warp(src, nod, T, g["anchor_indices"], g["anchor_weights"], point_lengths=pl, node_lengths=ml, eps=self.eps)
         res, p0, m0, e0 = [], 0, 0, 0
         for p, m, e in zip(pl, ml, g["edge_lengths"]):

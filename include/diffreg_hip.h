@@ -75,7 +75,9 @@ extern "C" {
  *   0.7.0, fourteenth set (same rule)  non-rigid ICP on an embedded deformation graph: dr_ed_graph_f32, dr_ed_warp_f32, dr_nicp_cost_grad_f32,
  *          dr_nicp_adam_f32 with their size queries (new entries only; nothing older changed).
  *   0.7.0, fifteenth set (same rule)  the 3D / 4D dataset item: dr_item3d_prepare_f32 with the new struct dr_item3d_args,
- *          dr_radius_pairs_ragged_f32 with dr_radius_pairs_ragged_workspace_bytes (new entries only; dr_radius_pairs_f32 is unchanged). */
+ *          dr_radius_pairs_ragged_f32 with dr_radius_pairs_ragged_workspace_bytes (new entries only; dr_radius_pairs_f32 is unchanged).
+ *   0.7.0, sixteenth set (same rule)  Gauss-Newton non-rigid ICP: dr_nicp_gn_f32, dr_nicp_gn_normal_f32 with dr_nicp_gn_workspace_bytes and the
+ *          new struct dr_nicp_gn_options, dr_spd_solve_f64 (new entries only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1733,6 +1735,66 @@ size_t dr_radius_pairs_ragged_workspace_bytes(int P, int ns, int nt);
 int dr_radius_pairs_ragged_f32(int P, int ns, int nt, const float* src, const int32_t* s_offsets, const float* tgt, const int32_t* t_offsets,
                                const float* transforms, float radius, const int64_t* c_offsets, long long capacity, int64_t* out_src,
                                int64_t* out_tgt, int32_t* counts, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, sixteenth set (detected by symbol like the fourth to fifteenth sets): Gauss-Newton non-rigid ICP on the embedded
+ * deformation graph of the fourteenth set, the solver vision3d wraps as the layer NonRigidICP.  2D-3D vision3d/layers/nonrigid_icp.py:18-154,
+ * vision3d/ops/so3.py:107-133 and :389-406, vision3d/ops/numeric.py:7-9.  csrc/nonrigid_gn.hip, indices in csrc/nonrigid_gn_index.h; DESIGN 5z.
+ *
+ * The entries keep the fourteenth set's conventions: dr_nicp_problem (with edge_weights == NULL allowed here: weight 1, :60-61), ragged over P
+ * pairs through int32 DEVICE offset arrays, PAIR-LOCAL int64 node indices, asynchronous on `stream`, nothing allocated, nothing read back, no
+ * floating-point atomic: two runs are bit-equal and every entry can be captured on one stream (the launch sequence depends only on
+ * problem->max_nodes / n_max and num_iterations).  status [P] int32 receives per pair 0 or a sum of: 1, more nodes than max_nodes; 2, the
+ * pair's offsets are not 0 <= lo <= hi <= total (a pair with bit 1 or 2 is neither read nor computed, its output rows are not written); 4, an
+ * anchor outside [-1, M) or an edge endpoint outside [0, M) was met and treated as absent; 32, a pivot of the factorisation was not finite or not
+ * > 0 (possible with lm_lambda <= 0 and a node that no row constrains).  P = 0 is a no-op; a negative size, a K out of 1 .. 8, max_nodes > 1024,
+ * or a NULL pointer that a non-empty array needs is DR_EINVAL, a product of sizes beyond 2^31 - 1 or P > 65535 DR_ENOSUP, a missing or short
+ * workspace DR_EWORKSPACE (16-byte aligned, else DR_EINVAL): all reported before the first launch, with every output untouched.
+ *
+ * The unknowns of a pair of M nodes are ordered as the reference's permute(1, 3, 0, 2, 4) orders its Jacobian's columns (:105): axis-angle
+ * increments first (3 n + d), then translation increments (3 M + 3 n + d).  One iteration (:93-150), at rotations R_n and translations t_n:
+ *   correspondence rows (:98-112): residual corr_lambda (warp(p_c) - q_c), warp = dr_ed_warp_f32's apply_deformation with its sum + 1e-6
+ *     normalisation; blocks -corr_lambda w [R_n (p_c - g_n)]x (rotation) and corr_lambda w I (translation) for the columns with anchor != -1
+ *     and anchor weight > 0 (:71), w = the RAW anchor weight, times sqrt(corr_weights[c]) when corr_weights is given (:79) -- which enters the
+ *     blocks only, never the residual, as in the reference.  A row that names one node in two such columns keeps the LATER column's block (the
+ *     reference's indexed assignment keeps one write, unspecified on a GPU).
+ *   ARAP rows (:117-137; none when arap_lambda <= 0): per edge (u, v), u != v (self edges dropped :54; (u, v) and (v, u) are two rows),
+ *     s = arap_lambda sqrt(edge_weight): residual s (R_u (g_v - g_u) + t_u + g_u - g_v - t_v); blocks -s [R_u (g_v - g_u)]x and s I at u,
+ *     -s I at v's translation.
+ *   solve (:140-144): A = J^T J + lm_lambda I, b = -J^T r, A x = b.  J is never built: the workgroup of node n gathers n's 6 x 6 blocks against
+ *     each partner node through the node-major lists of the fourteenth set's set-up pass (the same device code) in float64, in list order, and
+ *     writes row block n of the dense A [6 M, 6 M] in the workspace (both triangles).  A is factored by a blocked right-looking Cholesky
+ *     (64-wide blocks) and solved by forward and back substitution, all float64.
+ *   update (:146-150): R_n <- exp(phi_n) R_n by Rodrigues' formula with omega = phi / max(|phi|, 1e-6) (so a zero increment is the identity),
+ *     t_n <- t_n + dt_n, in float64 on the float32 state, rounded once.
+ *
+ * dr_nicp_gn_f32: options->num_iterations iterations.  state: NULL, or the fourteenth set's struct of DEVICE pointers, of which only rotations
+ *   and translations are used (each may be NULL): non-NULL members are the state the iterations work on and hold the final state; with
+ *   resume != 0 the run starts from them (both required), otherwise from identity rotations and zero translations.  transforms [n_nodes, 4, 4]
+ *   is written on every call; num_iterations == 0 returns the starting state.  A pair that gets status bit 32 stops there: its state stays as it
+ *   was before the failing iteration, its transforms are written from that state, nothing non-finite is written, and the other pairs are not
+ *   affected.  max_nodes <= 1024: the capacity is bounded by the workspace, P (6 max_nodes)^2 doubles dominate it (75 MB per pair at 512).
+ * dr_nicp_gn_normal_f32: A [P, 6 max_nodes, 6 max_nodes] and b [P, 6 max_nodes] float64 (row-major, pair p's system in the leading 6 M_p
+ *   rows / columns of its slot, the rest zero) of ONE iteration at the given rotations [n_nodes, 3, 3] / translations [n_nodes, 3], lm_lambda
+ *   added; num_iterations is ignored.
+ *   Workspace of both: dr_nicp_gn_workspace_bytes(P, n_corr, n_nodes, n_edges, K, max_nodes); the size query and the entries share one carve.
+ * dr_spd_solve_f64: P symmetric positive definite systems in one call, torch.linalg.solve's role at :144.  System p is the leading n[p] x n[p]
+ *   corner of slot p of A [P, n_max, n_max] (row-major; only the LOWER triangle is read) and the first n[p] entries of bx [P, n_max]; n is an
+ *   int32 DEVICE array.  The lower triangle receives the Cholesky factor L (A = L L^T), bx the solution; the strict upper triangle and
+ *   everything outside the leading corner are neither read nor written.  0 <= n_max <= 6144.  status [P]: 0; 2, n[p] outside [0, n_max]
+ *   (nothing is touched); 32, a pivot was not finite or not > 0 (the slot's lower triangle is partly overwritten, bx is untouched).  No
+ *   workspace. */
+typedef struct dr_nicp_gn_options {
+    int num_iterations;                                   /* 5 */
+    double corr_lambda, arap_lambda, lm_lambda;           /* 1.0, 0.1, 0.1 (the function); 1.0, 1.0, 0.01 (the layer) */
+} dr_nicp_gn_options;
+size_t dr_nicp_gn_workspace_bytes(int P, int n_corr, int n_nodes, int n_edges, int K, int max_nodes);
+int dr_nicp_gn_f32(const dr_nicp_problem* problem, const dr_nicp_gn_options* options, const float* corr_weights, const dr_nicp_state* state,
+                   int resume, float* transforms, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int dr_nicp_gn_normal_f32(const dr_nicp_problem* problem, const dr_nicp_gn_options* options, const float* corr_weights, const float* rotations,
+                          const float* translations, double* A, double* b, int32_t* status, void* workspace, size_t workspace_bytes,
+                          void* stream);
+int dr_spd_solve_f64(int P, int n_max, const int32_t* n, double* A, double* bx, int32_t* status, void* stream);
 
 #ifdef __cplusplus
 }
