@@ -146,6 +146,7 @@ void dr_debug_attention_split(int on) { attention_force_split(on); }
 int dr_debug_attention_last_form(void) { return attention_last_form(); }
 int dr_debug_procrustes_last_form(void) { return procrustes_last_form(); }
 int dr_debug_pgemm_acc_forms(int clear) { return pgemm_acc_forms(clear != 0); }
+void dr_debug_fps_force_streaming(int on) { fps_force_streaming(on); }
 
 int dr_vol_pe_f32(int rows, int rows_per_pair, int C, const float* xyz, const float* R, const float* t, float origin_x,
                   float origin_y, float origin_z, float voxel, const float* freq, float* cos_out, float* sin_out,

@@ -511,6 +511,16 @@ SIGNATURES.update({
 })
 
 
+SIGNATURES.update({
+    # added after ABI 0.7.0, seventeenth set: furthest-point sampling (csrc/fps.hip); the debug setter forces the streaming instantiation
+    "dr_fps_onchip_capacity": (c_int, []),
+    "dr_fps_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dr_fps_nodes_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_float, c_int, c_int] + [c_void_p] * 6 + [c_size_t, c_void_p]),
+    "dr_fps_batch_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_size_t, c_void_p]),
+    "dr_debug_fps_force_streaming": (None, [c_int]),
+})
+
+
 def _bind(table):
     for name, (res, args) in table.items():
         if not hasattr(_lib, name):          # the sets added under one ABI number are detected by symbol

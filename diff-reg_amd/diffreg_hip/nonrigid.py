@@ -13,7 +13,11 @@ have no place for it, discard it, and NonRigidRegistration hands it out as graph
 
 The Gauss-Newton solver (sixteenth set, csrc/nonrigid_gn.hip) sits next to the Adam one: non_rigid_icp_gauss_newton and the layer
 NonRigidICP keep the signatures of vision3d/layers/nonrigid_icp.py:18-207, nicp_gauss_newton / nicp_gn_normal / spd_solve are the ragged entries,
-and NonRigidRegistration(solver="gauss_newton") selects it (the default stays Adam).  It is inference only: an input that requires grad raises."""
+and NonRigidRegistration(solver="gauss_newton") selects it (the default stays Adam).  It is inference only: an input that requires grad raises.
+
+Furthest-point sampling (seventeenth set, csrc/fps.hip) is where the reference's nodes come from: furthest_point_sample_nodes and
+furthest_point_sample keep the signatures of vision3d/array_ops/furthest_point_sample.py:11-19 and vision3d/ops/furthest_point_sample.py:12-49,
+fps_nodes is the ragged entry, and NonRigidRegistration(node_sampler="fps") samples its nodes with it (the default stays the grid subsample)."""
 import ctypes
 
 import torch
@@ -387,6 +391,98 @@ def spd_solve(A, b, sizes=None):
     return status
 
 
+# ------------------------------------------------------------------------------------------------ furthest-point sampling (seventeenth set)
+FPS_CAP_REACHED = 64       # status bit of fps_nodes: sample_cap nodes were taken before the stop rule was met
+FPS_START_NONFINITE = 128  # status bit of fps_nodes: point 0 of the cloud is not finite, the cloud yields 0 nodes
+
+
+def _device_tensor(name, t):
+    """the new public names refuse a host tensor: its data pointer would be handed to the kernel as a device address"""
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+        raise TypeError("%s must be a tensor on the GPU (got %s)" % (name, getattr(t, "device", type(t))))
+
+
+def fps_onchip_capacity():
+    """the largest cloud whose coordinates and running distances stay in registers; a larger one takes the streaming form of the same kernel"""
+    return int(_raw.dr_fps_onchip_capacity())
+
+
+def fps_nodes(points, min_distance=None, num_samples=None, lengths=None, sample_cap=None, return_distance=False, out=None):
+    """dr_fps_nodes_f32 for P clouds: points [n, 3] stacked, lengths a host list (None: one cloud).  min_distance / num_samples: the stop rules of
+    vision3d's array_ops.furthest_point_sample (None: absent; at least one is needed, and min_distance <= 0 counts as absent).  sample_cap: the
+    row length of the outputs (default: num_samples, else the largest cloud).  Reads nothing back.  -> dict(indices [P, sample_cap] int64
+    cloud-local, -1 beyond the count; points [P, sample_cap, 3]; distances [P, sample_cap] when return_distance: the running-minimum distance
+    at which each node was taken; counts [P] int32; status [P] int32; offsets, workspace).  out: the dict of an earlier call of the same
+    shapes to write into, so that a captured graph allocates and uploads nothing."""
+    points = _f32("points", points, (3,))
+    lens = _lengths_of(lengths, points.shape[0])
+    md = -1.0 if min_distance is None else float(min_distance)
+    ns = -1 if num_samples is None else int(num_samples)
+    if num_samples is not None and ns < 1:
+        raise ValueError("num_samples must be positive (got %s)" % (num_samples,))
+    if not md > 0 and ns <= 0:
+        raise ValueError("furthest-point sampling needs min_distance > 0 or num_samples: with neither the reference's loop cannot stop")
+    P, n, mx = len(lens), points.shape[0], max(lens, default=0)
+    cap = int(sample_cap) if sample_cap is not None else (ns if ns > 0 else max(mx, 1))
+    if cap < 1:
+        raise ValueError("sample_cap must be positive (got %s)" % (sample_cap,))
+    _device_tensor("points", points)
+    lib.ensure_init()
+    dev = points.device
+    wsb = _raw.dr_fps_workspace_bytes(P, n, mx)
+    if out is None:
+        out = dict(indices=torch.empty(P, cap, dtype=torch.int64, device=dev), points=torch.empty(P, cap, 3, device=dev),
+                   counts=torch.empty(P, dtype=torch.int32, device=dev), status=torch.empty(P, dtype=torch.int32, device=dev),
+                   offsets=_offsets(lens, dev)[0], workspace=_ws(wsb, dev), lengths=lens)
+        if return_distance:
+            out["distances"] = torch.empty(P, cap, device=dev)
+    elif tuple(out["indices"].shape) != (P, cap) or out["lengths"] != lens or out["workspace"].numel() < wsb or (return_distance and
+                                                                                                               "distances" not in out):
+        raise ValueError("out must be the result of an earlier call with the same lengths, sample_cap and return_distance")
+    check(_raw.dr_fps_nodes_f32(P, n, mx, ptr(points) if n else None, ptr(out["offsets"]), md, ns, cap, ptr(out["indices"]) if P else None,
+                                ptr(out["points"]) if P else None, ptr(out["distances"]) if (P and return_distance) else None,
+                                ptr(out["counts"]) if P else None, ptr(out["status"]) if P else None, ptr(out["workspace"]), wsb,
+                                stream_of(points)))
+    return out
+
+
+def furthest_point_sample_nodes(points, min_distance=None, num_samples=None):
+    """vision3d/array_ops/furthest_point_sample.py:11-19 for one cloud on the device -> int64 indices [count] (one host read: the count).
+    Ties go to the lowest index and a non-finite point is never taken (include/diffreg_hip.h); the status word is discarded (fps_nodes
+    returns it)."""
+    r = fps_nodes(points, min_distance=min_distance, num_samples=num_samples)
+    return r["indices"][0, :int(r["counts"][0])].clone()
+
+
+def furthest_point_sample(points, num_samples, *input_tensors, gather_points=True, transposed=False):
+    """vision3d/ops/furthest_point_sample.py:12-49: points [B, N, 3] ([B, 3, N] when transposed), features [B, C, N] -> indices [B, M] when
+    not gather_points, else (sampled_points [B, M, 3] or [B, 3, M], *sampled features [B, C, M]), as the reference returns them."""
+    if not isinstance(points, torch.Tensor) or points.dtype != torch.float32 or points.dim() != 3:
+        raise TypeError("points must be a float32 tensor [B, N, 3]")
+    _device_tensor("points", points)         # input_tensors only pass through torch.gather, which checks its own devices
+    if transposed:
+        points = points.transpose(1, 2)
+    points = points.contiguous()
+    if points.shape[2] != 3:
+        raise ValueError("points must be [B, N, 3] (got %s)" % (tuple(points.shape),))
+    B, N, M = points.shape[0], points.shape[1], int(num_samples)
+    if M < 0 or (N == 0 and M > 0 and B > 0):
+        raise ValueError("num_samples must not be negative, and an empty cloud has no sample")
+    lib.ensure_init()
+    indices = torch.zeros(B, M, dtype=torch.int64, device=points.device)
+    if B and M:
+        wsb = _raw.dr_fps_workspace_bytes(B, B * N, N)
+        ws = _ws(wsb, points.device)
+        check(_raw.dr_fps_batch_f32(B, N, M, ptr(points), ptr(indices), ptr(ws), wsb, stream_of(points)))
+    if not gather_points:
+        return indices
+    sampled = torch.gather(points, 1, indices[:, :, None].expand(B, M, 3))
+    if transposed:
+        sampled = sampled.transpose(1, 2).contiguous()
+    outs = [torch.gather(t, 2, indices[:, None, :].expand(B, t.shape[1], M)) for t in input_tensors]
+    return (sampled, *outs)
+
+
 # ------------------------------------------------------------------------------------------------ vision3d's three names
 def build_euclidean_deformation_graph(points, nodes, num_anchors, node_coverage, return_point_anchor=True, return_node_graph=True,
                                       return_distance=False, return_adjacent_matrix=False, eps=1e-6):
@@ -465,11 +561,21 @@ class NonRigidRegistration:
     8: a non-finite coordinate left points without their full anchors; 4: an index out of range was treated as absent)."""
 
     def __init__(self, num_anchors=6, node_coverage=0.08, num_iterations=None, lr=0.5, gamma=0.999, weights=(1.0, 0.1, 0.1), eps=1e-6,
-                 solver="adam", corr_lambda=1.0, arap_lambda=0.1, lm_lambda=0.1):
+                 solver="adam", corr_lambda=1.0, arap_lambda=0.1, lm_lambda=0.1, node_sampler="grid", node_min_distance=None):
         """solver="gauss_newton": dr_nicp_gn_f32 with the three lambdas in place of the Adam solver; __call__ then takes match_weights,
-        per-match weights handed on as corr_weights.  num_iterations=None is each solver's reference default: 500 (Adam), 5 (Gauss-Newton)."""
+        per-match weights handed on as corr_weights.  num_iterations=None is each solver's reference default: 500 (Adam), 5 (Gauss-Newton).
+        node_sampler: where the nodes come from when __call__ is given none -- "grid" (the default): grid barycentres with cell =
+        node_coverage; "fps": furthest-point sampling as vision3d's array_ops.furthest_point_sample, with min_distance = node_min_distance
+        (None: node_coverage) and node_capacity() as the cap: the nodes are points of the cloud, at least min_distance apart, never more than
+        the solver holds; a pair cut by the cap carries FPS_CAP_REACHED in graph["status"]."""
         if solver not in ("adam", "gauss_newton"):
             raise ValueError("solver must be 'adam' or 'gauss_newton' (got %r)" % (solver,))
+        if node_sampler not in ("grid", "fps"):
+            raise ValueError("node_sampler must be 'grid' or 'fps' (got %r)" % (node_sampler,))
+        self.node_sampler = node_sampler
+        self.node_min_distance = float(node_coverage if node_min_distance is None else node_min_distance)
+        if node_sampler == "fps" and not self.node_min_distance > 0:
+            raise ValueError("node_min_distance must be positive")
         if num_iterations is None:
             num_iterations = 500 if solver == "adam" else 5
         self.num_anchors, self.node_coverage, self.num_iterations = _check_k(num_anchors), float(node_coverage), int(num_iterations)
@@ -486,6 +592,13 @@ class NonRigidRegistration:
             out.append(pts[lo:lo + n].contiguous())
             lo += n
         return out
+
+    def sample_nodes_fps(self, src_list):
+        """per-pair node sets by furthest-point sampling: one ragged call over the stacked clouds, one host read of the P counts.
+        -> (list of [count, 3] node tensors, status [P] on the device)"""
+        r = fps_nodes(torch.cat(src_list), min_distance=self.node_min_distance, lengths=[s.shape[0] for s in src_list],
+                      sample_cap=node_capacity())
+        return [r["points"][p, :c].contiguous() for p, c in enumerate(r["counts"].tolist())], r["status"]
 
     def __call__(self, src_points, tgt_points, matches, nodes=None, match_weights=None):
         single = isinstance(src_points, torch.Tensor)
@@ -504,7 +617,10 @@ class NonRigidRegistration:
             nod_l = [_f32("nodes", g, (3,)) for g in nod_l]
             if max(g.shape[0] for g in nod_l) > node_capacity():
                 raise ValueError("a pair has %d nodes; the solver holds at most %d" % (max(g.shape[0] for g in nod_l), node_capacity()))
-        else:
+        st_nodes = None
+        if nod_l is None and self.node_sampler == "fps":
+            nod_l, st_nodes = self.sample_nodes_fps(src_l)       # at most node_capacity() nodes per pair, by the call's sample_cap
+        elif nod_l is None:
             nod_l = self.subsample_nodes(src_l)      # a launch: only now is the node count known, so the capacity is checked here,
             if max(g.shape[0] for g in nod_l) > node_capacity():                     # before the graph and the solver are launched
                 raise ValueError("the grid subsample gave a pair %d nodes; the solver holds at most %d: raise node_coverage or pass nodes"
@@ -533,11 +649,14 @@ class NonRigidRegistration:
         else:
             T, _, _, st_solver = nicp_adam(pb, num_iterations=self.num_iterations, lr=self.lr, gamma=self.gamma, weights=self.weights)
         warped, st_warp = ed_warp(src, nod, T, g["anchor_indices"], g["anchor_weights"], point_lengths=pl, node_lengths=ml, eps=self.eps)
+        st_all = g["status"] | st_solver | st_warp
+        if st_nodes is not None:
+            st_all = st_all | (st_nodes & (FPS_CAP_REACHED | FPS_START_NONFINITE))   # the sampler's 1 / 2 / 8 mean other things than this word's
         res, p0, m0, e0 = [], 0, 0, 0
         for p, m, e in zip(pl, ml, g["edge_lengths"]):
             graph = dict(nodes=nod[m0:m0 + m], anchor_indices=g["anchor_indices"][p0:p0 + p], anchor_weights=g["anchor_weights"][p0:p0 + p],
                          edge_indices=g["edge_indices"][e0:e0 + e], edge_weights=g["edge_weights"][e0:e0 + e],
-                         status=(g["status"] | st_solver | st_warp)[len(res)])
+                         status=st_all[len(res)])
             res.append((warped[p0:p0 + p], T[m0:m0 + m], graph))
             p0, m0, e0 = p0 + p, m0 + m, e0 + e
         return res[0] if single else ([r[0] for r in res], [r[1] for r in res], [r[2] for r in res])

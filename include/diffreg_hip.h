@@ -77,7 +77,9 @@ extern "C" {
  *   0.7.0, fifteenth set (same rule)  the 3D / 4D dataset item: dr_item3d_prepare_f32 with the new struct dr_item3d_args,
  *          dr_radius_pairs_ragged_f32 with dr_radius_pairs_ragged_workspace_bytes (new entries only; dr_radius_pairs_f32 is unchanged).
  *   0.7.0, sixteenth set (same rule)  Gauss-Newton non-rigid ICP: dr_nicp_gn_f32, dr_nicp_gn_normal_f32 with dr_nicp_gn_workspace_bytes and the
- *          new struct dr_nicp_gn_options, dr_spd_solve_f64 (new entries only; nothing older changed). */
+ *          new struct dr_nicp_gn_options, dr_spd_solve_f64 (new entries only; nothing older changed).
+ *   0.7.0, seventeenth set (same rule)  furthest-point sampling: dr_fps_nodes_f32, dr_fps_batch_f32 with dr_fps_workspace_bytes and
+ *          dr_fps_onchip_capacity (new entries only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1576,7 +1578,9 @@ int dr_overlap_2d3d_f64(int H, int W, int N, const float* depth, double scaling_
  * status [P] int32 receives per pair 0 or a sum of: 1, the pair has points but no node (dr_ed_graph_f32) or more nodes than max_nodes;
  * 2, the pair's offsets are not 0 <= lo <= hi <= total; 4, an anchor outside [-1, M) or an edge endpoint outside [0, M) was met and treated as
  * absent; 8 (dr_ed_graph_f32), a NaN or Inf coordinate of a point or a node left a point with fewer than min(K, M) anchors; 16
- * (dr_nicp_adam_f32), a negative resumed step count was taken as 0.  A pair with bit 1 or 2 is neither read nor computed: its rows of the
+ * (dr_nicp_adam_f32), a negative resumed step count was taken as 0; 32 is the sixteenth set's (a failed pivot); 64 and 128 are the seventeenth
+ * set's (dr_fps_nodes_f32: sample_cap reached before the stop rule; point 0 of the cloud is not finite), the only two bits of that set's status
+ * which NonRigidRegistration ORs into the same word (its 1, 2 and 8 mean other things there and are masked off).  A pair with bit 1 or 2 is neither read nor computed: its rows of the
  * outputs are not written.  max_nodes is an upper bound of every pair's node count known to the HOST.  1 <= K <= 8.  P = 0 is a no-op; a negative size, a K out of range or a NULL pointer that a non-empty array needs is DR_EINVAL, a
  * product of sizes beyond 2^31 - 1 DR_ENOSUP, a missing or short workspace DR_EWORKSPACE (16-byte aligned, else DR_EINVAL): all reported before
  * the first launch, with every output untouched.
@@ -1795,6 +1799,60 @@ int dr_nicp_gn_normal_f32(const dr_nicp_problem* problem, const dr_nicp_gn_optio
                           const float* translations, double* A, double* b, int32_t* status, void* workspace, size_t workspace_bytes,
                           void* stream);
 int dr_spd_solve_f64(int P, int n_max, const int32_t* n, double* A, double* bx, int32_t* status, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, seventeenth set (detected by symbol like the fourth to sixteenth sets): furthest-point sampling, where the nodes of
+ * the fourteenth set's deformation graph come from in the reference.  2D-3D vision3d/csrc/cpu/node_sampling/node_sampling.cpp:10-78 and its
+ * numpy restatement vision3d/array_ops/furthest_point_sample.py:22-66 (node form); vision3d/csrc/cuda/furthest_point_sample/
+ * furthest_point_sample_cuda.cuh:29-88 behind vision3d/ops/furthest_point_sample.py:12-49 (batch form).  csrc/fps.hip, indices in
+ * csrc/fps_index.h; DESIGN 5za.
+ *
+ * Conventions of the fourteenth set: ragged over P clouds through an int32 DEVICE array of P + 1 offsets (node form), asynchronous on `stream`
+ * (a hipStream_t), nothing allocated, nothing read back, NO atomic of any kind: two runs are bit-equal and both entries can be captured on one
+ * stream.  One workgroup owns one cloud for all its iterations and clouds run side by side; no workgroup waits for another.  A cloud of at most
+ * dr_fps_onchip_capacity() points keeps its coordinates and running distances in registers; a larger one takes the streaming instantiation of
+ * the same kernel (running distances in the workspace, coordinates re-read each iteration), whose result is the same entry for entry.  P = 0 is
+ * a no-op; a negative size, max_points > n_points, sample_cap < 1 or a NULL pointer that a non-empty array needs is DR_EINVAL, more than
+ * 65 535 clouds or 2^31 / 3 stacked points DR_ENOSUP, a missing or short workspace DR_EWORKSPACE (16-byte aligned, else DR_EINVAL): all reported
+ * before the first launch, with every output untouched.
+ *
+ * Arithmetic: float32, operation by operation in the reference's order, never contracted into an FMA.  Every selection takes the candidate with
+ * the largest running distance; among EQUAL distances the LOWEST index wins, whatever lane, wave or instantiation holds it.  (Stated
+ * difference: the reference resolves a tie by the scan order of its swap-popped candidate array (C++), of its shrinking list (numpy), or by
+ * thread stride and tree order (CUDA).  The fixture is screened so that no selection of it is a tie.)  A point with a NaN or Inf coordinate
+ * is never selected and never enters the stop test: its distance key is -inf.
+ *
+ * dr_fps_nodes_f32: the node form.  d = sqrtf((dx dx + dy dy) + dz dz) with sq_norm's order (cloud.h:46) and a correctly rounded square root;
+ *   the running minimum starts at +inf; node 0 is point 0; each further node is the candidate with the largest running minimum that is
+ *   strictly > 0; the loop stops when num_samples > 0 nodes are taken (tested BEFORE the scan, node_sampling.cpp:44), when that maximum is
+ *   < min_distance (:67), or when no candidate is left -- every remaining running minimum is 0: the cloud is used up, e.g. num_samples >= the
+ *   number of distinct points (the reference indexes out of range there when min_distance <= 0).  min_distance <= 0 (or NaN) together with
+ *   num_samples <= 0 is therefore DR_EINVAL: neither rule could stop the reference.  "None" of the reference is min_distance = -1 /
+ *   num_samples = -1 (array_ops/furthest_point_sample.py:14-17).  The reference drops a point closer than min_distance to a node from its
+ *   candidate list (:60-61); such a point could win only a selection at which the loop stops, so this changes nothing but the reference's tie
+ *   order, and the device keeps no list.
+ *   max_points: an upper bound of every cloud's point count known to the HOST; it decides whether the streaming instantiation is launched.
+ *   out_indices [P, sample_cap] int64, CLOUD-LOCAL, -1 beyond the count; out_points (or NULL) [P, sample_cap, 3] = the nodes' coordinates, bit
+ *   for bit, 0 beyond the count; out_distances (or NULL) [P, sample_cap] = the running-minimum distance at which node k was taken (0 for node
+ *   0; non-increasing in k), 0 beyond the count: one sampling can be cut at any coarser min_distance without running again.  out_counts [P].
+ *   status [P] int32 receives per cloud 0 or a sum of: 1, the cloud has more points than max_points; 2, its offsets are not 0 <= lo <= hi <=
+ *   n_points (with 1 or 2 nothing is read, the count is 0 and the row is -1 / 0); 8, a point with a NaN or Inf coordinate was met and left out;
+ *   64, sample_cap nodes were taken and the next candidate did not meet the stop rule (the loop was cut by sample_cap, not by num_samples or
+ *   min_distance); 128, point 0 is not finite: the cloud yields 0 nodes.  An empty cloud yields count 0 and status 0.
+ *   Workspace: dr_fps_workspace_bytes(P, n_points, max_points): 0 when max_points <= dr_fps_onchip_capacity(), else one float per stacked point.
+ * dr_fps_batch_f32: the batch form on points [B, N, 3].  d = (dx dx + dy dy) + dz dz (.cuh:64); the running minimum starts at 1e10
+ *   (ops/furthest_point_sample.py:34); index 0 first, then num_samples - 1 times the candidate with the largest running minimum strictly > -1
+ *   (:55-70), and index 0 when there is none; there is no stop and no status.  num_samples > N repeats indices as the reference's kernel does:
+ *   once every running minimum is 0 the lowest index wins each time.  A non-finite point 0 is still index 0 (it updates no distance).
+ *   out_indices [B, num_samples] int64.  N == 0 with num_samples > 0 is DR_EINVAL (the reference reads point 0).  Workspace:
+ *   dr_fps_workspace_bytes(B, B N, N). */
+int dr_fps_onchip_capacity(void);
+size_t dr_fps_workspace_bytes(int P, int n_points, int max_points);
+int dr_fps_nodes_f32(int P, int n_points, int max_points, const float* points, const int32_t* p_offsets, float min_distance, int num_samples,
+                     int sample_cap, int64_t* out_indices, float* out_points, float* out_distances, int32_t* out_counts, int32_t* status,
+                     void* workspace, size_t workspace_bytes, void* stream);
+int dr_fps_batch_f32(int B, int N, int num_samples, const float* points, int64_t* out_indices, void* workspace, size_t workspace_bytes,
+                     void* stream);
 
 #ifdef __cplusplus
 }

@@ -96,6 +96,9 @@ void dr_debug_gemm_rows_tile(int c);
  * two k-groups of waves reduced through LDS when K >= 1024; the 128 x 128 tile is never chosen by it), 0 / 1 / 2 force 64 x 64 with 4 waves /
  * 128 x 128 with 4 waves / 64 x 64 with 8 waves and the k split; any other value makes every launch DR_EINVAL */
 void dr_debug_gemm_rows_f32_tile(int c);
+/* furthest-point sampling (dr_fps_nodes_f32, dr_fps_batch_f32): on != 0 makes every cloud take the streaming instantiation, whatever its
+ * size, and dr_fps_workspace_bytes size the workspace for it; 0 restores the rule (on chip up to dr_fps_onchip_capacity() points) */
+void dr_debug_fps_force_streaming(int on);
 /* n dependent launches of an empty kernel (tools/launch_floor.py) */
 int dr_debug_launch_chain(int n, int workgroups, int threads, void* stream);
 
