@@ -112,6 +112,7 @@ int dr_init(void) {
     if (rc == DR_OK) rc = pgemm_configure();
     if (rc == DR_OK) rc = vit_f32_configure();
     if (rc == DR_OK) rc = nonrigid_configure();
+    if (rc == DR_OK) rc = geo_graph_configure();
     if (rc == DR_OK && !device_status_word()) rc = DR_ELAUNCH;       // resolved here, outside any stream capture (eval2d3d.hip)
     return rc;
 }

@@ -51,6 +51,7 @@ int launch_gemm(const GemmBatch& g, hipStream_t st);
 int gemm_configure();
 int vit_f32_configure();      // vit_f32.hip: the dynamic LDS of the float32 rows GEMM's tiles
 int nonrigid_configure();     // nonrigid.hip: the dynamic LDS of the non-rigid ICP solver up to its node capacity
+int geo_graph_configure();    // geo_graph.hip: the dynamic LDS of the geodesic relaxation up to its on-chip capacity
 void gemm_force_config(int c);
 void fps_force_streaming(int on);   // fps.hip: every cloud takes the streaming instantiation (tests compare the two forms at a small size)
 

@@ -521,6 +521,21 @@ SIGNATURES.update({
 })
 
 
+class GeoGraphOptions(ctypes.Structure):
+    """dr_geo_graph_options"""
+    _fields_ = [("num_neighbors", c_int), ("num_anchors", c_int), ("max_distance", c_float), ("node_coverage", c_float), ("max_degree", c_int),
+                ("onchip_cap_override", c_int)]
+
+
+SIGNATURES.update({
+    # added after ABI 0.7.0, eighteenth set: the geodesic deformation graph of a point cloud (csrc/geo_graph.hip)
+    "dr_geo_graph_onchip_capacity": (c_int, []),
+    "dr_geo_graph_workspace_bytes": (c_size_t, [c_int] * 5),
+    "dr_geo_graph_f32": (c_int, [c_int] * 5 + [c_void_p] * 4 + [ctypes.POINTER(GeoGraphOptions)] + [c_void_p] * 8 + [c_size_t, c_void_p]),
+    "dr_geo_graph_edges": (c_int, [c_int] * 3 + [c_void_p] * 5 + [ctypes.c_longlong] + [c_void_p] * 3),
+})
+
+
 def _bind(table):
     for name, (res, args) in table.items():
         if not hasattr(_lib, name):          # the sets added under one ABI number are detected by symbol

@@ -17,7 +17,11 @@ and NonRigidRegistration(solver="gauss_newton") selects it (the default stays Ad
 
 Furthest-point sampling (seventeenth set, csrc/fps.hip) is where the reference's nodes come from: furthest_point_sample_nodes and
 furthest_point_sample keep the signatures of vision3d/array_ops/furthest_point_sample.py:11-19 and vision3d/ops/furthest_point_sample.py:12-49,
-fps_nodes is the ragged entry, and NonRigidRegistration(node_sampler="fps") samples its nodes with it (the default stays the grid subsample)."""
+fps_nodes is the ragged entry, and NonRigidRegistration(node_sampler="fps") samples its nodes with it (the default stays the grid subsample).
+
+The geodesic graph (eighteenth set, csrc/geo_graph.hip) is the reference's second graph builder: build_deformation_graph_from_point_cloud
+keeps the signature and keys of vision3d/array_ops/deformation.py:443-490, geo_graph / geo_graph_edges are the ragged entries, and
+NonRigidRegistration(graph="geodesic", node_sampler="fps") takes its anchors and node edges from them (the default stays "euclidean")."""
 import ctypes
 
 import torch
@@ -483,6 +487,101 @@ def furthest_point_sample(points, num_samples, *input_tensors, gather_points=Tru
     return (sampled, *outs)
 
 
+# ------------------------------------------------------------------------------------------------ geodesic graph (eighteenth set)
+GEO_MAX_K = 8              # compiled limit of num_neighbors and num_anchors
+GEO_DUPLICATE_NODE = 256   # status bit of geo_graph: two nodes name one point; the cloud's results are only guaranteed to be in range
+GEO_DEGREE_OVERFLOW = 512  # status bit of geo_graph: a point has more than max_degree points closer than max_distance; rows of padding only
+
+
+def geo_graph_onchip_capacity():
+    """the largest cloud whose path lengths stay in LDS while a node relaxes them; a larger one relaxes in the workspace, with the same result"""
+    return int(_raw.dr_geo_graph_onchip_capacity())
+
+
+def geo_graph(points, node_indices, num_neighbors, num_anchors, max_distance, node_coverage, point_lengths=None, node_lengths=None,
+              max_degree=64, onchip_cap_override=0, out=None):
+    """dr_geo_graph_f32 for P clouds: vision3d's build_deformation_graph_from_point_cloud on the device.  points [n, 3] stacked, node_indices [m]
+    int64 CLOUD-LOCAL point indices (as fps_nodes returns them), *_lengths host lists (None: one cloud).  Points closer than max_distance are
+    joined; a node reaches what lies within 2 node_coverage of it ALONG that graph.  -> dict(neighbor_indices [m, Kn] int64 cloud-local node
+    numbers, neighbor_distances, neighbor_weights, anchor_indices [n, Ka], anchor_distances, anchor_weights, status [P]; offsets, workspace).
+    Rows are padded with -1 / 0 / 0; a point no node reaches has a whole row of padding.  max_degree: the slots of a point's adjacency row in
+    the workspace; a cloud with a denser point gets GEO_DEGREE_OVERFLOW and padding only.  Reads nothing back.  out: the dict of an earlier
+    call of the same shapes to write into, so that a captured graph allocates and uploads nothing."""
+    points = _f32("points", points, (3,))
+    if not isinstance(node_indices, torch.Tensor) or node_indices.dtype != torch.int64 or node_indices.dim() != 1:
+        raise TypeError("node_indices must be a 1-d int64 tensor (got %s)" % (getattr(node_indices, "dtype", type(node_indices)),))
+    Kn, Ka = int(num_neighbors), int(num_anchors)
+    if not 1 <= Kn <= GEO_MAX_K or not 1 <= Ka <= GEO_MAX_K:
+        raise ValueError("num_neighbors and num_anchors must be in 1 .. %d (got %s, %s)" % (GEO_MAX_K, num_neighbors, num_anchors))
+    if not (float(max_distance) > 0 and float(node_coverage) > 0):
+        raise ValueError("max_distance and node_coverage must be positive")
+    if not 1 <= int(max_degree) <= 1024 or int(onchip_cap_override) < 0:
+        raise ValueError("max_degree must be in 1 .. 1024 and onchip_cap_override must not be negative")
+    node_indices = node_indices.contiguous()
+    pl, ml = _lengths_of(point_lengths, points.shape[0]), _lengths_of(node_lengths, node_indices.shape[0])
+    if len(pl) != len(ml):
+        raise ValueError("point_lengths and node_lengths must describe the same clouds")
+    _device_tensor("points", points)
+    _device_tensor("node_indices", node_indices)
+    lib.ensure_init()
+    dev, P, n, m, mxp, mxn = points.device, len(pl), points.shape[0], node_indices.shape[0], max(pl, default=0), max(ml, default=0)
+    wsb = _raw.dr_geo_graph_workspace_bytes(P, n, m, mxp, int(max_degree))
+    if out is None:
+        f = lambda r, k: torch.zeros(r, k, device=dev)
+        out = dict(neighbor_indices=torch.full((m, Kn), -1, dtype=torch.int64, device=dev), neighbor_distances=f(m, Kn), neighbor_weights=f(m, Kn),
+                   anchor_indices=torch.full((n, Ka), -1, dtype=torch.int64, device=dev), anchor_distances=f(n, Ka), anchor_weights=f(n, Ka),
+                   status=torch.empty(P, dtype=torch.int32, device=dev), offsets=(_offsets(pl, dev)[0], _offsets(ml, dev)[0]),
+                   workspace=_ws(wsb, dev), lengths=(pl, ml))
+    elif (tuple(out["neighbor_indices"].shape) != (m, Kn) or tuple(out["anchor_indices"].shape) != (n, Ka) or out["lengths"] != (pl, ml)
+          or out["workspace"].numel() < wsb):
+        raise ValueError("out must be the result of an earlier call with the same lengths, num_neighbors, num_anchors and max_degree")
+    op = lib.GeoGraphOptions(Kn, Ka, float(max_distance), float(node_coverage), int(max_degree), int(onchip_cap_override))
+    v = lambda t, k: ptr(t) if k else None
+    check(_raw.dr_geo_graph_f32(P, n, m, mxp, mxn, v(points, n), ptr(out["offsets"][0]), v(node_indices, m), ptr(out["offsets"][1]),
+                                ctypes.byref(op), v(out["neighbor_indices"], m), v(out["neighbor_distances"], m), v(out["neighbor_weights"], m),
+                                v(out["anchor_indices"], n), v(out["anchor_distances"], n), v(out["anchor_weights"], n),
+                                ptr(out["status"]) if P else None, ptr(out["workspace"]), wsb, stream_of(points)))
+    return out
+
+
+def geo_graph_edges(neighbor_indices, neighbor_weights, node_lengths=None):
+    """dr_geo_graph_edges: the neighbour table as the edge list Problem takes -- edge (i, j) for every valid neighbour j != i of node i, in
+    row-major order, with the neighbour's weight.  -> (edge_indices [E, 2] int64 cloud-local, edge_weights [E], edge_lengths host list).  Reads
+    the P edge counts back once, between the count pass and the write pass, as ed_graph does."""
+    if neighbor_indices.dim() != 2:
+        raise ValueError("neighbor_indices must be [m, Kn]")
+    Kn = neighbor_indices.shape[1]
+    if not 1 <= Kn <= GEO_MAX_K:
+        raise ValueError("num_neighbors must be in 1 .. %d (got %s)" % (GEO_MAX_K, Kn))
+    ni, nw = _i64("neighbor_indices", neighbor_indices, Kn), _f32("neighbor_weights", neighbor_weights, (Kn,))
+    _device_tensor("neighbor_indices", ni)
+    _device_tensor("neighbor_weights", nw)
+    m = ni.shape[0]
+    if nw.shape[0] != m:
+        raise ValueError("neighbor_weights needs one row per node")
+    ml = _lengths_of(node_lengths, m)
+    lib.ensure_init()
+    dev, P, st = ni.device, len(ml), stream_of(ni)
+    mo, _ = _offsets(ml, dev)
+    counts = torch.empty(P, dtype=torch.int32, device=dev)
+    check(_raw.dr_geo_graph_edges(P, m, Kn, ptr(ni) if m else None, ptr(nw) if m else None, ptr(mo), ptr(counts), None, 0, None, None, st))
+    el = [int(c) for c in counts.tolist()]                  # the one host read of the batch
+    eo, E = _offsets(el, dev)
+    ei = torch.empty(E, 2, dtype=torch.int64, device=dev)
+    ew = torch.empty(E, device=dev)
+    check(_raw.dr_geo_graph_edges(P, m, Kn, ptr(ni) if m else None, ptr(nw) if m else None, ptr(mo), None, ptr(eo), E, ptr(ei) if E else None,
+                                  ptr(ew) if E else None, st))
+    return ei, ew, el
+
+
+def build_deformation_graph_from_point_cloud(points, node_indices, num_neighbors, num_anchors, max_distance, node_coverage):
+    """vision3d/array_ops/deformation.py:443-490 for one cloud on the device -> the reference's six keys.  The status word is discarded
+    (geo_graph returns it).  Each point's anchors stand in the point's own row (the reference writes the r-th reached point's into row r)."""
+    g = geo_graph(points, node_indices, num_neighbors, num_anchors, max_distance, node_coverage)
+    return {k: g[k] for k in ("neighbor_indices", "neighbor_distances", "neighbor_weights", "anchor_indices", "anchor_distances",
+                              "anchor_weights")}
+
+
 # ------------------------------------------------------------------------------------------------ vision3d's three names
 def build_euclidean_deformation_graph(points, nodes, num_anchors, node_coverage, return_point_anchor=True, return_node_graph=True,
                                       return_distance=False, return_adjacent_matrix=False, eps=1e-6):
@@ -561,13 +660,31 @@ class NonRigidRegistration:
     8: a non-finite coordinate left points without their full anchors; 4: an index out of range was treated as absent)."""
 
     def __init__(self, num_anchors=6, node_coverage=0.08, num_iterations=None, lr=0.5, gamma=0.999, weights=(1.0, 0.1, 0.1), eps=1e-6,
-                 solver="adam", corr_lambda=1.0, arap_lambda=0.1, lm_lambda=0.1, node_sampler="grid", node_min_distance=None):
+                 solver="adam", corr_lambda=1.0, arap_lambda=0.1, lm_lambda=0.1, node_sampler="grid", node_min_distance=None,
+                 graph="euclidean", num_neighbors=8, max_distance=None, max_degree=64):
         """solver="gauss_newton": dr_nicp_gn_f32 with the three lambdas in place of the Adam solver; __call__ then takes match_weights,
         per-match weights handed on as corr_weights.  num_iterations=None is each solver's reference default: 500 (Adam), 5 (Gauss-Newton).
         node_sampler: where the nodes come from when __call__ is given none -- "grid" (the default): grid barycentres with cell =
         node_coverage; "fps": furthest-point sampling as vision3d's array_ops.furthest_point_sample, with min_distance = node_min_distance
         (None: node_coverage) and node_capacity() as the cap: the nodes are points of the cloud, at least min_distance apart, never more than
-        the solver holds; a pair cut by the cap carries FPS_CAP_REACHED in graph["status"]."""
+        the solver holds; a pair cut by the cap carries FPS_CAP_REACHED in graph["status"].
+        graph: "euclidean" (the default): anchors are the nearest nodes in space (ed_graph); "geodesic": anchors and node edges come from
+        geo_graph, i.e. from path lengths along the cloud's own point graph (points closer than max_distance are joined; None: node_coverage
+        / 2), with num_neighbors neighbours per node, so that two surfaces that are close without being connected do not share nodes.  The
+        nodes must then be points of the cloud: it requires node_sampler="fps" (whose indices are used), or __call__'s node_indices=.
+        ed_warp sends a point whose anchors are all -1 to the origin, as the reference's apply_deformation does; under "geodesic" a point
+        that no node reaches has such a row, and __call__ LEAVES IT WHERE IT IS (it copies the source coordinates into those rows).  A cloud
+        with GEO_DEGREE_OVERFLOW in graph["status"] has no anchors at all: raise max_degree."""
+        if graph not in ("euclidean", "geodesic"):
+            raise ValueError("graph must be 'euclidean' or 'geodesic' (got %r)" % (graph,))
+        if graph == "geodesic" and node_sampler != "fps":
+            raise ValueError("graph='geodesic' needs nodes that are points of the cloud: construct with node_sampler='fps'")
+        self.graph, self.num_neighbors, self.max_degree = graph, int(num_neighbors), int(max_degree)
+        if graph == "geodesic" and not 1 <= self.num_neighbors <= GEO_MAX_K:
+            raise ValueError("num_neighbors must be in 1 .. %d (got %s)" % (GEO_MAX_K, num_neighbors))
+        self.max_distance = float(node_coverage) / 2 if max_distance is None else float(max_distance)
+        if graph == "geodesic" and not self.max_distance > 0:
+            raise ValueError("max_distance must be positive")
         if solver not in ("adam", "gauss_newton"):
             raise ValueError("solver must be 'adam' or 'gauss_newton' (got %r)" % (solver,))
         if node_sampler not in ("grid", "fps"):
@@ -598,9 +715,12 @@ class NonRigidRegistration:
         -> (list of [count, 3] node tensors, status [P] on the device)"""
         r = fps_nodes(torch.cat(src_list), min_distance=self.node_min_distance, lengths=[s.shape[0] for s in src_list],
                       sample_cap=node_capacity())
-        return [r["points"][p, :c].contiguous() for p, c in enumerate(r["counts"].tolist())], r["status"]
+        counts = r["counts"].tolist()
+        self._fps_indices = [r["indices"][p, :c].contiguous() for p, c in enumerate(counts)]
+        return [r["points"][p, :c].contiguous() for p, c in enumerate(counts)], r["status"]
 
-    def __call__(self, src_points, tgt_points, matches, nodes=None, match_weights=None):
+    def __call__(self, src_points, tgt_points, matches, nodes=None, match_weights=None, node_indices=None):
+        """node_indices (graph="geodesic" only): per pair the int64 rows of the source cloud that are its nodes, in place of sampling them"""
         single = isinstance(src_points, torch.Tensor)
         if match_weights is not None and self.solver != "gauss_newton":
             raise ValueError("match_weights are the Gauss-Newton solver's corr_weights: construct with solver='gauss_newton'")
@@ -610,6 +730,16 @@ class NonRigidRegistration:
         nod_l = None if nodes is None else ([nodes] if single else list(nodes))
         if not len(src_l) == len(tgt_l) == len(mat_l) or (nod_l is not None and len(nod_l) != len(src_l)):
             raise ValueError("one source cloud, target cloud, match list (and node set) per pair")
+        idx_l = None
+        if node_indices is not None:
+            if self.graph != "geodesic" or nodes is not None:
+                raise ValueError("node_indices belong to graph='geodesic' and replace nodes=")
+            idx_l = [node_indices] if single else list(node_indices)
+            if len(idx_l) != len(src_l):
+                raise ValueError("one node index list per pair")
+            nod_l = [s[i] for s, i in zip(src_l, idx_l)]
+        elif self.graph == "geodesic" and nodes is not None:
+            raise ValueError("graph='geodesic' needs the nodes as rows of the source cloud: pass node_indices=, not nodes=")
         src_l = [_f32("src_points", s, (3,)) for s in src_l]
         tgt_l = [_f32("tgt_points", t, (3,)) for t in tgt_l]
         mat_l = [_i64("matches", m, 2) for m in mat_l]
@@ -620,6 +750,7 @@ class NonRigidRegistration:
         st_nodes = None
         if nod_l is None and self.node_sampler == "fps":
             nod_l, st_nodes = self.sample_nodes_fps(src_l)       # at most node_capacity() nodes per pair, by the call's sample_cap
+            idx_l = self._fps_indices
         elif nod_l is None:
             nod_l = self.subsample_nodes(src_l)      # a launch: only now is the node count known, so the capacity is checked here,
             if max(g.shape[0] for g in nod_l) > node_capacity():                     # before the graph and the solver are launched
@@ -627,7 +758,14 @@ class NonRigidRegistration:
                                  % (max(g.shape[0] for g in nod_l), node_capacity()))
         pl, ml, cl = [s.shape[0] for s in src_l], [g.shape[0] for g in nod_l], [m.shape[0] for m in mat_l]
         src, nod = torch.cat(src_l), torch.cat(nod_l)
-        g = ed_graph(src, nod, self.num_anchors, self.node_coverage, point_lengths=pl, node_lengths=ml, eps=self.eps)
+        if self.graph == "geodesic":
+            gg = geo_graph(src, torch.cat(idx_l), self.num_neighbors, self.num_anchors, self.max_distance, self.node_coverage,
+                           point_lengths=pl, node_lengths=ml, max_degree=self.max_degree)
+            ei, ew, el = geo_graph_edges(gg["neighbor_indices"], gg["neighbor_weights"], node_lengths=ml)
+            g = dict(anchor_indices=gg["anchor_indices"], anchor_weights=gg["anchor_weights"], edge_indices=ei, edge_weights=ew, edge_lengths=el,
+                     status=gg["status"] & ~3)          # its 1 and 2 mean other things than this word's
+        else:
+            g = ed_graph(src, nod, self.num_anchors, self.node_coverage, point_lengths=pl, node_lengths=ml, eps=self.eps)
         rows, lo = [], 0
         for s, m in zip(src_l, mat_l):                      # the correspondences' rows of the stacked source cloud
             rows.append(m[:, 0] + lo)
@@ -649,6 +787,8 @@ class NonRigidRegistration:
         else:
             T, _, _, st_solver = nicp_adam(pb, num_iterations=self.num_iterations, lr=self.lr, gamma=self.gamma, weights=self.weights)
         warped, st_warp = ed_warp(src, nod, T, g["anchor_indices"], g["anchor_weights"], point_lengths=pl, node_lengths=ml, eps=self.eps)
+        if self.graph == "geodesic":                     # a point no node reaches stays where it is (ed_warp alone sends it to the origin)
+            warped = torch.where((g["anchor_indices"] >= 0).any(1, keepdim=True), warped, src)
         st_all = g["status"] | st_solver | st_warp
         if st_nodes is not None:
             st_all = st_all | (st_nodes & (FPS_CAP_REACHED | FPS_START_NONFINITE))   # the sampler's 1 / 2 / 8 mean other things than this word's

@@ -79,7 +79,9 @@ extern "C" {
  *   0.7.0, sixteenth set (same rule)  Gauss-Newton non-rigid ICP: dr_nicp_gn_f32, dr_nicp_gn_normal_f32 with dr_nicp_gn_workspace_bytes and the
  *          new struct dr_nicp_gn_options, dr_spd_solve_f64 (new entries only; nothing older changed).
  *   0.7.0, seventeenth set (same rule)  furthest-point sampling: dr_fps_nodes_f32, dr_fps_batch_f32 with dr_fps_workspace_bytes and
- *          dr_fps_onchip_capacity (new entries only; nothing older changed). */
+ *          dr_fps_onchip_capacity (new entries only; nothing older changed).
+ *   0.7.0, eighteenth set (same rule)  the geodesic deformation graph: dr_geo_graph_f32, dr_geo_graph_edges with dr_geo_graph_workspace_bytes,
+ *          dr_geo_graph_onchip_capacity and the new struct dr_geo_graph_options (new entries only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1580,7 +1582,8 @@ int dr_overlap_2d3d_f64(int H, int W, int N, const float* depth, double scaling_
  * absent; 8 (dr_ed_graph_f32), a NaN or Inf coordinate of a point or a node left a point with fewer than min(K, M) anchors; 16
  * (dr_nicp_adam_f32), a negative resumed step count was taken as 0; 32 is the sixteenth set's (a failed pivot); 64 and 128 are the seventeenth
  * set's (dr_fps_nodes_f32: sample_cap reached before the stop rule; point 0 of the cloud is not finite), the only two bits of that set's status
- * which NonRigidRegistration ORs into the same word (its 1, 2 and 8 mean other things there and are masked off).  A pair with bit 1 or 2 is neither read nor computed: its rows of the
+ * which NonRigidRegistration ORs into the same word (its 1, 2 and 8 mean other things there and are masked off); 256 and 512 are the
+ * eighteenth set's (dr_geo_graph_f32: a duplicate node index; a point with more neighbours than max_degree).  A pair with bit 1 or 2 is neither read nor computed: its rows of the
  * outputs are not written.  max_nodes is an upper bound of every pair's node count known to the HOST.  1 <= K <= 8.  P = 0 is a no-op; a negative size, a K out of range or a NULL pointer that a non-empty array needs is DR_EINVAL, a
  * product of sizes beyond 2^31 - 1 DR_ENOSUP, a missing or short workspace DR_EWORKSPACE (16-byte aligned, else DR_EINVAL): all reported before
  * the first launch, with every output untouched.
@@ -1853,6 +1856,65 @@ int dr_fps_nodes_f32(int P, int n_points, int max_points, const float* points, c
                      void* workspace, size_t workspace_bytes, void* stream);
 int dr_fps_batch_f32(int B, int N, int num_samples, const float* points, int64_t* out_indices, void* workspace, size_t workspace_bytes,
                      void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, eighteenth set (detected by symbol like the fourth to seventeenth sets): the geodesic deformation graph of a point
+ * cloud, the reference's second graph builder.  2D-3D vision3d/csrc/cpu/deformation_graph/deformation_graph.cpp:13-180 behind
+ * vision3d/array_ops/deformation.py:443-490.  csrc/geo_graph.hip, indices in csrc/geo_graph_index.h; DESIGN 5zb.
+ *
+ * Conventions of the fourteenth set: ragged over P clouds through int32 DEVICE arrays of P + 1 offsets (p_offsets: points, n_offsets: nodes),
+ * asynchronous on `stream` (a hipStream_t), nothing allocated, nothing read back, no floating-point atomic and no atomic that decides an order:
+ * two runs are bit-equal and both entries can be captured in a graph (dr_init sets the relaxation's LDS attribute, outside any capture).
+ * node_indices [n_nodes] int64 are CLOUD-LOCAL point indices, as dr_fps_nodes_f32 returns them; the node numbers in the outputs are
+ * cloud-local too.  P = 0 is a no-op; a negative size, max_points > n_points, max_nodes > n_nodes, num_neighbors or num_anchors outside
+ * 1 .. 8, max_degree < 1, a max_distance or node_coverage that is not finite and > 0, or a NULL pointer that a non-empty array needs is
+ * DR_EINVAL; more than 65 535 clouds, 2^31 / 3 stacked points, max_nodes > 2 048 or max_degree > 1 024 DR_ENOSUP; a missing or short workspace
+ * DR_EWORKSPACE (16-byte aligned, else DR_EINVAL): all reported before the first launch, with every output untouched.
+ *
+ * dr_geo_graph_f32 computes, for every cloud, exactly this:
+ *   Edges: points i != k are joined iff d(i, k) < max_distance, d = sqrtf((dx dx + dy dy) + dz dz) in float32, operation by operation, never
+ *     contracted (cloud.h:46, .cpp:62).  (The reference's voxel hash only finds these pairs.)  A point with a NaN or Inf coordinate has no edge.
+ *   Path length: g_i(x) = the smallest left-to-right float32 sum of edge lengths over the paths from node i's point to x; x is reached iff
+ *     g_i(x) <= 2.0 * node_coverage, compared in double (.cpp:137); the node's own point is reached at 0.  The device relaxes
+ *     g(y) = min(g(y), fl(g(x) + d(x, y))) to its least fixed point, which is the reference's Dijkstra result bit for bit.
+ *   neighbor_* [n_nodes, num_neighbors]: of the NODES node i reaches, the first num_neighbors by (g ascending, point index DESCENDING) -- the
+ *     pop order of the reference's max-heap of (-g, point); the node itself comes first.  Rows are padded with -1 / 0 / 0.
+ *   anchor_* [n_points, num_anchors]: of the nodes that reach point x, the first num_anchors by (g ascending, node index ascending) (.cpp:151);
+ *     padded with -1 / 0 / 0; an unreached point has a whole row of padding.
+ *   Weights: exp(-(g g) / (2. c c)) with g g in float32 and the rest in double, rounded once (.cpp:9-11).  Anchor weights are then divided by
+ *     their float32 sum taken in list order; a sum of 0 gives each 1 / count (.cpp:163-176).  Neighbour weights are not normalised.
+ *   Parity with the reference is claimed where no comparison above is a tie or within rounding of its bound (the fixture is screened so).
+ *   max_points / max_nodes: upper bounds of every cloud's point / node count known to the HOST.  options->max_degree: the slots of a point's
+ *   adjacency row in the workspace; options->onchip_cap_override: 0, or a smaller on-chip capacity than dr_geo_graph_onchip_capacity() (a
+ *   test drives the streamed form with it).  A cloud of at most that many points keeps its distances in LDS; a larger one relaxes in the
+ *   workspace, with the same result entry for entry.
+ *   status [P] int32 receives per cloud 0 or a sum of: 1, more points than max_points or more nodes than max_nodes; 2, the offsets up to this
+ *   cloud do not ascend inside [0, total] (nothing of the cloud is written: its rows stay as the caller left them); 4, a node index outside
+ *   [0, n) was treated as an absent node (it reaches nothing and nobody's neighbour); 8, a point with a NaN or Inf coordinate was met; 256,
+ *   two nodes name one point (the cloud's results are then only guaranteed to be in range); 512, a point has more than max_degree points
+ *   closer than max_distance.  A cloud with bit 1 or 512 gets rows of padding only: nothing is cut silently.
+ *   Workspace: dr_geo_graph_workspace_bytes(P, n_points, n_nodes, max_points, max_degree): 8 (1 + max_degree) bytes per point and
+ *   4 max_points bytes per node (the reach table the anchors are read from).
+ * dr_geo_graph_onchip_capacity: the largest cloud whose distances stay in LDS.
+ * dr_geo_graph_edges: the neighbour table as dr_nicp_problem's edge list: edge (i, j) for every neighbour 0 <= j < M, j != i of node i, in
+ *   row-major order, with the neighbour's weight.  TWO calls, as dr_ed_graph_f32: with e_offsets == NULL it writes edge_counts [P]; with
+ *   e_offsets [P + 1] it writes cloud p's edges from row e_offsets[p]; rows at or behind min(e_offsets[p + 1], edge_cap) are not written.
+ *   edge_weights may be NULL.  n_nodes * num_neighbors is an upper bound of the total, so a caller that must not read back can size by it. */
+typedef struct dr_geo_graph_options {
+    int num_neighbors, num_anchors;                       /* Kn, Ka: 1 .. 8 */
+    float max_distance, node_coverage;
+    int max_degree;                                       /* slots of a point's adjacency row */
+    int onchip_cap_override;                              /* 0 = the default capacity */
+} dr_geo_graph_options;
+int dr_geo_graph_onchip_capacity(void);
+size_t dr_geo_graph_workspace_bytes(int P, int n_points, int n_nodes, int max_points, int max_degree);
+int dr_geo_graph_f32(int P, int n_points, int n_nodes, int max_points, int max_nodes, const float* points, const int32_t* p_offsets,
+                     const int64_t* node_indices, const int32_t* n_offsets, const dr_geo_graph_options* options, int64_t* neighbor_indices,
+                     float* neighbor_distances, float* neighbor_weights, int64_t* anchor_indices, float* anchor_distances, float* anchor_weights,
+                     int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int dr_geo_graph_edges(int P, int n_nodes, int num_neighbors, const int64_t* neighbor_indices, const float* neighbor_weights,
+                       const int32_t* n_offsets, int32_t* edge_counts, const int32_t* e_offsets, long long edge_cap, int64_t* edge_indices,
+                       float* edge_weights, void* stream);
 
 #ifdef __cplusplus
 }
