@@ -536,6 +536,19 @@ SIGNATURES.update({
 })
 
 
+SIGNATURES.update({
+    # added after ABI 0.7.0, nineteenth set: the non-rigid evaluation (csrc/knn_points.hip)
+    "dr_knn_points_max_k": (c_int, []),
+    "dr_knn_points_tile": (c_int, []),
+    "dr_knn_points_block": (c_int, []),
+    "dr_knn_points_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [c_int] + [c_void_p] * 4),
+    "dr_nn_stats_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dr_nn_stats_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 4 + [c_float] + [c_void_p] * 3 + [c_size_t, c_void_p]),
+    "dr_flow_metrics_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dr_flow_metrics_f32": (c_int, [c_int, c_int] + [c_void_p] * 7 + [c_float] * 7 + [c_void_p] * 3 + [c_size_t, c_void_p]),
+})
+
+
 def _bind(table):
     for name, (res, args) in table.items():
         if not hasattr(_lib, name):          # the sets added under one ABI number are detected by symbol

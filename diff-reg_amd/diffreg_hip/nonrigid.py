@@ -800,3 +800,12 @@ class NonRigidRegistration:
             res.append((warped[p0:p0 + p], T[m0:m0 + m], graph))
             p0, m0, e0 = p0 + p, m0 + m, e0 + e
         return res[0] if single else ([r[0] for r in res], [r[1] for r in res], [r[2] for r in res])
+
+    def evaluate(self, result, src_points, scene_flows, tgt_points, gt_transform=None, matches=None, test_indices=None, **kw):
+        """__call__'s output, for one pair or a list of pairs, into metrics_nonrigid.evaluate_nonrigid_pairs (which names the keyword
+        arguments: the strict / relaxed / outlier threshold pairs are required); -> its dict.  Nothing is read back."""
+        from . import metrics_nonrigid
+        single = isinstance(src_points, torch.Tensor)
+        wrap = (lambda x: None if x is None else [x]) if single else (lambda x: None if x is None else list(x))
+        return metrics_nonrigid.evaluate_nonrigid_pairs(wrap(src_points), wrap(result[0]), wrap(scene_flows), wrap(tgt_points),
+                                                        wrap(gt_transform), wrap(matches), wrap(test_indices), **kw)

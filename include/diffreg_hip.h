@@ -81,7 +81,9 @@ extern "C" {
  *   0.7.0, seventeenth set (same rule)  furthest-point sampling: dr_fps_nodes_f32, dr_fps_batch_f32 with dr_fps_workspace_bytes and
  *          dr_fps_onchip_capacity (new entries only; nothing older changed).
  *   0.7.0, eighteenth set (same rule)  the geodesic deformation graph: dr_geo_graph_f32, dr_geo_graph_edges with dr_geo_graph_workspace_bytes,
- *          dr_geo_graph_onchip_capacity and the new struct dr_geo_graph_options (new entries only; nothing older changed). */
+ *          dr_geo_graph_onchip_capacity and the new struct dr_geo_graph_options (new entries only; nothing older changed).
+ *   0.7.0, nineteenth set (same rule)  the non-rigid evaluation: dr_knn_points_f32 with dr_knn_points_max_k / _tile / _block, dr_nn_stats_f32
+ *          with dr_nn_stats_workspace_bytes, dr_flow_metrics_f32 with dr_flow_metrics_workspace_bytes (new entries only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1915,6 +1917,61 @@ int dr_geo_graph_f32(int P, int n_points, int n_nodes, int max_points, int max_n
 int dr_geo_graph_edges(int P, int n_nodes, int num_neighbors, const int64_t* neighbor_indices, const float* neighbor_weights,
                        const int32_t* n_offsets, int32_t* edge_counts, const int32_t* e_offsets, long long edge_cap, int64_t* edge_indices,
                        float* edge_weights, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, nineteenth set (detected by symbol like the fourth to eighteenth sets): what measures the output of the non-rigid
+ * chain.  2D-3D vision3d/ops/knn.py:10-107 (knn over keops_knn), vision3d/ops/knn_interpolate.py:10-40 (its k = 3 consumer) and the six
+ * non-rigid metrics of vision3d/ops/metrics.py:258-372.  csrc/knn_points.hip, indices in csrc/knn_index.h; DESIGN 5zc.
+ *
+ * Conventions of the fourteenth set: ragged over P pairs through int32 DEVICE arrays of P + 1 offsets, asynchronous on `stream` (a
+ * hipStream_t), nothing allocated, nothing read back, NO atomic of any kind: two runs are bit-equal and every entry can be captured.  Each
+ * offset array may be given a second time as a HOST mirror (host_*_offsets, or NULL): a mirror that does not start at >= 0, ascend and end at
+ * <= the row count is DR_EINVAL before any launch.  The device arrays are checked by the kernels: a pair whose offsets do not describe slices
+ * sets status bit 4 and is skipped (its rows are not written; its sums are 0).  P = 0 is a no-op; a negative size, k outside
+ * 1 .. dr_knn_points_max_k() or a NULL pointer that a non-empty array needs is DR_EINVAL, more than 65 535 pairs or 2^31 / 3 stacked rows
+ * DR_ENOSUP, a missing or short workspace DR_EWORKSPACE (16-byte aligned, else DR_EINVAL): all reported before the first launch.
+ *
+ * dr_knn_points_f32: for every query of pair p its k nearest supports of pair p (knn.py:22-27, dij = (xi - xj).norm2(), Kmin_argKmin).
+ *   THE RULE: d2 = (dx dx + dy dy) + dz dz in float32, operation by operation, never contracted into an FMA; a row's k slots ascend by
+ *   (d2, support index), so among equal d2 the LOWER index comes first, whatever lane, wave or tile met it; out_distances = sqrtf(d2),
+ *   correctly rounded.  KeOps' own tie order is not claimed.  (Ordering by (distance, index) differs only where two distinct d2 round to one
+ *   sqrtf; the fixture's screen excludes that.)  out_distances [n_queries, k] float32 and out_indices [n_queries, k] int64 (PAIR-LOCAL support
+ *   rows); either may be NULL.  Slots that cannot be filled -- fewer than k supports, an empty support cloud -- hold +inf and -1 (stated
+ *   difference: the reference returns min(k, S) columns, knn.py:75).  A support with a NaN or Inf coordinate, and one whose d2 overflows
+ *   float32, is never selected.  A query with a NaN or Inf coordinate gets an all +inf / -1 row and sets status bit 8 (the bit's meaning
+ *   in the fourteenth set).  status [P] int32: 0 or a sum of 4 and 8.  No workspace.
+ *   dr_knn_points_max_k() = 16; dr_knn_points_block() = the queries of one workgroup, dr_knn_points_tile() = the supports of one LDS tile
+ *   (exported so that tests can place shapes on both sides of them).
+ * dr_nn_stats_f32: the k = 1 search with its reduction fused, no distance array: out [P, 4] double = the number of queries that have a
+ *   nearest support (a query without a finite support, and a non-finite query, is not counted and contributes nothing), sum dist,
+ *   sum dist^2 (dist promoted to double, then squared), the count of dist < distance_limit (float32 compare).  compute_chamfer_distance
+ *   (metrics.py:365-372) is two calls, compute_corr_coverage (:359-362) one.  The order is fixed: the 64 queries of a block by the tree
+ *   lane l += lane l + off, off = 32 .. 1; the blocks of a pair in ascending order, in double.  Workspace: dr_nn_stats_workspace_bytes(P,
+ *   n_queries).
+ * dr_flow_metrics_f32: the per-point predicates of compute_scene_flow_accuracy (:323-337), compute_scene_flow_outlier_ratio (:340-356),
+ *   compute_nonrigid_inlier_ratio (:258-284) and the last two lines of compute_nonrigid_feature_matching_recall (:318-319) in one pass over
+ *   pred / target [n_points, 3]: with rot [P, 9] / trn [P, 3] (both or neither) pred is first replaced by R pred + t of its pair (the
+ *   reference's `transform`); |e| = sqrtf of the float32 d2 above of (pred, target); rel = |e| / (|target| + eps); strict / relaxed =
+ *   |e| < abs || rel < rel_thr; outlier = |e| > abs || rel > rel_thr, where a NEGATIVE threshold is the reference's None; within = |e| <
+ *   strict_abs alone (the NIR / NFMR predicate).  mask (uint8 [n_points] or NULL): a point with mask 0 is left out of everything.
+ *   out [P, 6] double = n, sum |e|, n_strict, n_relaxed, n_outlier, n_within; counts are integers held in double; sums go lanes -> wave
+ *   (the tree above) -> the four waves in order -> the blocks of a pair in ascending order.  status [P]: 0 or 4.  Workspace:
+ *   dr_flow_metrics_workspace_bytes(P, n_points). */
+int dr_knn_points_max_k(void);
+int dr_knn_points_tile(void);
+int dr_knn_points_block(void);
+int dr_knn_points_f32(int P, int n_queries, const float* queries, const int32_t* q_offsets, int n_supports, const float* supports,
+                      const int32_t* s_offsets, const int32_t* host_q_offsets, const int32_t* host_s_offsets, int k, float* out_distances,
+                      int64_t* out_indices, int32_t* status, void* stream);
+size_t dr_nn_stats_workspace_bytes(int P, int n_queries);
+int dr_nn_stats_f32(int P, int n_queries, const float* queries, const int32_t* q_offsets, int n_supports, const float* supports,
+                    const int32_t* s_offsets, const int32_t* host_q_offsets, const int32_t* host_s_offsets, float distance_limit, double* out,
+                    int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+size_t dr_flow_metrics_workspace_bytes(int P, int n_points);
+int dr_flow_metrics_f32(int P, int n_points, const float* pred, const float* target, const int32_t* offsets, const int32_t* host_offsets,
+                        const uint8_t* mask, const float* rot, const float* trn, float strict_abs, float strict_rel, float relaxed_abs,
+                        float relaxed_rel, float outlier_abs, float outlier_rel, float eps, double* out, int32_t* status, void* workspace,
+                        size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
