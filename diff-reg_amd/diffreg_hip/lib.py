@@ -548,6 +548,22 @@ SIGNATURES.update({
     "dr_flow_metrics_f32": (c_int, [c_int, c_int] + [c_void_p] * 7 + [c_float] * 7 + [c_void_p] * 3 + [c_size_t, c_void_p]),
 })
 
+SIGNATURES.update({
+    # added after ABI 0.7.0, twentieth set: the RANSAC-free rigid estimators (csrc/lgr.hip; wrappers in diffreg_hip/registration.py)
+    "dr_lgr_wave_limit": (c_int, []),
+    "dr_sc_block": (c_int, []),
+    "dr_sc_tile": (c_int, []),
+    "dr_weighted_procrustes_f32": (c_int, [c_int, c_int] + [c_void_p] * 5 + [c_float, c_float, c_int] + [c_void_p] * 3),
+    "dr_lgr_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dr_lgr_f32": (c_int, [c_int, c_int] + [c_void_p] * 5 + [c_int] + [c_void_p] * 6 + [c_float, c_int, c_int, c_float, c_float] +
+                   [c_void_p] * 8 + [c_size_t, c_void_p]),
+    "dr_spatial_consistency_f32": (c_int, [c_int, c_int] + [c_void_p] * 3 + [c_int] + [c_void_p] * 5 + [c_float] + [c_void_p] * 4),
+    "dr_sc_row_sums_f32": (c_int, [c_int, c_int] + [c_void_p] * 3 + [c_int] + [c_void_p] * 5 + [c_float] + [c_void_p] * 4),
+    "dr_sc_leading_eigenvector_workspace_bytes": (c_size_t, [c_int, c_int]),
+    "dr_sc_leading_eigenvector_f32": (c_int, [c_int, c_int] + [c_void_p] * 4 + [c_float] + [c_void_p] * 2 + [c_int] + [c_void_p] * 4 +
+                                      [c_size_t, c_void_p]),
+})
+
 
 def _bind(table):
     for name, (res, args) in table.items():

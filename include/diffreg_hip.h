@@ -83,7 +83,10 @@ extern "C" {
  *   0.7.0, eighteenth set (same rule)  the geodesic deformation graph: dr_geo_graph_f32, dr_geo_graph_edges with dr_geo_graph_workspace_bytes,
  *          dr_geo_graph_onchip_capacity and the new struct dr_geo_graph_options (new entries only; nothing older changed).
  *   0.7.0, nineteenth set (same rule)  the non-rigid evaluation: dr_knn_points_f32 with dr_knn_points_max_k / _tile / _block, dr_nn_stats_f32
- *          with dr_nn_stats_workspace_bytes, dr_flow_metrics_f32 with dr_flow_metrics_workspace_bytes (new entries only; nothing older changed). */
+ *          with dr_nn_stats_workspace_bytes, dr_flow_metrics_f32 with dr_flow_metrics_workspace_bytes (new entries only; nothing older changed).
+ *   0.7.0, twentieth set (same rule)  the RANSAC-free rigid estimators: dr_weighted_procrustes_f32 with dr_lgr_wave_limit, dr_lgr_f32 with
+ *          dr_lgr_workspace_bytes, dr_spatial_consistency_f32, dr_sc_row_sums_f32 with dr_sc_block / dr_sc_tile, dr_sc_leading_eigenvector_f32
+ *          with dr_sc_leading_eigenvector_workspace_bytes (new entries only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -1972,6 +1975,86 @@ int dr_flow_metrics_f32(int P, int n_points, const float* pred, const float* tar
                         const uint8_t* mask, const float* rot, const float* trn, float strict_abs, float strict_rel, float relaxed_abs,
                         float relaxed_rel, float outlier_abs, float outlier_rel, float eps, double* out, int32_t* status, void* workspace,
                         size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, twentieth set (detected by symbol like the fourth to nineteenth sets): the rigid counterpart of the non-rigid
+ * chain, vision3d's RANSAC-free estimators.  2D-3D vision3d/ops/weighted_procrustes.py:10-71, vision3d/models/geotransformer/
+ * local_global_registration.py:104-161, vision3d/ops/spatial_consistency.py:7-54, vision3d/ops/eigenvector.py:21-31 and
+ * vision3d/models/geotransformer/spatial_consistency_filtering.py:15-19.  csrc/lgr.hip, indices in csrc/lgr_index.h; DESIGN 5zd.
+ *
+ * Conventions of the fourteenth set: ragged over P problems (G groups) through int32 DEVICE arrays of P + 1 offsets, asynchronous on `stream`
+ * (a hipStream_t), nothing allocated, nothing read back, no floating-point atomic: two runs are bit-equal and every entry can be captured on
+ * one stream.  Each offset array may be given a second time as a HOST mirror (host_*_offsets, or NULL): a mirror that does not start at >= 0,
+ * ascend and end at <= the row count is DR_EINVAL before any launch.  The device arrays are checked by the kernels: a problem whose offsets
+ * do not describe slices sets status bit 4, one that holds a NaN or Inf coordinate, weight or score sets status bit 8; either way the problem
+ * is SKIPPED: none of its outputs but the status word is written.  P = 0 is a no-op; a negative size or a NULL pointer that a non-empty
+ * array needs is DR_EINVAL, more than 65 535 problems or 2^31 / 3 stacked rows DR_ENOSUP, a missing or short workspace DR_EWORKSPACE
+ * (16-byte aligned, else DR_EINVAL; transform arrays are 16-byte aligned as well): all reported before the first launch.
+ *
+ * dr_weighted_procrustes_f32 (RULE 1): for group g, rows [offsets[g], offsets[g + 1]) of src / tgt [n, 3] and weights [n] (NULL: ones):
+ *   w = (w < weight_threshold) ? 0 : w;  W = sum w;  pc = (sum w p) / (W + eps), qc = (sum w q) / (W + eps);
+ *   H = sum (w / (W + eps)) (p - pc)(q - qc)^T;  H = U S V^T by the library's double one-sided Jacobi (svd3_jacobi);
+ *   R = V diag(1, 1, sign det(V U^T)) U^T;  t = qc - R pc.  Every sum runs in double on the float32 inputs in ONE order: element i belongs
+ *   to slot (i / 64 % 4, i % 64); a slot adds its elements ascending, the 64 slots of a virtual wave meet in the tree lane l += lane l + off
+ *   (off = 32 .. 1), the four virtual waves are added ascending.  R and t are rounded once to float32: transforms [G, 16], row-major 4 x 4.
+ *   A group of at most wave_limit rows is fitted by one wave, a longer one by a workgroup (wave_limit < 0: dr_lgr_wave_limit(); 0 sends
+ *   every group to the workgroup path, INT_MAX every group to the wave path): the two paths add the same doubles in the same order and are
+ *   bit-equal.  A group with no positive weight, or an all-zero H, has R = identity and status bit 16 (torch.svd of a zero matrix gives
+ *   U = V = identity as well); t follows the rule (0 when W = 0).  A group of one or two rows has a rank-1 H (eps keeps it from zero): R is
+ *   a proper rotation that maps the fitted direction, its turn about that direction is the Jacobi SVD's completion of the basis, not
+ *   LAPACK's.  status [G]: 0, 4, 8 or 16.  No workspace.
+ * dr_lgr_f32: local_to_global_registration for P problems in one call, five launches whatever P.  Per problem its correspondences in
+ *   torch.nonzero order -- src_points / tgt_points [n_corr, 3], scores [n_corr], patch_ids [n_corr] int32, NON-DESCENDING inside a problem
+ *   (a violation sets status bit 4) -- and its verification set v_* under offsets of its own (the same arrays, or the caller's top
+ *   max_global_correspondences).  (a) chunks = the runs of equal patch id of at least min_local_correspondences rows, found by a count pass
+ *   and a scan; (b) one fit per chunk by rule 1 with the scores as weights; (c) per chunk the INTEGER count of verification correspondences
+ *   inside acceptance_radius, one wave per hypothesis; the best chunk has the largest count, the LOWEST chunk index among equals;
+ *   (d), (e) num_refinement_steps times: cur = v_scores * inlier(current transform), then a fit by rule 1 on the verification set with cur;
+ *   the first round's transform is the best chunk's.  A problem without a chunk first fits the whole verification set with v_scores (the
+ *   reference's degenerate branch, :147-151).  All rounds of a problem run in one launch by one workgroup.
+ *   THE RESIDUAL RULE: with the transform already rounded to float32, x' = ((R00 x + R01 y) + R02 z) + t0 and likewise y', z', in float32,
+ *   never contracted; d2 = (dx dx + dy dy) + dz dz of (tgt - x'); inlier iff sqrtf(d2) < acceptance_radius, a float32 compare.
+ *   Outputs: transform [P, 16]; optional best_chunk [P] (-1 in the degenerate branch), final_scores [n_verify] (the cur of the last fit),
+ *   chunk_transforms [n_corr, 16] / chunk_counts [n_corr] (hypothesis chunk_offsets[p] + j is chunk j of problem p; capacity n_corr rows) and
+ *   chunk_offsets [P + 1]; status [P]: bit 32 = a problem with no correspondence (transform = identity; the reference raises), bit 16 = the
+ *   last fit was degenerate.  Workspace: dr_lgr_workspace_bytes(P, n_corr).  1 <= num_refinement_steps <= 64, min_local >= 1.
+ * dr_spatial_consistency_f32: the dense [Nq_p, Ns_p] matrix of problem p at element mat_offsets[p] of out (int64 DEVICE offsets, P + 1).
+ *   RULE, float32, never contracted: d = sqrtf(d2) of the two source points and of the two target points, d2 = (dx dx + dy dy) + dz dz;
+ *   delta = |ds - dt|; sc = max(1 - (delta * delta) / (sigma * sigma), 0).  Stated difference: the reference's pairwise_distance expands
+ *   |x|^2 - 2xy + |y|^2 and clamps; this entry takes the difference first.  status [P]: 0, 4 or 8.  No workspace.
+ * dr_sc_row_sums_f32: out[i] = sum_j sc(i, j) * multiplier[j] (NULL: 1) over the supports of query i's problem, without the matrix.  A
+ *   workgroup owns dr_sc_block() queries, a lane one query; the supports pass through LDS in tiles of dr_sc_tile(); the sum runs in double,
+ *   supports ascending, and is rounded once to float32.  out [n_queries].  No workspace.
+ * dr_sc_leading_eigenvector_f32: power iteration on the spatial-consistency matrix of src_points / tgt_points [n, 3] (matrix-free), or, with
+ *   mat != NULL (points NULL), on the caller's dense [N_p, N_p] matrices at mat_offsets.  v0 = 1; per iteration y = float32(M v) (double
+ *   sums; dense form: lane l adds columns l, l + 64, ... ascending, then the tree), v = y / max(float32(sqrt(sum y^2 in double, rule 1's
+ *   order)), 1e-12); the problem stops when |v - v_last| <= 1e-8 + 1e-5 |v_last| holds for every entry in float32 -- a DEVICE flag: the
+ *   remaining iterations leave that problem's vector untouched.  out [n]; iterations [P] = the iterations that ran.  Two launches per
+ *   iteration and one before the first.  Workspace: dr_sc_leading_eigenvector_workspace_bytes(P, n). */
+int dr_lgr_wave_limit(void);
+int dr_sc_block(void);
+int dr_sc_tile(void);
+int dr_weighted_procrustes_f32(int G, int n, const float* src, const float* tgt, const float* weights, const int32_t* offsets,
+                               const int32_t* host_offsets, float weight_threshold, float eps, int wave_limit, float* transforms,
+                               int32_t* status, void* stream);
+size_t dr_lgr_workspace_bytes(int P, int n_corr);
+int dr_lgr_f32(int P, int n_corr, const float* src_points, const float* tgt_points, const float* scores, const int32_t* patch_ids,
+               const int32_t* corr_offsets, int n_verify, const float* v_src_points, const float* v_tgt_points, const float* v_scores,
+               const int32_t* verify_offsets, const int32_t* host_corr_offsets, const int32_t* host_verify_offsets, float acceptance_radius,
+               int min_local_correspondences, int num_refinement_steps, float weight_threshold, float eps, float* transform,
+               int32_t* best_chunk, float* final_scores, float* chunk_transforms, int32_t* chunk_counts, int32_t* chunk_offsets,
+               int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+int dr_spatial_consistency_f32(int P, int n_queries, const float* q_src_points, const float* q_tgt_points, const int32_t* q_offsets,
+                               int n_supports, const float* s_src_points, const float* s_tgt_points, const int32_t* s_offsets,
+                               const int32_t* host_q_offsets, const int32_t* host_s_offsets, float sigma, const int64_t* mat_offsets, float* out,
+                               int32_t* status, void* stream);
+int dr_sc_row_sums_f32(int P, int n_queries, const float* q_src_points, const float* q_tgt_points, const int32_t* q_offsets, int n_supports,
+                       const float* s_src_points, const float* s_tgt_points, const int32_t* s_offsets, const int32_t* host_q_offsets,
+                       const int32_t* host_s_offsets, float sigma, const float* multiplier, float* out, int32_t* status, void* stream);
+size_t dr_sc_leading_eigenvector_workspace_bytes(int P, int n);
+int dr_sc_leading_eigenvector_f32(int P, int n, const float* src_points, const float* tgt_points, const int32_t* offsets,
+                                  const int32_t* host_offsets, float sigma, const float* mat, const int64_t* mat_offsets, int num_iterations,
+                                  float* out, int32_t* iterations, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }
