@@ -162,12 +162,6 @@ __global__ __launch_bounds__(256) void bitonic_global_kernel(unsigned long long*
     if (bs_greater(ka, va, kb, vb) == up) { keys[i] = kb; keys[l] = ka; vals[i] = vb; vals[l] = va; }
 }
 
-static int next_pow2(int n) {
-    int p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
 int launch_bitonic_sort(unsigned long long* keys, unsigned* vals, int n_pad, hipStream_t st) {   // (kernels.h: also sorts the keys of fine2d3d.hip)
     const int chunks = (n_pad + BS_CHUNK - 1) / BS_CHUNK;
     hipLaunchKernelGGL(bitonic_local_kernel, dim3(chunks), dim3(1024), 0, st, keys, vals, n_pad, 2, min(n_pad, BS_CHUNK));
@@ -459,6 +453,20 @@ __global__ __launch_bounds__(CH_BLOCK) void radius_count_hist_kernel(CountArgs C
     }
 }
 
+// grid subsample (members in layout order, as in carve.h): the clouds' table, the sort rows, the heads counted per scan block
+struct SubsampleWs { int n_pad, nblk; CloudInfo* info; unsigned long long* keys; unsigned* vals; int* block_off; size_t bytes; };
+static SubsampleWs subsample_carve(void* base, int n, int nb) {
+    Carver c(base); const int np = next_pow2(n), nblk = (n + SC_BLOCK * SC_PER - 1) / (SC_BLOCK * SC_PER);
+    return {np, nblk, c.take<CloudInfo>(nb), c.take<unsigned long long>(np), c.take<unsigned>(np), c.take<int>(nblk), align256(c.off)};
+}
+// the ball index of both radius entries: the clouds' tables, the supports' sort rows, the supports in key order, the cell table (2 n_pad slots)
+struct BallWs { int n_pad; unsigned tab_size; CloudInfo *q_info, *s_info; unsigned long long* keys; unsigned* vals; float4* sorted; CellSlot* tab; size_t bytes; };
+static BallWs ball_carve(void* base, int ns, int nb) {
+    Carver c(base); const int np = next_pow2(ns);
+    return {np, 2u * (unsigned)np, c.take<CloudInfo>(nb), c.take<CloudInfo>(nb), c.take<unsigned long long>(np), c.take<unsigned>(np),
+            c.take<float4>(ns), c.take<CellSlot>(2 * (size_t)np), align256(c.off)};
+}
+
 }  // namespace dr
 
 using namespace dr;
@@ -466,10 +474,7 @@ using namespace dr;
 extern "C" {
 
 size_t dr_grid_subsample_workspace_bytes(int n, int nb) {
-    if (n <= 0 || nb <= 0) return 0;
-    const int n_pad = next_pow2(n);
-    const int nblk = (n + SC_BLOCK * SC_PER - 1) / (SC_BLOCK * SC_PER);
-    return align256(sizeof(CloudInfo) * nb) + align256(8ull * n_pad) + align256(4ull * n_pad) + align256(4ull * nblk);
+    return (n <= 0 || nb <= 0) ? 0 : subsample_carve(nullptr, n, nb).bytes;
 }
 
 static int grid_subsample_impl(int origin_mode, int n, int nb, const float* points, const int32_t* lengths, float dl, float* out_points,
@@ -484,24 +489,18 @@ static int grid_subsample_impl(int origin_mode, int n, int nb, const float* poin
     if (n == 0) return DR_OK;
     if (!points || !out_points) return DR_EINVAL;
     if (!workspace || workspace_bytes < dr_grid_subsample_workspace_bytes(n, nb)) return DR_EWORKSPACE;
-    const int n_pad = next_pow2(n);
-    const int nblk = (n + SC_BLOCK * SC_PER - 1) / (SC_BLOCK * SC_PER);
-    char* w = (char*)workspace;
-    CloudInfo* info = (CloudInfo*)w; w += align256(sizeof(CloudInfo) * nb);
-    unsigned long long* keys = (unsigned long long*)w; w += align256(8ull * n_pad);
-    unsigned* vals = (unsigned*)w; w += align256(4ull * n_pad);
-    int* block_off = (int*)w;
-    hipLaunchKernelGGL(cloud_info_kernel, dim3(nb), dim3(1024), 0, st, points, lengths, nb, dl, origin_mode, info, status);
+    const SubsampleWs w = subsample_carve(workspace, n, nb);
+    hipLaunchKernelGGL(cloud_info_kernel, dim3(nb), dim3(1024), 0, st, points, lengths, nb, dl, origin_mode, w.info, status);
     DR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(point_key_kernel, dim3((n_pad + 255) / 256), dim3(256), 0, st, points, n, n_pad, info, nb, dl, keys, vals);
+    hipLaunchKernelGGL(point_key_kernel, dim3((w.n_pad + 255) / 256), dim3(256), 0, st, points, n, w.n_pad, w.info, nb, dl, w.keys, w.vals);
     DR_LAUNCH_CHECK();
-    int rc = launch_bitonic_sort(keys, vals, n_pad, st);
+    int rc = launch_bitonic_sort(w.keys, w.vals, w.n_pad, st);
     if (rc != DR_OK) return rc;
-    hipLaunchKernelGGL(heads_count_kernel, dim3(nblk), dim3(SC_BLOCK), 0, st, keys, n, block_off);
+    hipLaunchKernelGGL(heads_count_kernel, dim3(w.nblk), dim3(SC_BLOCK), 0, st, w.keys, n, w.block_off);
     DR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(heads_blockscan_kernel, dim3(1), dim3(SC_BLOCK), 0, st, block_off, nblk, out_total);
+    hipLaunchKernelGGL(heads_blockscan_kernel, dim3(1), dim3(SC_BLOCK), 0, st, w.block_off, w.nblk, out_total);
     DR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(barycentre_kernel, dim3(nblk), dim3(SC_BLOCK), 0, st, keys, vals, n, block_off, points, out_points, out_lengths);
+    hipLaunchKernelGGL(barycentre_kernel, dim3(w.nblk), dim3(SC_BLOCK), 0, st, w.keys, w.vals, n, w.block_off, points, out_points, out_lengths);
     DR_LAUNCH_CHECK();
     return DR_OK;
 }
@@ -521,40 +520,29 @@ int dr_grid_subsample_vision3d_f32(int n, int nb, const float* points, const int
 }
 
 size_t dr_radius_neighbors_workspace_bytes(int nq, int ns, int nb) {
-    if (ns <= 0 || nb <= 0) return 0;
-    const int n_pad = next_pow2(ns);
-    return 2 * align256(sizeof(CloudInfo) * nb) + align256(8ull * n_pad) + align256(4ull * n_pad) + align256(16ull * ns) +
-           align256(sizeof(CellSlot) * 2ull * n_pad);
+    return (ns <= 0 || nb <= 0) ? 0 : ball_carve(nullptr, ns, nb).bytes;
 }
 
 // the supports sorted by cell and their cell table in `workspace` (dr_radius_neighbors_workspace_bytes; ns > 0) -> *B
 static int build_ball_index(int nq, int ns, int nb, const float* queries, const float* supports, const int32_t* q_lengths,
                             const int32_t* s_lengths, float radius, int32_t* status, void* workspace, hipStream_t st, BallArgs* B) {
-    const int n_pad = next_pow2(ns);
-    char* w = (char*)workspace;
-    CloudInfo* q_info = (CloudInfo*)w; w += align256(sizeof(CloudInfo) * nb);
-    CloudInfo* s_info = (CloudInfo*)w; w += align256(sizeof(CloudInfo) * nb);
-    unsigned long long* keys = (unsigned long long*)w; w += align256(8ull * n_pad);
-    unsigned* vals = (unsigned*)w; w += align256(4ull * n_pad);
-    float4* sorted = (float4*)w; w += align256(16ull * ns);
-    CellSlot* tab = (CellSlot*)w;
-    const unsigned tab_size = 2u * (unsigned)n_pad;
+    const BallWs w = ball_carve(workspace, ns, nb);
     const float cell = radius * (1.0f + 1.0f / 128.0f);
-    B->queries = queries; B->nq = nq; B->q_info = q_info; B->s_info = s_info; B->nb = nb; B->tab = tab; B->mask = tab_size - 1;
-    B->sorted = sorted; B->ns = ns; B->cell = cell; B->r2 = radius * radius;
+    B->queries = queries; B->nq = nq; B->q_info = w.q_info; B->s_info = w.s_info; B->nb = nb; B->tab = w.tab; B->mask = w.tab_size - 1;
+    B->sorted = w.sorted; B->ns = ns; B->cell = cell; B->r2 = radius * radius;
     // (the query table only provides the cloud boundaries of the stacked queries)
-    hipLaunchKernelGGL(cloud_info_kernel, dim3(nb), dim3(1024), 0, st, queries, q_lengths, nb, cell, CL_ORIGIN_MIN, q_info, status);
+    hipLaunchKernelGGL(cloud_info_kernel, dim3(nb), dim3(1024), 0, st, queries, q_lengths, nb, cell, CL_ORIGIN_MIN, w.q_info, status);
     DR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(cloud_info_kernel, dim3(nb), dim3(1024), 0, st, supports, s_lengths, nb, cell, CL_ORIGIN_MIN, s_info, status);
+    hipLaunchKernelGGL(cloud_info_kernel, dim3(nb), dim3(1024), 0, st, supports, s_lengths, nb, cell, CL_ORIGIN_MIN, w.s_info, status);
     DR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(point_key_kernel, dim3((n_pad + 255) / 256), dim3(256), 0, st, supports, ns, n_pad, s_info, nb, cell, keys, vals);
+    hipLaunchKernelGGL(point_key_kernel, dim3((w.n_pad + 255) / 256), dim3(256), 0, st, supports, ns, w.n_pad, w.s_info, nb, cell, w.keys, w.vals);
     DR_LAUNCH_CHECK();
-    int rc = launch_bitonic_sort(keys, vals, n_pad, st);
+    int rc = launch_bitonic_sort(w.keys, w.vals, w.n_pad, st);
     if (rc != DR_OK) return rc;
-    hipLaunchKernelGGL(gather_sorted_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, vals, ns, supports, sorted);
+    hipLaunchKernelGGL(gather_sorted_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, w.vals, ns, supports, w.sorted);
     DR_LAUNCH_CHECK();
-    DR_HIP_CHECK(hipMemsetAsync(tab, 0xFF, sizeof(CellSlot) * (size_t)tab_size, st));
-    hipLaunchKernelGGL(cell_table_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, keys, ns, tab, tab_size - 1);
+    DR_HIP_CHECK(hipMemsetAsync(w.tab, 0xFF, sizeof(CellSlot) * (size_t)w.tab_size, st));
+    hipLaunchKernelGGL(cell_table_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, w.keys, ns, w.tab, w.tab_size - 1);
     DR_LAUNCH_CHECK();
     return DR_OK;
 }

@@ -15,6 +15,7 @@
 #endif
 #include <stddef.h>
 #include <stdint.h>
+#include "carve.h"               // align256
 
 namespace dr {
 
@@ -58,14 +59,13 @@ __host__ __device__ inline int cg_stage_count(int n, int k0) {
 struct CgMatchCarve {
     size_t nn_st, d2_st, nn_ts, bytes;
 };
-__host__ __device__ inline size_t cg_align256(size_t b) { return (b + 255) & ~(size_t)255; }
 __host__ __device__ inline CgMatchCarve cg_match_carve(int ns, int nt) {
     CgMatchCarve c;
     const size_t s = ns > 0 ? (size_t)ns : 0, t = nt > 0 ? (size_t)nt : 0;
     c.nn_st = 0;
-    c.d2_st = c.nn_st + cg_align256(s * sizeof(int32_t));
-    c.nn_ts = c.d2_st + cg_align256(s * sizeof(float));
-    c.bytes = c.nn_ts + cg_align256(t * sizeof(int32_t));
+    c.d2_st = c.nn_st + align256(s * sizeof(int32_t));
+    c.nn_ts = c.d2_st + align256(s * sizeof(float));
+    c.bytes = c.nn_ts + align256(t * sizeof(int32_t));
     return c;
 }
 

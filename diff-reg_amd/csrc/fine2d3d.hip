@@ -141,12 +141,8 @@ int dr_patch_similarity_f32(int P, int Ki, int Kc, int C, const float* img_feats
     return DR_OK;
 }
 
-static int uq_pad(int n) { int p = 1; while (p < n) p <<= 1; return p; }
-
 size_t dr_unique_pairs_workspace_bytes(int n) {
-    if (n < 1) return 256;
-    const size_t np = (size_t)uq_pad(n);
-    return dr::align256(np * 8) + dr::align256(np * 4);
+    return n < 1 ? 256 : dr::sort_carve(nullptr, n).bytes;
 }
 
 int dr_unique_pairs_i64(int n, const int64_t* first, const int64_t* second, long long multiplier, int64_t* unique_keys, int32_t* count,
@@ -155,15 +151,13 @@ int dr_unique_pairs_i64(int n, const int64_t* first, const int64_t* second, long
     hipStream_t st = (hipStream_t)stream;
     if (n == 0) { DR_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(int32_t), st)); return DR_OK; }
     if (workspace_bytes < dr_unique_pairs_workspace_bytes(n)) return DR_EWORKSPACE;
-    const int n_pad = uq_pad(n);
-    unsigned long long* keys = (unsigned long long*)workspace;
-    unsigned* vals = (unsigned*)((char*)workspace + dr::align256((size_t)n_pad * 8));
-    hipLaunchKernelGGL(dr::make_keys_kernel, dim3((n_pad + 255) / 256), dim3(256), 0, st, n, n_pad, (const long long*)first, (const long long*)second,
-                       multiplier, keys, vals);
+    const dr::SortWs w = dr::sort_carve(workspace, n);
+    hipLaunchKernelGGL(dr::make_keys_kernel, dim3((w.n_pad + 255) / 256), dim3(256), 0, st, n, w.n_pad, (const long long*)first, (const long long*)second,
+                       multiplier, w.keys, w.vals);
     DR_LAUNCH_CHECK();
-    const int rc = dr::launch_bitonic_sort(keys, vals, n_pad, st);
+    const int rc = dr::launch_bitonic_sort(w.keys, w.vals, w.n_pad, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(dr::unique_sorted_kernel, dim3(1), dim3(1024), 0, st, n, keys, (long long*)unique_keys, count);
+    hipLaunchKernelGGL(dr::unique_sorted_kernel, dim3(1), dim3(1024), 0, st, n, w.keys, (long long*)unique_keys, count);
     DR_LAUNCH_CHECK();
     return DR_OK;
 }

@@ -3,7 +3,7 @@
 // on-chip form and the strided walk of the streaming form, the LDS exchange between the waves, the padded outputs, and the workspace that the
 // size query and the entries share.  Outside hipcc the file compiles as plain C++.
 #pragma once
-#include "nonrigid_index.h"      // nr_slice_ok, nr_align256
+#include "nonrigid_index.h"      // nr_slice_ok, align256
 
 namespace dr {
 
@@ -57,7 +57,7 @@ __host__ __device__ inline size_t fps_out_coord(int p, int cap, int k, int c) { 
 __host__ __device__ inline size_t fps_workspace_bytes(int n_points, int max_points, bool force_streaming) {
     if (n_points <= 0 || max_points <= 0) return 0;
     if (fps_fits_onchip(max_points) && !force_streaming) return 0;
-    return nr_align256((size_t)n_points * sizeof(float));
+    return align256((size_t)n_points * sizeof(float));
 }
 
 }  // namespace dr

@@ -4,7 +4,7 @@
 // on-chip capacity, the padded output tables, the chunked scan of the edge list, and the workspace that the size query and the entry share.
 // Outside hipcc the file compiles as plain C++.
 #pragma once
-#include "nonrigid_index.h"      // NR_TILE, NR_LDS_BYTES, nr_align256, nr_grid_bound
+#include "nonrigid_index.h"      // NR_TILE, NR_LDS_BYTES, align256, nr_grid_bound
 
 namespace dr {
 
@@ -109,10 +109,10 @@ __host__ __device__ inline GeoCarve geo_carve(int n_points, int n_nodes, int max
     const size_t n = n_points > 0 ? (size_t)n_points : 0, m = n_nodes > 0 ? (size_t)n_nodes : 0;
     const size_t s = max_points > 0 ? (size_t)max_points : 0, d = max_degree > 0 ? (size_t)max_degree : 0;
     c.mark = 0;
-    c.deg = c.mark + nr_align256(n * sizeof(int32_t));
-    c.adj = c.deg + nr_align256(n * sizeof(int32_t));
-    c.reach = c.adj + nr_align256(n * d * sizeof(GeoAdj));
-    c.bytes = c.reach + nr_align256(m * s * sizeof(uint32_t));
+    c.deg = c.mark + align256(n * sizeof(int32_t));
+    c.adj = c.deg + align256(n * sizeof(int32_t));
+    c.reach = c.adj + align256(n * d * sizeof(GeoAdj));
+    c.bytes = c.reach + align256(m * s * sizeof(uint32_t));
     return c;
 }
 

@@ -17,6 +17,7 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "carve.h"               // align256
 
 namespace dr {
 
@@ -125,18 +126,17 @@ __host__ __device__ inline int it_saturate_i32(long long v) { return v > 0x7ffff
 struct ItCarve {
     size_t pts, win, rpx, pnt, pix, off, sums, bytes;
 };
-__host__ __device__ inline size_t it_align256(size_t b) { return (b + 255) & ~(size_t)255; }
 __host__ __device__ inline ItCarve it_carve(int H, int W, int N) {
     ItCarve c;
     const size_t n = N > 0 ? (size_t)N : 0, p = (H > 0 && W > 0) ? (size_t)H * (size_t)W : 0, m = n > p ? n : p;
     c.pts = 0;
-    c.win = c.pts + it_align256(n * 4 * sizeof(double));
-    c.rpx = c.win + it_align256(n * 4 * sizeof(int32_t));
-    c.pnt = c.rpx + it_align256(n * 2 * sizeof(int32_t));
-    c.pix = c.pnt + it_align256(n * sizeof(int32_t));
-    c.off = c.pix + it_align256(p * sizeof(int32_t));
-    c.sums = c.off + it_align256(m * sizeof(int64_t));
-    c.bytes = c.sums + it_align256((size_t)it_scan_chunks((long long)m) * sizeof(int64_t));
+    c.win = c.pts + align256(n * 4 * sizeof(double));
+    c.rpx = c.win + align256(n * 4 * sizeof(int32_t));
+    c.pnt = c.rpx + align256(n * 2 * sizeof(int32_t));
+    c.pix = c.pnt + align256(n * sizeof(int32_t));
+    c.off = c.pix + align256(p * sizeof(int32_t));
+    c.sums = c.off + align256(m * sizeof(int64_t));
+    c.bytes = c.sums + align256((size_t)it_scan_chunks((long long)m) * sizeof(int64_t));
     return c;
 }
 

@@ -397,7 +397,7 @@ int dr_radius_pairs_ragged_f32(int P, int ns, int nt, const float* src, const in
     hipStream_t st = (hipStream_t)stream;
     char* w = (char*)workspace;
     PairsArgs A;
-    A.P = P; A.ns = ns; A.nt = nt; A.n_pad = nt > 0 ? it3_next_pow2(nt) : 0;
+    A.P = P; A.ns = ns; A.nt = nt; A.n_pad = nt > 0 ? next_pow2(nt) : 0;
     A.src = src; A.s_off = s_offsets; A.tgt = tgt; A.t_off = t_offsets; A.transforms = transforms;
     A.cell = radius * (1.0f + 1.0f / 128.0f); A.r2 = radius * radius;
     A.moved = (float*)(w + c.moved); A.row_start = (long long*)(w + c.row_start); A.origin = (float4*)(w + c.origin);

@@ -17,6 +17,7 @@
 #include <math.h>
 #include <stddef.h>
 #include <stdint.h>
+#include "carve.h"               // align256, next_pow2
 
 namespace dr {
 
@@ -95,12 +96,6 @@ __host__ __device__ inline long long it3_room(long long lo, long long hi, long l
 // a count as the int32 the caller reads: saturated at 2^31 - 1
 __host__ __device__ inline int32_t it3_saturate(long long n) { return n > 0x7fffffffLL ? 0x7fffffff : (n < 0 ? 0 : (int32_t)n); }
 
-__host__ __device__ inline int it3_next_pow2(int n) {
-    int p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
 // workgroups of a one-row-per-thread launch over n rows (at least one: it also serves an empty side)
 __host__ __device__ inline unsigned it3_blocks(int n, int per) { return n <= 0 ? 1u : (unsigned)((n + per - 1) / per); }
 
@@ -109,18 +104,17 @@ __host__ __device__ inline unsigned it3_blocks(int n, int per) { return n <= 0 ?
 struct It3PairsCarve {
     size_t moved, row_start, origin, keys, vals, sorted, bytes;
 };
-__host__ __device__ inline size_t it3_align256(size_t b) { return (b + 255) & ~(size_t)255; }
 __host__ __device__ inline It3PairsCarve it3_pairs_carve(int P, int ns, int nt) {
     It3PairsCarve c;
     const size_t p = P > 0 ? (size_t)P : 0, s = ns > 0 ? (size_t)ns : 0, t = nt > 0 ? (size_t)nt : 0;
-    const size_t pad = nt > 0 ? (size_t)it3_next_pow2(nt) : 0;
+    const size_t pad = nt > 0 ? (size_t)next_pow2(nt) : 0;
     c.moved = 0;
-    c.row_start = c.moved + it3_align256(s * 3 * sizeof(float));
-    c.origin = c.row_start + it3_align256(s * sizeof(int64_t));
-    c.keys = c.origin + it3_align256(p * 4 * sizeof(float));
-    c.vals = c.keys + it3_align256(pad * sizeof(unsigned long long));
-    c.sorted = c.vals + it3_align256(pad * sizeof(uint32_t));
-    c.bytes = c.sorted + it3_align256(t * 4 * sizeof(float));
+    c.row_start = c.moved + align256(s * 3 * sizeof(float));
+    c.origin = c.row_start + align256(s * sizeof(int64_t));
+    c.keys = c.origin + align256(p * 4 * sizeof(float));
+    c.vals = c.keys + align256(pad * sizeof(unsigned long long));
+    c.sorted = c.vals + align256(pad * sizeof(uint32_t));
+    c.bytes = c.sorted + align256(t * 4 * sizeof(float));
     return c;
 }
 

@@ -1,5 +1,6 @@
 // kernels.h -- internal launch interface between the .hip translation units of libdiffreg_hip.
 #pragma once
+#include "carve.h"
 #include "common.h"
 
 namespace dr {

@@ -4,7 +4,7 @@
 // the [rows, k] outputs, and the partials of the two-stage reductions that the size queries and the entries share.  Outside hipcc the file
 // compiles as plain C++.
 #pragma once
-#include "nonrigid_index.h"      // nr_slice_ok, nr_align256
+#include "nonrigid_index.h"      // nr_slice_ok, align256
 
 namespace dr {
 
@@ -102,11 +102,11 @@ __host__ __device__ inline size_t knn_out(size_t row, int k, int j) { return row
 __host__ __device__ inline size_t knn_partial(long long block, int slots, int s) { return (size_t)block * (size_t)slots + (size_t)s; }
 __host__ __device__ inline size_t nn_stats_workspace_bytes(int P, int n_q) {
     if (P <= 0) return 0;
-    return nr_align256((size_t)knn_grid_bound(n_q, P, KNN_BLOCK) * NN_SLOTS * sizeof(double));
+    return align256((size_t)knn_grid_bound(n_q, P, KNN_BLOCK) * NN_SLOTS * sizeof(double));
 }
 __host__ __device__ inline size_t flow_metrics_workspace_bytes(int P, int n) {
     if (P <= 0) return 0;
-    return nr_align256((size_t)knn_grid_bound(n, P, FLOW_BLOCK) * FLOW_SLOTS * sizeof(double));
+    return align256((size_t)knn_grid_bound(n, P, FLOW_BLOCK) * FLOW_SLOTS * sizeof(double));
 }
 // the flow kernel's cross-wave exchange: slot s of wave w
 __host__ __device__ inline int flow_lds_word(int w, int s) { return w * FLOW_SLOTS + s; }

@@ -4,7 +4,7 @@
 // and hypotheses it serves, the chunk scan of a problem's patch ids, the LDS tiles of the row sums and the carve of the two workspaces.
 // Outside hipcc the file compiles as plain C++.
 #pragma once
-#include "knn_index.h"           // knn_blocks, knn_grid_bound, knn_block_to_pair, knn_row, knn_coord, knn_local_coord; nr_slice_ok, nr_align256
+#include "knn_index.h"           // knn_blocks, knn_grid_bound, knn_block_to_pair, knn_row, knn_coord, knn_local_coord; nr_slice_ok, align256
 
 namespace dr {
 
@@ -76,16 +76,16 @@ __host__ __device__ inline LgrCarve lgr_carve(int P, int n_corr) {
     LgrCarve c;
     const size_t n = (size_t)(n_corr < 0 ? 0 : n_corr), p = (size_t)(P < 0 ? 0 : P);
     size_t at = 0;
-    c.starts = at;      at += nr_align256(n * sizeof(int32_t));
-    c.chunk_lo = at;    at += nr_align256(n * sizeof(int32_t));
-    c.chunk_hi = at;    at += nr_align256(n * sizeof(int32_t));
-    c.n_chunks = at;    at += nr_align256(p * sizeof(int32_t));
-    c.chunk_off = at;   at += nr_align256((p + 1) * sizeof(int32_t));
-    c.dense_lo = at;    at += nr_align256(n * sizeof(int32_t));
-    c.dense_hi = at;    at += nr_align256(n * sizeof(int32_t));
-    c.dense_p = at;     at += nr_align256(n * sizeof(int32_t));
-    c.counts = at;      at += nr_align256(n * sizeof(int32_t));
-    c.transforms = at;  at += nr_align256(n * 16 * sizeof(float));
+    c.starts = at;      at += align256(n * sizeof(int32_t));
+    c.chunk_lo = at;    at += align256(n * sizeof(int32_t));
+    c.chunk_hi = at;    at += align256(n * sizeof(int32_t));
+    c.n_chunks = at;    at += align256(p * sizeof(int32_t));
+    c.chunk_off = at;   at += align256((p + 1) * sizeof(int32_t));
+    c.dense_lo = at;    at += align256(n * sizeof(int32_t));
+    c.dense_hi = at;    at += align256(n * sizeof(int32_t));
+    c.dense_p = at;     at += align256(n * sizeof(int32_t));
+    c.counts = at;      at += align256(n * sizeof(int32_t));
+    c.transforms = at;  at += align256(n * 16 * sizeof(float));
     c.total = P <= 0 ? 0 : at;
     return c;
 }
@@ -114,8 +114,8 @@ struct EigCarve {
 __host__ __device__ inline EigCarve eig_carve(int P, int n) {
     EigCarve c;
     size_t at = 0;
-    c.y = at;       at += nr_align256((size_t)(n < 0 ? 0 : n) * sizeof(float));
-    c.done = at;    at += nr_align256((size_t)(P < 0 ? 0 : P) * sizeof(int32_t));
+    c.y = at;       at += align256((size_t)(n < 0 ? 0 : n) * sizeof(float));
+    c.done = at;    at += align256((size_t)(P < 0 ? 0 : P) * sizeof(int32_t));
     c.total = P <= 0 ? 0 : at;
     return c;
 }

@@ -1,5 +1,5 @@
 // loop_common.h -- host helpers shared by the two denoise loops (loop.hip, loop2d3d.hip), the single-op entries (api.hip) and the training
-// entry points: the carving of caller memory, the two-sided token view (Sides) and the ONE layer schedule of both denoisers, the plane
+// entry points: the carving of caller memory (carve.h), the two-sided token view (Sides) and the ONE layer schedule of both denoisers, the plane
 // path's small types, its packed-weight plumbing and its on / off rule, a one-problem GEMM launch, and reverse_sampling(), the ONE driver of
 // the reverse-diffusion steps -- both loops honour the dr_loop_trace / teacher-forcing contract through it.
 #pragma once
@@ -9,20 +9,6 @@
 #include "pgemm.h"
 
 namespace dr {
-
-static inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
-// hands out consecutive arrays of caller memory, each starting at a multiple of 256 bytes; a null base only counts (`off` = bytes so far)
-struct Carver {
-    char* base; size_t off;
-    explicit Carver(void* p) : base((char*)p), off(0) {}
-    template <typename T> T* take(size_t n) {
-        off = align256(off);
-        T* r = base ? reinterpret_cast<T*>(base + off) : nullptr;
-        off += n * sizeof(T);
-        return r;
-    }
-};
 
 // a token tensor of the plane path: fp32 rows [T, C] (the residual stream; may be null), plane image (first side, then second side, each
 // padded to 128 rows) and per-row bounds [T]

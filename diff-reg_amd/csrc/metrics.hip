@@ -196,6 +196,11 @@ struct RsArgs {
     double thr2; int iters; uint64_t seed; RsBest* blk; int nblk; double* pts;
     double* rot; double* trn; double* fitness; double* rmse; int* best_iter;
 };
+// the workspace: every pair's best hypothesis per workgroup of RS_BLOCK, then its gathered correspondences [P, cap, 6]
+static size_t ransac_carve(void* base, RsArgs& A, int P, int cap, int iters) {
+    Carver c(base); A.nblk = (iters + RS_BLOCK - 1) / RS_BLOCK; A.blk = c.take<RsBest>((size_t)P * A.nblk); A.pts = c.take<double>((size_t)P * cap * 6);
+    return c.off;
+}
 
 // rigid fit of the three correspondences of hypothesis `it` (Eigen::umeyama without scaling:
 // sigma = 1/3 sum (y - ybar)(x - xbar)^T = U D V^T, R = U diag(1,1,det U det V) V^T, t = ybar - R xbar)
@@ -472,8 +477,7 @@ int dr_nrfmr_f32(int P, int cap, int N, int M, const int64_t* matches, const int
 }
 
 size_t dr_ransac_workspace_bytes(int P, int cap, int iters) {
-    if (P <= 0 || iters <= 0 || cap <= 0) return 0;
-    return (size_t)P * ((iters + RS_BLOCK - 1) / RS_BLOCK) * sizeof(RsBest) + (size_t)P * cap * 6 * sizeof(double);
+    RsArgs A; return (P <= 0 || iters <= 0 || cap <= 0) ? 0 : ransac_carve(nullptr, A, P, cap, iters);
 }
 
 int dr_ransac_corr_f64(int P, int cap, int N, int M, const int64_t* matches, const int32_t* count, const float* s_pcd,
@@ -489,8 +493,7 @@ int dr_ransac_corr_f64(int P, int cap, int N, int M, const int64_t* matches, con
     A.matches = (const long long*)matches; A.count = count; A.cap = cap; A.N = N; A.M = M;
     A.s_pcd = s_pcd; A.t_pcd = t_pcd; A.pair_ids = (const long long*)pair_ids;
     A.thr2 = distance_thr * distance_thr; A.iters = iters; A.seed = seed;
-    A.blk = (RsBest*)workspace; A.nblk = (iters + RS_BLOCK - 1) / RS_BLOCK;
-    A.pts = (double*)((char*)workspace + (size_t)P * A.nblk * sizeof(RsBest));
+    ransac_carve(workspace, A, P, cap, iters);
     A.rot = rot; A.trn = trn; A.fitness = fitness; A.rmse = inlier_rmse; A.best_iter = best_iter;
     hipLaunchKernelGGL(ransac_gather_kernel, dim3((cap + 255) / 256, P), dim3(256), 0, st, A);
     DR_LAUNCH_CHECK();

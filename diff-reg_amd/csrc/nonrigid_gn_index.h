@@ -61,12 +61,12 @@ __host__ __device__ inline NrGnCarve nrg_carve(int P, int n_corr, int n_nodes, i
     const size_t k = K > 0 ? (size_t)K : 0;
     c.ld = 6 * (max_nodes > 0 ? max_nodes : 0);
     c.n6 = c.lists.bytes;
-    c.rot = c.n6 + nr_align256(p * 4);
-    c.trn = c.rot + nr_align256(m * 9 * 4);
-    c.jac = c.trn + nr_align256(m * 3 * 4);
-    c.b = c.jac + nr_align256(n * k * 4 * 8);
-    c.A = c.b + nr_align256(p * (size_t)c.ld * 8);
-    c.bytes = c.A + nr_align256(p * (size_t)c.ld * (size_t)c.ld * 8);
+    c.rot = c.n6 + align256(p * 4);
+    c.trn = c.rot + align256(m * 9 * 4);
+    c.jac = c.trn + align256(m * 3 * 4);
+    c.b = c.jac + align256(n * k * 4 * 8);
+    c.A = c.b + align256(p * (size_t)c.ld * 8);
+    c.bytes = c.A + align256(p * (size_t)c.ld * (size_t)c.ld * 8);
     return c;
 }
 

@@ -16,6 +16,7 @@
 #endif
 #include <stddef.h>
 #include <stdint.h>
+#include "carve.h"               // align256
 
 namespace dr {
 
@@ -69,8 +70,6 @@ __host__ __device__ inline int nr_bitmap_words(int n_nodes) { return n_nodes <= 
 __host__ __device__ inline size_t nr_bitmap_word(int m0, int i, int words, int j) { return ((size_t)m0 + (size_t)i) * (size_t)words + (size_t)(j >> 5); }
 __host__ __device__ inline uint32_t nr_bitmap_bit(int j) { return 1u << (j & 31); }
 
-__host__ __device__ inline size_t nr_align256(size_t b) { return (b + 255) & ~(size_t)255; }
-
 // the workspace of dr_ed_graph_f32: the bit map, then per node the number of set bits of its row and the sum of its row's skinning weights
 struct NrGraphCarve {
     size_t bitmap, row_count, row_sum, bytes;
@@ -79,9 +78,9 @@ __host__ __device__ inline NrGraphCarve nr_graph_carve(int n_nodes, int max_node
     NrGraphCarve c;
     const size_t m = n_nodes > 0 ? (size_t)n_nodes : 0;
     c.bitmap = 0;
-    c.row_count = c.bitmap + nr_align256(m * (size_t)nr_bitmap_words(max_nodes) * sizeof(uint32_t));
-    c.row_sum = c.row_count + nr_align256(m * sizeof(int32_t));
-    c.bytes = c.row_sum + nr_align256(m * sizeof(double));
+    c.row_count = c.bitmap + align256(m * (size_t)nr_bitmap_words(max_nodes) * sizeof(uint32_t));
+    c.row_sum = c.row_count + align256(m * sizeof(int32_t));
+    c.bytes = c.row_sum + align256(m * sizeof(double));
     return c;
 }
 
@@ -130,16 +129,16 @@ __host__ __device__ inline NrSolveCarve nr_solve_carve(int P, int n_corr, int n_
     const size_t p = P > 0 ? (size_t)P : 0, n = n_corr > 0 ? (size_t)n_corr : 0, m = n_nodes > 0 ? (size_t)n_nodes : 0;
     const size_t e = n_edges > 0 ? (size_t)n_edges : 0, k = K > 0 ? (size_t)K : 0;
     c.resid = 0;
-    c.anchor = c.resid + nr_align256(n * 3 * 8);
-    c.weight = c.anchor + nr_align256(n * k * 4);
-    c.lm_ptr = c.weight + nr_align256(n * k * 4);
-    c.lm_corr = c.lm_ptr + nr_align256((m + p) * 4);
-    c.lm_pw = c.lm_corr + nr_align256(n * k * 4);
-    c.out_ptr = c.lm_pw + nr_align256(n * k * 16);
-    c.out_adj = c.out_ptr + nr_align256((m + p) * 4);
-    c.in_ptr = c.out_adj + nr_align256(e * 8);
-    c.in_adj = c.in_ptr + nr_align256((m + p) * 4);
-    c.bytes = c.in_adj + nr_align256(e * 8);
+    c.anchor = c.resid + align256(n * 3 * 8);
+    c.weight = c.anchor + align256(n * k * 4);
+    c.lm_ptr = c.weight + align256(n * k * 4);
+    c.lm_corr = c.lm_ptr + align256((m + p) * 4);
+    c.lm_pw = c.lm_corr + align256(n * k * 4);
+    c.out_ptr = c.lm_pw + align256(n * k * 16);
+    c.out_adj = c.out_ptr + align256((m + p) * 4);
+    c.in_ptr = c.out_adj + align256(e * 8);
+    c.in_adj = c.in_ptr + align256((m + p) * 4);
+    c.bytes = c.in_adj + align256(e * 8);
     return c;
 }
 

@@ -17,8 +17,6 @@ constexpr int PT_MAX_LIMIT = 128;      // point_limit of dr_point_to_node_partit
 constexpr int PT_NODE_CHUNK = 1024;    // nodes staged in LDS at a time (12 KB)
 constexpr int NC_MAX_KI = 256, NC_MAX_KC = 128;
 
-int next_pow2(int n) { int p = 1; while (p < n) p <<= 1; return p; }
-
 __device__ __forceinline__ float sq_dist3(float ax, float ay, float az, float bx, float by, float bz) {
     const float dx = ax - bx, dy = ay - by, dz = az - bz;
     return dx * dx + dy * dy + dz * dz;
@@ -412,9 +410,7 @@ struct RadiusPred {
 extern "C" {
 
 size_t dr_point_to_node_partition_workspace_bytes(int Nf) {
-    if (Nf < 1) return 256;
-    const size_t np = (size_t)dr::next_pow2(Nf);
-    return dr::align256(np * 8) + dr::align256(np * 4);
+    return Nf < 1 ? 256 : dr::sort_carve(nullptr, Nf).bytes;
 }
 
 int dr_point_to_node_partition_f32(int Nf, int Nc, int point_limit, const float* points, const float* nodes, int64_t* point_to_node, int64_t* node_sizes,
@@ -426,15 +422,13 @@ int dr_point_to_node_partition_f32(int Nf, int Nc, int point_limit, const float*
     if (point_limit > dr::PT_MAX_LIMIT || Nf > (1 << 28)) return DR_ENOSUP;
     if (workspace_bytes < dr_point_to_node_partition_workspace_bytes(Nf)) return DR_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    const int n_pad = dr::next_pow2(Nf);
-    unsigned long long* keys = (unsigned long long*)workspace;
-    unsigned* vals = (unsigned*)((char*)workspace + dr::align256((size_t)n_pad * 8));
+    const dr::SortWs w = dr::sort_carve(workspace, Nf);
     DR_HIP_CHECK(hipMemsetAsync(max_points_per_node, 0, sizeof(int32_t), st));
-    hipLaunchKernelGGL(dr::pt_assign_kernel, dim3((n_pad + 255) / 256), dim3(256), 0, st, Nf, Nc, n_pad, points, nodes, (long long*)point_to_node, keys, vals);
+    hipLaunchKernelGGL(dr::pt_assign_kernel, dim3((w.n_pad + 255) / 256), dim3(256), 0, st, Nf, Nc, w.n_pad, points, nodes, (long long*)point_to_node, w.keys, w.vals);
     DR_LAUNCH_CHECK();
-    const int rc = dr::launch_bitonic_sort(keys, vals, n_pad, st);
+    const int rc = dr::launch_bitonic_sort(w.keys, w.vals, w.n_pad, st);
     if (rc) return rc;
-    hipLaunchKernelGGL(dr::pt_gather_kernel, dim3((Nc + 3) / 4), dim3(256), 0, st, Nf, Nc, point_limit, keys, vals, (long long*)node_sizes, node_masks,
+    hipLaunchKernelGGL(dr::pt_gather_kernel, dim3((Nc + 3) / 4), dim3(256), 0, st, Nf, Nc, point_limit, w.keys, w.vals, (long long*)node_sizes, node_masks,
                        (long long*)node_knn_indices, node_knn_masks, (int*)max_points_per_node);
     DR_LAUNCH_CHECK();
     return DR_OK;
@@ -456,8 +450,7 @@ int dr_patchify_f32(int H_f, int W_f, int H_c, int W_c, int stride, const float*
 }
 
 size_t dr_node_correspondences_2d3d_workspace_bytes(int M, int N, int Kc, long long capacity) {
-    if (M < 1 || N < 1 || Kc < 1 || capacity < 1) return 256;
-    return dr::align256((size_t)N * Kc * 12) + dr::align256((size_t)M * 4) * 2 + dr::align256((size_t)N * 4) + 4 * dr::align256((size_t)capacity * 4);
+    return (M < 1 || N < 1 || Kc < 1 || capacity < 1) ? 256 : dr::node_corr_carve(nullptr, M, N, Kc, (size_t)capacity).bytes;
 }
 
 int dr_node_correspondences_2d3d_f32(int M, int Ki, int N, int Kc, const uint8_t* img_masks, const float* img_knn_points, const float* img_knn_points_da,
@@ -473,35 +466,26 @@ int dr_node_correspondences_2d3d_f32(int M, int Ki, int N, int Kc, const uint8_t
     if (Ki > dr::NC_MAX_KI || Kc > dr::NC_MAX_KC || capacity > (1ll << 30) || (long long)M * N > (1ll << 30)) return DR_ENOSUP;
     if (workspace_bytes < dr_node_correspondences_2d3d_workspace_bytes(M, N, Kc, capacity)) return DR_EWORKSPACE;
     hipStream_t st = (hipStream_t)stream;
-    char* w = (char*)workspace;
-    float* pcd_moved = (float*)w;      w += dr::align256((size_t)N * Kc * 12);
-    float* img_rad = (float*)w;        w += dr::align256((size_t)M * 4);
-    int* row_count = (int*)w;          w += dr::align256((size_t)M * 4);
-    float* pcd_rad = (float*)w;        w += dr::align256((size_t)N * 4);
-    int* cand_i = (int*)w;             w += dr::align256((size_t)capacity * 4);
-    int* cand_j = (int*)w;             w += dr::align256((size_t)capacity * 4);
-    float* ratio_img = (float*)w;      w += dr::align256((size_t)capacity * 4);
-    float* ratio_pcd = (float*)w;
+    const dr::NodeCorrWs w = dr::node_corr_carve(workspace, M, N, Kc, (size_t)capacity);
     hipLaunchKernelGGL(dr::nc_centers_kernel, dim3(M + N), dim3(64), 0, st, M, Ki, N, Kc, img_knn_points, img_knn_points_da, img_knn_masks, img_knn_masks_da,
-                       pcd_knn_points, pcd_knn_masks, transform, pcd_moved, img_centers, img_centers_da, pcd_centers, img_rad, pcd_rad);
+                       pcd_knn_points, pcd_knn_masks, transform, w.pcd_moved, img_centers, img_centers_da, pcd_centers, w.img_rad, w.pcd_rad);
     DR_LAUNCH_CHECK();
-    dr::NcCandidate pred{img_centers, pcd_centers, img_rad, pcd_rad, img_masks, pcd_masks, pos_radius_3d};
+    dr::NcCandidate pred{img_centers, pcd_centers, w.img_rad, w.pcd_rad, img_masks, pcd_masks, pos_radius_3d};
     // counts[1], [2] = candidates kept / found (found > capacity: the list was cut and the caller must not use the result); counts[0] = pairs written
-    const int rc = dr::compact_pairs(M, N, pred, row_count, capacity, cand_i, cand_j, (int*)counts + 1, st);
+    const int rc = dr::compact_pairs(M, N, pred, w.row_count, capacity, w.cand_i, w.cand_j, (int*)counts + 1, st);
     if (rc) return rc;
     const int grid = (int)(capacity < 16384 ? capacity : 16384);
-    hipLaunchKernelGGL(dr::nc_overlap_kernel, dim3(grid), dim3(256), 0, st, Ki, Kc, (const int*)counts + 1, cand_i, cand_j, img_knn_points, img_knn_pixels,
-                       img_knn_masks, pcd_moved, pcd_knn_pixels, pcd_knn_masks, pos_radius_2d, pos_radius_3d, ratio_img, ratio_pcd);
+    hipLaunchKernelGGL(dr::nc_overlap_kernel, dim3(grid), dim3(256), 0, st, Ki, Kc, (const int*)counts + 1, w.cand_i, w.cand_j, img_knn_points, img_knn_pixels,
+                       img_knn_masks, w.pcd_moved, pcd_knn_pixels, pcd_knn_masks, pos_radius_2d, pos_radius_3d, w.ratio_img, w.ratio_pcd);
     DR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(dr::nc_filter_kernel, dim3(1), dim3(1024), 0, st, (const int*)counts + 1, cand_i, cand_j, ratio_img, ratio_pcd,
+    hipLaunchKernelGGL(dr::nc_filter_kernel, dim3(1), dim3(1024), 0, st, (const int*)counts + 1, w.cand_i, w.cand_j, w.ratio_img, w.ratio_pcd,
                        (long long*)img_corr_indices, (long long*)pcd_corr_indices, img_corr_overlaps, pcd_corr_overlaps, (int*)counts);
     DR_LAUNCH_CHECK();
     return DR_OK;
 }
 
 size_t dr_mutual_nn_radius_workspace_bytes(int ns, int nt) {
-    if (ns < 1 || nt < 1) return 256;
-    return 2 * dr::align256((size_t)ns * 4) + 2 * dr::align256((size_t)nt * 4);
+    return (ns < 1 || nt < 1) ? 256 : dr::mutual_nn_carve(nullptr, ns, nt).bytes;
 }
 
 int dr_mutual_nn_radius_f32(int ns, int nt, const float* src, const float* tgt, float radius, int64_t* out_src, int64_t* out_tgt, int32_t* count,
@@ -510,23 +494,18 @@ int dr_mutual_nn_radius_f32(int ns, int nt, const float* src, const float* tgt, 
     hipStream_t st = (hipStream_t)stream;
     if (ns == 0 || nt == 0) { DR_HIP_CHECK(hipMemsetAsync(count, 0, sizeof(int32_t), st)); return DR_OK; }
     if (workspace_bytes < dr_mutual_nn_radius_workspace_bytes(ns, nt)) return DR_EWORKSPACE;
-    char* w = (char*)workspace;
-    int* s2t = (int*)w;        w += dr::align256((size_t)ns * 4);
-    float* s2t_d2 = (float*)w; w += dr::align256((size_t)ns * 4);
-    int* t2s = (int*)w;        w += dr::align256((size_t)nt * 4);
-    float* t2s_d2 = (float*)w;
-    hipLaunchKernelGGL(dr::nn1_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, ns, nt, src, tgt, s2t, s2t_d2);
+    const dr::MutualNnWs w = dr::mutual_nn_carve(workspace, ns, nt);
+    hipLaunchKernelGGL(dr::nn1_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, ns, nt, src, tgt, w.s2t, w.s2t_d2);
     DR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(dr::nn1_kernel, dim3((nt + 255) / 256), dim3(256), 0, st, nt, ns, tgt, src, t2s, t2s_d2);
+    hipLaunchKernelGGL(dr::nn1_kernel, dim3((nt + 255) / 256), dim3(256), 0, st, nt, ns, tgt, src, w.t2s, w.t2s_d2);
     DR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(dr::mutual_select_kernel, dim3(1), dim3(1024), 0, st, ns, s2t, s2t_d2, t2s, radius, (long long*)out_src, (long long*)out_tgt, (int*)count);
+    hipLaunchKernelGGL(dr::mutual_select_kernel, dim3(1), dim3(1024), 0, st, ns, w.s2t, w.s2t_d2, w.t2s, radius, (long long*)out_src, (long long*)out_tgt, (int*)count);
     DR_LAUNCH_CHECK();
     return DR_OK;
 }
 
 size_t dr_radius_pairs_workspace_bytes(int ns, int nt) {
-    if (ns < 1) return 256;
-    return dr::align256((size_t)ns * 12) + dr::align256((size_t)ns * 4);
+    return ns < 1 ? 256 : dr::radius_pairs_carve(nullptr, ns).bytes;
 }
 
 int dr_radius_pairs_f32(int ns, int nt, const float* src, const float* tgt, const float* transform, float radius, long long capacity, int64_t* out_src,
@@ -537,12 +516,11 @@ int dr_radius_pairs_f32(int ns, int nt, const float* src, const float* tgt, cons
     hipStream_t st = (hipStream_t)stream;
     if (ns == 0 || nt == 0) { DR_HIP_CHECK(hipMemsetAsync(counts, 0, 2 * sizeof(int32_t), st)); return DR_OK; }
     if (workspace_bytes < dr_radius_pairs_workspace_bytes(ns, nt)) return DR_EWORKSPACE;
-    float* moved = (float*)workspace;
-    int* row_count = (int*)((char*)workspace + dr::align256((size_t)ns * 12));
-    hipLaunchKernelGGL(dr::move_points_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, ns, src, transform, moved);
+    const dr::RadiusPairsWs w = dr::radius_pairs_carve(workspace, ns);
+    hipLaunchKernelGGL(dr::move_points_kernel, dim3((ns + 255) / 256), dim3(256), 0, st, ns, src, transform, w.moved);
     DR_LAUNCH_CHECK();
-    dr::RadiusPred pred{moved, tgt, radius * radius};
-    return dr::compact_pairs(ns, nt, pred, row_count, capacity, (long long*)out_src, (long long*)out_tgt, (int*)counts, st);
+    dr::RadiusPred pred{w.moved, tgt, radius * radius};
+    return dr::compact_pairs(ns, nt, pred, w.row_count, capacity, (long long*)out_src, (long long*)out_tgt, (int*)counts, st);
 }
 
 }  // extern "C"

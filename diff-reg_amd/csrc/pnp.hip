@@ -30,6 +30,11 @@ struct PnpArgs {
     PnpBest* blk; int nblk;
     double* T; int* n_inlier; int* best_iter; uint8_t* inlier_mask;
 };
+// the workspace: the best hypothesis of each workgroup of 256, then one inlier byte per point
+size_t pnp_carve(void* base, PnpArgs& A, int n, int iters) {
+    Carver c(base); A.nblk = (iters + 255) / 256; A.blk = c.take<PnpBest>(A.nblk); A.inlier_mask = c.take<uint8_t>(n);
+    return align256(c.off);
+}
 
 __device__ __forceinline__ void load_px(const PnpArgs& A, int i, double& u, double& v) {
     const double a = A.px[2 * i], b = A.px[2 * i + 1];
@@ -299,8 +304,7 @@ __global__ __launch_bounds__(256) void pnp_final_kernel(PnpArgs A) {
 extern "C" {
 
 size_t dr_pnp_ransac_workspace_bytes(int n, int iters) {
-    if (n < 0 || iters < 1) return 0;
-    return (size_t)((iters + 255) / 256) * sizeof(dr::PnpBest) + (((size_t)n + 255) & ~(size_t)255);
+    dr::PnpArgs A; return (n < 0 || iters < 1) ? 0 : dr::pnp_carve(nullptr, A, n, iters);
 }
 
 int dr_pnp_ransac_f64(int n, const float* points, const float* pixels, int transposed, const double* intrinsics_host, int iters, double distance_tolerance,
@@ -311,9 +315,7 @@ int dr_pnp_ransac_f64(int n, const float* points, const float* pixels, int trans
     A.X = points; A.px = pixels; A.n = n; A.transposed = transposed ? 1 : 0;
     A.fx = intrinsics_host[0]; A.cx = intrinsics_host[2]; A.fy = intrinsics_host[4]; A.cy = intrinsics_host[5];
     A.iters = iters; A.base = dr::pnp_mix64(seed * 0x100000001B3ull + 0ull); A.tol2 = distance_tolerance * distance_tolerance;
-    A.nblk = (iters + 255) / 256;
-    A.blk = (dr::PnpBest*)workspace;
-    A.inlier_mask = (uint8_t*)workspace + (size_t)A.nblk * sizeof(dr::PnpBest);
+    dr::pnp_carve(workspace, A, n, iters);
     A.T = transform; A.n_inlier = n_inlier; A.best_iter = best_iter;
     hipStream_t st = (hipStream_t)stream;
     hipLaunchKernelGGL(dr::pnp_hyp_kernel, dim3(A.nblk), dim3(256), 0, st, A);

@@ -773,14 +773,15 @@ static int proc_slice_len(int P, long NM) {
     SL = (SL + 1023) / 1024 * 1024;
     return (int)(SL < 4096 ? 4096 : SL);
 }
-static size_t proc_zeroed_bytes(int P) { return (size_t)P * 3 * PH_BINS * 4; }
+// the workspace of a large tile: the list (keys, indices), its length, the digit histograms (zeroed per call), per-slice {above, equal} tables
+static size_t proc_carve(void* base, ProcArgs& a, int P, long NM) {
+    Carver c(base); a.SL = proc_slice_len(P, NM); a.S = (int)((NM + a.SL - 1) / a.SL);
+    a.g_ckey = c.take<unsigned>((size_t)P * PC_CAP); a.g_cidx = c.take<int>((size_t)P * PC_CAP); a.g_ccount = c.take<int>(P);
+    a.g_hist = c.take<unsigned>((size_t)P * 3 * PH_BINS); a.g_shist = c.take<uint2>((size_t)P * a.S * PH_LAST);
+    return align256(c.off) + 512;
+}
 size_t procrustes_workspace_bytes(int P, int N, int M) {
-    const long NM = (long)N * M;
-    if (P <= 0 || NM <= 65536) return 0;
-    const long SL = proc_slice_len(P, NM);
-    const size_t S = (size_t)((NM + SL - 1) / SL);
-    // the list (keys, indices), its length, digit histograms, per-slice {above, equal} tables
-    return (size_t)P * (PC_CAP * 8 + S * PH_LAST * 8) + (((size_t)P * 4 + 255) & ~(size_t)255) + proc_zeroed_bytes(P) + 512;
+    ProcArgs a; return (P <= 0 || (long)N * M <= 65536) ? 0 : proc_carve(nullptr, a, P, (long)N * M);
 }
 
 // which launch form the calling thread's last launch_procrustes took (dr_debug_procrustes_last_form): -1 = none
@@ -810,16 +811,8 @@ int launch_procrustes(const float* conf, const float* src_pcd, const float* tgt_
         hipLaunchKernelGGL(procrustes_kernel<true>, dim3(P), dim3(1024), 0, st, a);
     } else {
         if (ws && ws_bytes >= procrustes_workspace_bytes(P, N, M)) {
-            a.SL = proc_slice_len(P, NM);
-            a.S = (int)((NM + a.SL - 1) / a.SL);
-            char* w8 = (char*)ws;
-            a.g_ckey = (unsigned*)w8; w8 += (size_t)P * PC_CAP * 4;
-            a.g_cidx = (int*)w8; w8 += (size_t)P * PC_CAP * 4;
-            a.g_ccount = (int*)w8; w8 += ((size_t)P * 4 + 255) & ~(size_t)255;
-            a.g_hist = (unsigned*)w8;
-            DR_HIP_CHECK(hipMemsetAsync(a.g_hist, 0, proc_zeroed_bytes(P), st));
-            w8 += proc_zeroed_bytes(P);
-            a.g_shist = (uint2*)w8;
+            proc_carve(ws, a, P, NM);
+            DR_HIP_CHECK(hipMemsetAsync(a.g_hist, 0, (size_t)P * 3 * PH_BINS * sizeof(unsigned), st));
             hipLaunchKernelGGL(proc_hist_kernel<0>, dim3(a.S, P), dim3(1024), 0, st, a);
             DR_LAUNCH_CHECK();
             hipLaunchKernelGGL(proc_hist_kernel<1>, dim3(a.S, P), dim3(1024), 0, st, a);

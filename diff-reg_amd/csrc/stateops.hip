@@ -341,10 +341,14 @@ __global__ __launch_bounds__(1024) void top1_merge_kernel(int N, int M, int NB, 
     top1_emit(s_key, s_w, N, M, out + (size_t)pair * (N + M) * 3, count + pair);
 }
 
+// byte offsets from the caller's pointer rounded up to 16 (the loops budget for these bytes: no Carver): best value (at 0) and its row per cell, row keys
+struct Top1Ws { int NB; size_t colrow, rowkey, bytes; };
+static Top1Ws top1_carve(int P, int N, int M, size_t elt) {
+    const int NB = (N + T1_ROWS - 1) / T1_ROWS; const size_t cells = (size_t)P * NB * M;
+    return {NB, cells * elt, cells * (elt + 4), cells * (elt + 4) + (((size_t)P * N * 4 + 15) & ~(size_t)15) + 64};
+}
 size_t top1_union_workspace_bytes(int P, int N, int M, size_t elt) {
-    if (P <= 0 || N < 2 * T1_ROWS) return 0;                     // a single row block: the one-workgroup kernel is the same work
-    const size_t NB = (size_t)(N + T1_ROWS - 1) / T1_ROWS;
-    return (size_t)P * NB * M * (elt + 4) + (((size_t)P * N * 4 + 15) & ~(size_t)15) + 64;
+    return (P <= 0 || N < 2 * T1_ROWS) ? 0 : top1_carve(P, N, M, elt).bytes;      // a single row block: the one-workgroup kernel is the same work
 }
 
 template <typename T>
@@ -355,11 +359,9 @@ int launch_top1_union(const T* conf, int P, int N, int M, long long* out, int* c
     if (!(sm && tm)) sm = tm = nullptr;
     const size_t need = top1_union_workspace_bytes(P, N, M, sizeof(T));
     if (ws && need && ws_bytes >= need) {
-        const int NB = (N + T1_ROWS - 1) / T1_ROWS;
+        const Top1Ws c = top1_carve(P, N, M, sizeof(T));
         char* w8 = (char*)(((uintptr_t)ws + 15) & ~(uintptr_t)15);
-        T* colval = (T*)w8; w8 += (size_t)P * NB * M * sizeof(T);
-        int* colrow = (int*)w8; w8 += (size_t)P * NB * M * 4;
-        unsigned* rowkey = (unsigned*)w8;
+        const int NB = c.NB; T* colval = (T*)w8; int* colrow = (int*)(w8 + c.colrow); unsigned* rowkey = (unsigned*)(w8 + c.rowkey);
         hipLaunchKernelGGL((top1_block_kernel<T>), dim3(NB, P), dim3(1024), 0, st, conf, N, M, rowkey, colval, colrow, sm, tm);
         DR_LAUNCH_CHECK();
         hipLaunchKernelGGL((top1_merge_kernel<T>), dim3(P), dim3(1024), 0, st, N, M, NB, rowkey, colval, colrow, out, count);
@@ -632,14 +634,17 @@ __global__ __launch_bounds__(256) void mt_write_kernel(MtArgs A) {
     }
 }
 
+// the workspace: one bit per entry of every batch element (`words` 32-bit words each), then the elements' counts
+static size_t mt_carve(void* base, MtArgs& A, int B, int N, int M) {
+    Carver c(base); const size_t words = ((size_t)N * M + 31) / 32; A.words = (int)words; A.bits = c.take<unsigned>((size_t)B * words); A.counts = c.take<int>(B);
+    return c.off + 256;
+}
 }  // namespace dr
 
 extern "C" {
 
 size_t dr_mutual_topk_workspace_bytes(int B, int N, int M) {
-    if (B <= 0 || N <= 0 || M <= 0) return 0;
-    const size_t words = ((size_t)N * M + 31) / 32;
-    return (size_t)B * words * 4 + (size_t)B * 4 + 256;
+    dr::MtArgs A; return (B <= 0 || N <= 0 || M <= 0) ? 0 : dr::mt_carve(nullptr, A, B, N, M);
 }
 
 int dr_mutual_topk_select_f32(int B, int N, int M, const float* score, int k, int largest, int use_threshold, float threshold,
@@ -652,15 +657,13 @@ int dr_mutual_topk_select_f32(int B, int N, int M, const float* score, int k, in
     DR_HIP_CHECK(hipMemsetAsync(total, 0, sizeof(int32_t), st));
     if (B == 0) return DR_OK;
     if (!score || (capacity > 0 && (!out_idx || !out_score))) return DR_EINVAL;
-    const size_t words = ((size_t)N * M + 31) / 32;
-    if (words * 8 > 64 * 1024) return DR_ENOSUP;                       // both bit planes of one element live in LDS
-    if (!workspace || workspace_bytes < dr_mutual_topk_workspace_bytes(B, N, M)) return DR_EWORKSPACE;
+    if ((size_t)N * M > 32 * 8192) return DR_ENOSUP;                   // both bit planes of one element (8 bytes per 32 entries) live in 64 KiB of LDS
     MtArgs A{};
+    if (!workspace || workspace_bytes < mt_carve(workspace, A, B, N, M)) return DR_EWORKSPACE;
     A.score = score; A.rmask = row_masks; A.cmask = col_masks; A.B = B; A.N = N; A.M = M; A.k = k; A.largest = largest; A.mutual = mutual;
-    A.use_thr = use_threshold; A.thr = threshold; A.bits = (unsigned*)workspace; A.words = (int)words;
-    A.counts = (int*)((char*)workspace + (size_t)B * words * 4); A.out_idx = (long long*)out_idx; A.out_score = out_score; A.total = total;
+    A.use_thr = use_threshold; A.thr = threshold; A.out_idx = (long long*)out_idx; A.out_score = out_score; A.total = total;
     A.capacity = capacity;
-    hipLaunchKernelGGL(mt_select_kernel, dim3(B), dim3(256), words * 8, st, A);
+    hipLaunchKernelGGL(mt_select_kernel, dim3(B), dim3(256), A.words * 8, st, A);
     DR_LAUNCH_CHECK();
     hipLaunchKernelGGL(mt_scan_kernel, dim3(1), dim3(256), 0, st, A.counts, B, total);
     DR_LAUNCH_CHECK();

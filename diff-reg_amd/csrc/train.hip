@@ -200,14 +200,19 @@ __global__ __launch_bounds__(64) void motion_final_kernel(MotionArgs A) {
     *A.loss = (float)(se / cnt);                          // mean of an empty selection is nan in the reference too
 }
 
+// dr_train_workspace_bytes: the reductions' partials (all a single-array entry reads), then dr_match_recall_f32's mark byte per matrix entry
+struct RecallWs { double* part; uint8_t* mark; size_t bytes; };
+static RecallWs recall_carve(void* base, int P, int N, int M) {
+    Carver c(base); return {c.take<double>((size_t)TR_BLOCKS * 4), c.take<uint8_t>((size_t)P * N * M), align256(c.off)};
+}
+
 }  // namespace
 }  // namespace dr
 
 extern "C" {
 
 size_t dr_train_workspace_bytes(int P, int N, int M) {
-    if (P < 0 || N < 0 || M < 0) return 0;
-    return (size_t)dr::TR_BLOCKS * 4 * sizeof(double) + (((size_t)P * N * M + 255) & ~(size_t)255);
+    return (P < 0 || N < 0 || M < 0) ? 0 : dr::recall_carve(nullptr, P, N, M).bytes;
 }
 
 int dr_match_matrix_f32(int P, int N, int M, int K, const int64_t* matches, float* out, void* stream) {
@@ -250,17 +255,16 @@ int dr_match_recall_f32(int P, int N, int M, const float* conf_gt, int K, const 
                         void* stream) {
     if (P < 1 || N < 1 || M < 1 || K < 0 || !conf_gt || !recall_precision || !workspace || (K > 0 && !match_pred)) return DR_EINVAL;
     hipStream_t st = (hipStream_t)stream;
-    double* part = (double*)workspace;
-    uint8_t* mark = (uint8_t*)workspace + (size_t)dr::TR_BLOCKS * 4 * sizeof(double);
+    const dr::RecallWs w = dr::recall_carve(workspace, P, N, M);
     const long long n = (long long)P * N * M;
-    DR_HIP_CHECK(hipMemsetAsync(mark, 0, (size_t)n, st));
+    DR_HIP_CHECK(hipMemsetAsync(w.mark, 0, (size_t)n, st));
     if (K > 0) {
-        hipLaunchKernelGGL(dr::mark_pred_kernel, dim3((K + 255) / 256), dim3(256), 0, st, K, (long long)N * M, N, M, P, (const long long*)match_pred, mark);
+        hipLaunchKernelGGL(dr::mark_pred_kernel, dim3((K + 255) / 256), dim3(256), 0, st, K, (long long)N * M, N, M, P, (const long long*)match_pred, w.mark);
         DR_LAUNCH_CHECK();
     }
-    hipLaunchKernelGGL(dr::recall_partial_kernel, dim3(dr::TR_BLOCKS), dim3(dr::TR_THREADS), 0, st, n, conf_gt, mark, part);
+    hipLaunchKernelGGL(dr::recall_partial_kernel, dim3(dr::TR_BLOCKS), dim3(dr::TR_THREADS), 0, st, n, conf_gt, w.mark, w.part);
     DR_LAUNCH_CHECK();
-    hipLaunchKernelGGL(dr::recall_final_kernel, dim3(1), dim3(64), 0, st, part, K, recall_precision);
+    hipLaunchKernelGGL(dr::recall_final_kernel, dim3(1), dim3(64), 0, st, w.part, K, recall_precision);
     DR_LAUNCH_CHECK();
     return DR_OK;
 }

@@ -1,6 +1,6 @@
 // train_common.h -- host helpers shared by the training entry points (train_layer.hip, train_fusion.hip, circle_loss.hip): a batched
 // transposition (the GEMM contracts along contiguous k: x W for a gradient w.r.t. the input and g^T x for a weight gradient need the transposed
-// operand), a two-operand add and a builder of GEMM launches (the carving of caller memory into 256-byte aligned arrays: Carver of loop_common.h).
+// operand), a two-operand add and a builder of GEMM launches (the carving of caller memory into 256-byte aligned arrays: Carver of carve.h).
 #pragma once
 #include <string.h>
 #include "loop_common.h"

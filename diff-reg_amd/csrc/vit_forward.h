@@ -13,6 +13,7 @@
 #include <stddef.h>
 
 #include "../../include/diffreg_hip.h"
+#include "carve.h"               // align256
 #include "vit_index.h"
 
 namespace dr {
@@ -26,15 +27,14 @@ inline bool vit_dims_ok(int H, int W, int p, int D, int Dh) {
 struct VitCarve {
     size_t xn, qkv, ao, hid, patches, total;      // byte offsets (256-byte aligned) and the total
 };
-inline size_t vit_align256(size_t v) { return (v + 255) & ~(size_t)255; }
 inline VitCarve vit_carve(int L, int D, int Dh, int Np, int Kp, size_t elem) {
     VitCarve c;
     size_t o = 0;
-    c.xn = o; o = vit_align256(o + (size_t)L * D * elem);
-    c.qkv = o; o = vit_align256(o + (size_t)L * 3 * D * elem);
-    c.ao = o; o = vit_align256(o + (size_t)L * D * elem);
-    c.hid = o; o = vit_align256(o + (size_t)L * Dh * elem);
-    c.patches = o; o = vit_align256(o + (size_t)Np * Kp * elem);
+    c.xn = o; o = align256(o + (size_t)L * D * elem);
+    c.qkv = o; o = align256(o + (size_t)L * 3 * D * elem);
+    c.ao = o; o = align256(o + (size_t)L * D * elem);
+    c.hid = o; o = align256(o + (size_t)L * Dh * elem);
+    c.patches = o; o = align256(o + (size_t)Np * Kp * elem);
     c.total = o;
     return c;
 }

@@ -64,7 +64,7 @@ static void walk_pairs(const std::vector<int>& ns_, const std::vector<int>& nt_,
     std::vector<int32_t> s_off = prefix(ns_), t_off = prefix(nt_);
     for (auto& o : s_off) o += lead;                           // `lead` rows of no pair in front of offsets[0], 3 behind the last
     for (auto& o : t_off) o += lead;
-    const int ns = s_off.back() + (lead ? 3 : 0), nt = t_off.back() + (lead ? 3 : 0), n_pad = nt > 0 ? it3_next_pow2(nt) : 0;
+    const int ns = s_off.back() + (lead ? 3 : 0), nt = t_off.back() + (lead ? 3 : 0), n_pad = nt > 0 ? next_pow2(nt) : 0;
     CHECK(n_pad >= nt && (n_pad & (n_pad - 1)) == 0);
     std::mt19937 rng(seed);
     std::uniform_real_distribution<float> U(-spread, spread);
@@ -205,13 +205,13 @@ int main() {
     CHECK(it3_room(0, 10, 5) == 5 && it3_room(3, 10, 20) == 7 && it3_room(10, 3, 20) == 0 && it3_room(-1, 10, 20) == 0 && it3_room(21, 30, 20) == 0);
     CHECK(it3_room(20, 30, 20) == 0 && it3_room(0, 1LL << 40, 1LL << 30) == (1LL << 30));
     CHECK(it3_saturate(-5) == 0 && it3_saturate(0x7fffffffLL) == 0x7fffffff && it3_saturate(1LL << 40) == 0x7fffffff && it3_saturate(12) == 12);
-    CHECK(it3_next_pow2(0) == 1 && it3_next_pow2(1) == 1 && it3_next_pow2(257) == 512 && it3_next_pow2(IT3_MAX_ROWS) == IT3_MAX_ROWS);
+    CHECK(next_pow2(0) == 1 && next_pow2(1) == 1 && next_pow2(257) == 512 && next_pow2(IT3_MAX_ROWS) == IT3_MAX_ROWS);
     CHECK(it3_blocks(0, 256) == 1 && it3_blocks(256, 256) == 1 && it3_blocks(257, 256) == 2 && it3_blocks(IT3_MAX_ROWS, IT3_ROWS) == (unsigned)(IT3_MAX_ROWS / IT3_ROWS));
     // the workspace carve: six arrays in order, each on 256 bytes, none overlapping, the total covering the last
     const int carve[][3] = {{1, 0, 0}, {1, 1, 1}, {3, 63, 65}, {2, 300, 257}, {IT3_MAX_PAIRS, IT3_MAX_ROWS, IT3_MAX_ROWS}, {-1, -4, -4}};
     for (const auto& c : carve) {
         const It3PairsCarve k = it3_pairs_carve(c[0], c[1], c[2]);
-        const size_t p = c[0] > 0 ? c[0] : 0, s = c[1] > 0 ? c[1] : 0, t = c[2] > 0 ? c[2] : 0, pad = c[2] > 0 ? (size_t)it3_next_pow2(c[2]) : 0;
+        const size_t p = c[0] > 0 ? c[0] : 0, s = c[1] > 0 ? c[1] : 0, t = c[2] > 0 ? c[2] : 0, pad = c[2] > 0 ? (size_t)next_pow2(c[2]) : 0;
         CHECK(k.moved == 0 && k.row_start % 256 == 0 && k.origin % 256 == 0 && k.keys % 256 == 0 && k.vals % 256 == 0 && k.sorted % 256 == 0);
         CHECK(k.row_start >= k.moved + s * 12 && k.origin >= k.row_start + s * 8 && k.keys >= k.origin + p * 16 && k.vals >= k.keys + pad * 8);
         CHECK(k.sorted >= k.vals + pad * 4 && k.bytes >= k.sorted + t * 16);
