@@ -149,6 +149,51 @@ int dr_debug_procrustes_last_form(void) { return procrustes_last_form(); }
 int dr_debug_pgemm_acc_forms(int clear) { return pgemm_acc_forms(clear != 0); }
 void dr_debug_fps_force_streaming(int on) { fps_force_streaming(on); }
 
+/* diagnostics for the per-kernel edge tests: one launch of a row / state kernel of the loops; every check stands in front of the launch */
+int dr_debug_layernorm_f32(int rows, int C, const float* x, int ldx, const float* gamma, const float* beta, const float* res, int ldres,
+                           int postadd, float* out, int ldo, float* rowmax, void* stream) {
+    if (rows < 0 || C < 1 || !x || !gamma || !beta || !out || ldx < C || ldo < C || (res && ldres < C)) return DR_EINVAL;
+    if (postadd && (!res || rowmax)) return DR_EINVAL;
+    if (C > 1024) return DR_ENOSUP;
+    if (postadd) return launch_layernorm_postadd(x, ldx, gamma, beta, res, ldres, out, ldo, rows, C, (hipStream_t)stream);
+    return launch_layernorm(x, ldx, gamma, beta, res, ldres, out, ldo, rows, C, (hipStream_t)stream, rowmax);
+}
+
+int dr_debug_fourier_f32(int D, int P, int rows_per_pair, const float* pts, const float* R, const float* t, int L, float* emb, int ldo,
+                         float* warped_ws, void* stream) {
+    if ((D != 2 && D != 3) || P < 0 || rows_per_pair < 0 || !pts || !emb || L < 0 || L > 30 || ldo < (2 * L + 1) * D) return DR_EINVAL;
+    if (D == 3 && (!warped_ws || (R == nullptr) != (t == nullptr))) return DR_EINVAL;
+    if ((long long)P * rows_per_pair * ldo > 0x7fffffffLL) return DR_ENOSUP;       // the kernels index rows * ldo in 32 bits
+    if (P == 0 || rows_per_pair == 0) return DR_OK;
+    if (D == 3) return launch_fourier3d(pts, P, rows_per_pair, R, t, L, emb, ldo, warped_ws, (hipStream_t)stream);
+    return launch_fourier2d(pts, P * rows_per_pair, L, emb, ldo, (hipStream_t)stream);
+}
+
+size_t dr_debug_pair_min_scratch_bytes(int P) { return pair_min_scratch_bytes(P); }
+
+int dr_debug_pair_min_f64(int P, int N, int M, const double* x, const uint8_t* src_mask, const uint8_t* tgt_mask, double* out, void* scratch,
+                          void* stream) {
+    if (P < 0 || N < 1 || M < 1 || !x || !out || (src_mask == nullptr) != (tgt_mask == nullptr)) return DR_EINVAL;
+    if ((long long)N * M > 0x7fffffffLL) return DR_ENOSUP;
+    return launch_pair_min(x, P, N * M, out, (hipStream_t)stream, M, src_mask, tgt_mask, scratch);
+}
+
+int dr_debug_ddim_f64(const dr_debug_ddim_args* a, int P, void* stream) {
+    if (!a || P < 0 || a->N < 1 || a->M < 1 || !a->x || !a->x0 || (a->src_mask == nullptr) != (a->tgt_mask == nullptr)) return DR_EINVAL;
+    if ((long long)a->N * a->M > 0x7fffffffLL) return DR_ENOSUP;
+    DdimArgs d;
+    d.x = a->x; d.x0 = a->x0; d.shift = a->shift; d.noise = a->noise; d.src_mask = a->src_mask; d.tgt_mask = a->tgt_mask;
+    d.N = a->N; d.M = a->M; d.first_step = a->first_step; d.sra = a->sra; d.srm1 = a->srm1; d.c = a->c; d.sigma = a->sigma; d.sqrt_an = a->sqrt_an;
+    return launch_ddim(d, P, (hipStream_t)stream);
+}
+
+int dr_debug_state_map(int kind, const void* in, void* out, long long n, void* stream) {
+    if (kind < 0 || kind > 2 || n < 0 || (n > 0 && (!in || !out))) return DR_EINVAL;
+    if (kind == 0) return launch_f32_to_f64((const float*)in, (double*)out, (size_t)n, (hipStream_t)stream);
+    if (kind == 1) return launch_f64_to_f32((const double*)in, (float*)out, (size_t)n, (hipStream_t)stream);
+    return launch_sigmoid((const double*)in, (double*)out, (size_t)n, (hipStream_t)stream);
+}
+
 int dr_vol_pe_f32(int rows, int rows_per_pair, int C, const float* xyz, const float* R, const float* t, float origin_x,
                   float origin_y, float origin_z, float voxel, const float* freq, float* cos_out, float* sin_out,
                   void* stream) {

@@ -28,7 +28,13 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const float* __restrict_
         if (POSTADD && c < C) v[i] += res[(size_t)row * ldres + c];
         s += v[i];
     }
-    const float mean = wave_sum(s) / (float)C;
+    float mean = wave_sum(s) / (float)C;
+    // the float32 sum is a few ulps of |mean| off, and (x - mean) * rstd magnifies that by up to 1 / sqrt(eps) = 316 on rows whose mean dwarfs
+    // their spread (a constant row came out 1e-4 from beta): a second pass over the registers adds what the first left, mean of (x - mean)
+    float s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < LN_MAX_PER_LANE; ++i) s2 += lane + 64 * i < C ? v[i] - mean : 0.f;
+    mean += wave_sum(s2) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < LN_MAX_PER_LANE; ++i) {
@@ -72,7 +78,12 @@ __global__ __launch_bounds__(256) void layernorm_vec_kernel(const float* __restr
         if (POSTADD && c < C4) { const float4 r = rr[c]; v[i].x += r.x; v[i].y += r.y; v[i].z += r.z; v[i].w += r.w; }
         s += (v[i].x + v[i].y) + (v[i].z + v[i].w);
     }
-    const float mean = wave_sum(s) / (float)C;
+    float mean = wave_sum(s) / (float)C;
+    float s2 = 0.f;                                          // the mean's second pass (see layernorm_kernel)
+#pragma unroll
+    for (int i = 0; i < NV; ++i)
+        if (lane + 64 * i < C4) s2 += ((v[i].x - mean) + (v[i].y - mean)) + ((v[i].z - mean) + (v[i].w - mean));
+    mean += wave_sum(s2) / (float)C;
     float q = 0.f;
 #pragma unroll
     for (int i = 0; i < NV; ++i) {
@@ -137,6 +148,14 @@ int launch_layernorm_postadd(const float* x, int ldx, const float* g, const floa
 // FourierEmbedding(length L, use_pi=False, use_input=True) (2D3D/vision3d/layers/embedding.py:75-100):
 // [p (D) | level 0: sin (D), cos (D) | level 1: ... ], factors 2^l exact in float32
 // ---------------------------------------------------------------------------------------------
+// One axis of R p + t in float32, operation by operation: three products, added left to right, then + t.  The HIP headers define __fmul_rn /
+// __fadd_rn as plain `*` / `+`, which contract into FMAs like any other expression; the pragma is what pins the stated order.
+__device__ __forceinline__ float warp_axis(const float* __restrict__ Rrow, float px, float py, float pz, float t) {
+#pragma clang fp contract(off)
+    const float a = Rrow[0] * px, b = Rrow[1] * py, c = Rrow[2] * pz;
+    return ((a + b) + c) + t;
+}
+
 __global__ __launch_bounds__(256) void warp_mean_kernel(const float* __restrict__ xyz, int n, const float* __restrict__ R,
                                                         const float* __restrict__ tv, float* __restrict__ warped) {
     // one workgroup per pair: warped = R p + t, then subtract the mean over the n rows (points.mean(dim=1))
@@ -152,8 +171,7 @@ __global__ __launch_bounds__(256) void warp_mean_kernel(const float* __restrict_
             const float* tp = tv + pair * 3;
             float o[3];
 #pragma unroll
-            for (int a = 0; a < 3; ++a)
-                o[a] = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(Rp[a * 3], q[0]), __fmul_rn(Rp[a * 3 + 1], q[1])), __fmul_rn(Rp[a * 3 + 2], q[2])), tp[a]);
+            for (int a = 0; a < 3; ++a) o[a] = warp_axis(Rp + a * 3, q[0], q[1], q[2], tp[a]);
             q[0] = o[0]; q[1] = o[1]; q[2] = o[2];
         }
 #pragma unroll
@@ -233,8 +251,7 @@ __global__ __launch_bounds__(256) void vol_pe_kernel(const float* __restrict__ x
         const float* Rp = R + (size_t)(row / rows_per_pair) * 9;
         const float* tp = tv + (size_t)(row / rows_per_pair) * 3;
         // matmul(R, p) + t in the operation order of a 3-term dot product followed by the add
-        p = __fadd_rn(__fadd_rn(__fadd_rn(__fmul_rn(Rp[a * 3 + 0], px), __fmul_rn(Rp[a * 3 + 1], py)),
-                                __fmul_rn(Rp[a * 3 + 2], pz)), tp[a]);
+        p = warp_axis(Rp + a * 3, px, py, pz, tp[a]);
         if (warped && k == 0) warped[row * 3 + a] = p;
     } else {
         p = a == 0 ? px : (a == 1 ? py : pz);

@@ -565,6 +565,23 @@ SIGNATURES.update({
 })
 
 
+class DebugDdimArgs(ctypes.Structure):
+    """dr_debug_ddim_args (include/diffreg_hip_debug.h): the DDIM kernel's launch argument, field for field"""
+    _fields_ = [(n, c_void_p) for n in ("x", "x0", "shift", "noise", "src_mask", "tgt_mask")] + \
+               [(n, c_int) for n in ("N", "M", "first_step")] + [(n, c_double) for n in ("sra", "srm1", "c", "sigma")] + [("sqrt_an", c_float)]
+
+
+SIGNATURES.update({
+    # diagnostics (include/diffreg_hip_debug.h): one launch of a row / state kernel of the loops, for tests/test_row_state_edges_gpu.py
+    "dr_debug_layernorm_f32": (c_int, [c_int, c_int, c_void_p, c_int, c_void_p, c_void_p, c_void_p, c_int, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "dr_debug_fourier_f32": (c_int, [c_int, c_int, c_int, c_void_p, c_void_p, c_void_p, c_int, c_void_p, c_int, c_void_p, c_void_p]),
+    "dr_debug_pair_min_scratch_bytes": (c_size_t, [c_int]),
+    "dr_debug_pair_min_f64": (c_int, [c_int, c_int, c_int] + [c_void_p] * 6),
+    "dr_debug_ddim_f64": (c_int, [ctypes.POINTER(DebugDdimArgs), c_int, c_void_p]),
+    "dr_debug_state_map": (c_int, [c_int, c_void_p, c_void_p, ctypes.c_longlong, c_void_p]),
+})
+
+
 def _bind(table):
     for name, (res, args) in table.items():
         if not hasattr(_lib, name):          # the sets added under one ABI number are detected by symbol

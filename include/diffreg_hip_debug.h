@@ -102,6 +102,48 @@ void dr_debug_fps_force_streaming(int on);
 /* n dependent launches of an empty kernel (tools/launch_floor.py) */
 int dr_debug_launch_chain(int n, int workgroups, int threads, void* stream);
 
+/* The row and state kernels the denoise loops launch between their GEMMs (csrc/rowops.hip, csrc/stateops.hip), one launch each, for the
+ * per-kernel edge tests.  Every entry checks its arguments BEFORE it launches: a refused call (DR_EINVAL / DR_ENOSUP) runs no kernel and
+ * writes nothing.  All pointers are device pointers; leading dimensions and strides are in elements. */
+/* out[r][c] = LayerNorm(x[r])[c] gamma[c] + beta[c] (+ res[r][c] with res != NULL, postadd == 0), or LayerNorm(x[r] + res[r]) gamma + beta with
+ * postadd != 0 (res required); eps = 1e-5, r < rows, c < C <= 1024 (beyond: DR_ENOSUP).  rowmax (nullable, [rows]): max_c |out[r][c]|; with
+ * postadd it must be NULL (DR_EINVAL).  C % 4 == 0 up to 768 with leading dimensions that are multiples of 4 and 16-byte aligned pointers
+ * takes the float4 form, everything else the scalar one. */
+int dr_debug_layernorm_f32(int rows, int C, const float* x, int ldx, const float* gamma, const float* beta, const float* res, int ldres,
+                           int postadd, float* out, int ldo, float* rowmax, void* stream);
+/* Fourier embedding [p | sin(2^l p), cos(2^l p) for l < L] of width (2L+1) D, zero-padded to ldo (below that width: DR_EINVAL).
+ * D == 3: pts [P, rows_per_pair, 3], warped by R [P, 3, 3], t [P, 3] (both NULL: not warped) and centred on the mean of each pair's rows;
+ *         warped_ws [P, rows_per_pair, 3] receives the warped, centred points and is required.
+ * D == 2: pts [P rows_per_pair, 2] as they are; R, t, warped_ws are ignored.  Any other D: DR_EINVAL.  L in 0..30. */
+int dr_debug_fourier_f32(int D, int P, int rows_per_pair, const float* pts, const float* R, const float* t, int L, float* emb, int ldo,
+                         float* warped_ws, void* stream);
+/* out[p] = min of x[p][:, :] (float64, [P, N, M]) over the entries inside both masks (uint8 [P, N] / [P, M], both NULL: all of them; a pair
+ * with no such entry gives +inf).  scratch == NULL: one workgroup per pair.  scratch of dr_debug_pair_min_scratch_bytes(P) bytes whose last
+ * 64 P bytes (the arrival counters) are zero: the sliced form wherever the library's rule chooses it (P <= 32 and N M >= 16384), which
+ * leaves the counters zero again. */
+size_t dr_debug_pair_min_scratch_bytes(int P);
+int dr_debug_pair_min_f64(int P, int N, int M, const double* x, const uint8_t* src_mask, const uint8_t* tgt_mask, double* out, void* scratch,
+                          void* stream);
+/* one DDIM update of the state in place (the launch argument of csrc/kernels.h, field for field):
+ *   x <- x0 * sqrt_an + c * ((sra * xs - x0) / srm1) [+ sigma * noise],  xs = x - shift[pair] (shift != NULL) or x
+ * with the reference's dtype bookkeeping: on the first step x - shift and sigma * noise are float32 operations, x0 * sqrt_an is a float32
+ * product on every step, the rest is float64.  Entries outside the masks (both NULL: none) become -inf. */
+typedef struct dr_debug_ddim_args {
+    double* x;
+    const float* x0;
+    const double* shift;
+    const float* noise;
+    const uint8_t* src_mask;
+    const uint8_t* tgt_mask;
+    int N, M, first_step;
+    double sra, srm1, c, sigma;
+    float sqrt_an;
+} dr_debug_ddim_args;
+int dr_debug_ddim_f64(const dr_debug_ddim_args* args, int P, void* stream);
+/* element-wise maps of the state, n elements: kind 0 float32 -> float64 (exact), 1 float64 -> float32 (round to nearest even),
+ * 2 float64 -> float64 1 / (1 + exp(-x)); any other kind: DR_EINVAL */
+int dr_debug_state_map(int kind, const void* in, void* out, long long n, void* stream);
+
 #ifdef __cplusplus
 }
 #endif
