@@ -22,12 +22,12 @@ constexpr unsigned long long CL_PAD_KEY = ~0ull;
 struct CloudInfo {
     int begin, end;          // rows of the stacked array
     float ox, oy, oz;        // origin corner by CL_ORIGIN_*: the min corner (neighbours), floor(min * (1 / dl)) * dl (KPConv's subsample),
-                             // floor(min / dl) * dl (vision3d's subsample)
+                             // floor(min / dl) * dl (vision3d's subsample), min - 0.5 dl (Open3D's voxel_down_sample)
     int lx, ly, lz;          // smallest voxel coordinate of the cloud (keys are stored relative to it)
     int bad;                 // a coordinate range does not fit CL_AXIS_BITS
 };
 
-constexpr int CL_ORIGIN_MIN = 0, CL_ORIGIN_KPCONV = 1, CL_ORIGIN_VISION3D = 2;     // CloudInfo origin: see cloud_info_kernel
+constexpr int CL_ORIGIN_MIN = 0, CL_ORIGIN_KPCONV = 1, CL_ORIGIN_VISION3D = 2, CL_ORIGIN_OPEN3D = 3;     // CloudInfo origin: see cloud_info_kernel
 
 __device__ __forceinline__ int cl_floor_div(float p, float o, float d) { return (int)floorf((p - o) / d); }
 
@@ -67,8 +67,10 @@ __global__ __launch_bounds__(1024) void cloud_info_kernel(const float* __restric
     for (int c = 0; c < 3; ++c) {
         // CL_ORIGIN_KPCONV    grid_subsampling.cpp:26 (cpp_wrappers)  originCorner = floor(minCorner * (1 / sampleDl)) * sampleDl
         // CL_ORIGIN_VISION3D  vision3d/csrc/cpu/grid_subsampling/grid_subsampling.cpp:32  origin = floor(min_corner / voxel_size) * voxel_size
+        // CL_ORIGIN_OPEN3D    PointCloud::VoxelDownSample (open3d/geometry/PointCloud.cpp)  voxel_min_bound = min_bound - voxel_size * 0.5
         o[c] = origin_mode == CL_ORIGIN_KPCONV ? floorf(mn[c] * (1.0f / cell)) * cell
-             : origin_mode == CL_ORIGIN_VISION3D ? floorf(mn[c] / cell) * cell : mn[c];
+             : origin_mode == CL_ORIGIN_VISION3D ? floorf(mn[c] / cell) * cell
+             : origin_mode == CL_ORIGIN_OPEN3D ? mn[c] - 0.5f * cell : mn[c];
     }
     ci.ox = o[0]; ci.oy = o[1]; ci.oz = o[2];
     int lo[3] = {0, 0, 0};
@@ -516,6 +518,13 @@ int dr_grid_subsample_vision3d_f32(int n, int nb, const float* points, const int
                                    int32_t* out_lengths, int32_t* out_total, int32_t* status, void* workspace, size_t workspace_bytes,
                                    void* stream) {
     return grid_subsample_impl(CL_ORIGIN_VISION3D, n, nb, points, lengths, voxel_size, out_points, out_lengths, out_total, status,
+                               workspace, workspace_bytes, stream);
+}
+
+int dr_grid_subsample_open3d_f32(int n, int nb, const float* points, const int32_t* lengths, float voxel_size, float* out_points,
+                                 int32_t* out_lengths, int32_t* out_total, int32_t* status, void* workspace, size_t workspace_bytes,
+                                 void* stream) {
+    return grid_subsample_impl(CL_ORIGIN_OPEN3D, n, nb, points, lengths, voxel_size, out_points, out_lengths, out_total, status,
                                workspace, workspace_bytes, stream);
 }
 

@@ -339,6 +339,27 @@ __global__ __launch_bounds__(IT3_ROWS * WAVE) void rp_write_kernel(PairsArgs A) 
 }
 
 }  // namespace
+
+// the targets of all pairs sorted by (pair, cell): origin -> keys -> sort -> the targets in key order.  The grid of dr_radius_pairs_ragged_f32,
+// shared with the point-to-point ICP (icp.hip), whose targets never move (kernels.h)
+int launch_target_grid(int P, int nt, const float* tgt, const int* t_off, float cell, float4* origin, unsigned long long* keys, unsigned* vals,
+                       float4* sorted, hipStream_t st) {
+    if (nt <= 0) return DR_OK;
+    PairsArgs A = {};
+    A.P = P; A.nt = nt; A.n_pad = next_pow2(nt);
+    A.tgt = tgt; A.t_off = t_off; A.cell = cell;
+    A.origin = origin; A.keys = keys; A.vals = vals; A.sorted = sorted;
+    hipLaunchKernelGGL(rp_origin_kernel, dim3(P), dim3(IT3_BLOCK), 0, st, A);
+    DR_LAUNCH_CHECK();
+    hipLaunchKernelGGL(rp_key_kernel, dim3(it3_blocks(A.n_pad, IT3_BLOCK)), dim3(IT3_BLOCK), 0, st, A);
+    DR_LAUNCH_CHECK();
+    const int rc = launch_bitonic_sort(A.keys, A.vals, A.n_pad, st);
+    if (rc != DR_OK) return rc;
+    hipLaunchKernelGGL(rp_gather_kernel, dim3(it3_blocks(nt, IT3_BLOCK)), dim3(IT3_BLOCK), 0, st, A);
+    DR_LAUNCH_CHECK();
+    return DR_OK;
+}
+
 }  // namespace dr
 
 using namespace dr;
@@ -408,16 +429,8 @@ int dr_radius_pairs_ragged_f32(int P, int ns, int nt, const float* src, const in
         hipLaunchKernelGGL(rp_move_kernel, dim3(it3_blocks(ns, IT3_BLOCK)), dim3(IT3_BLOCK), 0, st, A);
         DR_LAUNCH_CHECK();
     }
-    if (nt > 0) {
-        hipLaunchKernelGGL(rp_origin_kernel, dim3(P), dim3(IT3_BLOCK), 0, st, A);
-        DR_LAUNCH_CHECK();
-        hipLaunchKernelGGL(rp_key_kernel, dim3(it3_blocks(A.n_pad, IT3_BLOCK)), dim3(IT3_BLOCK), 0, st, A);
-        DR_LAUNCH_CHECK();
-        const int rc = launch_bitonic_sort(A.keys, A.vals, A.n_pad, st);
-        if (rc != DR_OK) return rc;
-        hipLaunchKernelGGL(rp_gather_kernel, dim3(it3_blocks(nt, IT3_BLOCK)), dim3(IT3_BLOCK), 0, st, A);
-        DR_LAUNCH_CHECK();
-    }
+    const int grc = launch_target_grid(P, nt, tgt, t_offsets, A.cell, A.origin, A.keys, A.vals, A.sorted, st);
+    if (grc != DR_OK) return grc;
     if (ns > 0) {
         hipLaunchKernelGGL(rp_count_kernel, dim3(it3_blocks(ns, IT3_ROWS)), dim3(IT3_ROWS * WAVE), 0, st, A);
         DR_LAUNCH_CHECK();

@@ -179,6 +179,12 @@ int launch_top1_union(const T* conf, int P, int N, int M, long long* out, int* c
 // collate.hip: in-place bitonic sort of (key, value) pairs ascending by (key, value); n_pad = a power of two (pad keys ~0ull sort last)
 int launch_bitonic_sort(unsigned long long* keys, unsigned* vals, int n_pad, hipStream_t st);
 
+// item3d.hip: the targets [nt, 3] of P pairs (int32 device offsets, P + 1) sorted by (pair, cell) for the 27-cell sweep of item3d_index.h:
+// origin [P] = a pair's min corner, keys / vals [next_pow2(nt)] = the sorted (key, stacked row) list, sorted [nt] = (x, y, z, stacked row)
+// in key order.  A pair with bad offsets has no rows in the list.  nt = 0 launches nothing.
+int launch_target_grid(int P, int nt, const float* tgt, const int* t_off, float cell, float4* origin, unsigned long long* keys, unsigned* vals,
+                       float4* sorted, hipStream_t st);
+
 // KPConv influence of a kernel point at squared distance d2 (blocks.py:304-321): mode & 3 = 0 'constant', 1 'linear', 2 'gaussian'
 // (radius_gaussian with sigma = 0.3 extent, blocks.py:36-44); bit 2 of mode = aggregation 'closest' (applied by the caller: only the nearest
 // kernel point of a neighbour keeps its influence, blocks.py:324-326)

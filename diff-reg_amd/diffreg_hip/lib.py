@@ -565,6 +565,15 @@ SIGNATURES.update({
 })
 
 
+SIGNATURES.update({
+    # added after ABI 0.7.0, twenty-first set: point-to-point ICP (csrc/icp.hip; wrappers in diffreg_hip/registration.py) and Open3D's voxel origin
+    "dr_icp_p2p_workspace_bytes": (c_size_t, [c_int, c_int, c_int]),
+    "dr_icp_p2p_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_int] + [c_void_p] * 5 + [c_float, c_int, c_float, c_float] +
+                       [c_void_p] * 7 + [c_size_t, c_void_p]),
+    "dr_grid_subsample_open3d_f32": (c_int, [c_int, c_int, c_void_p, c_void_p, c_float] + [c_void_p] * 5 + [c_size_t, c_void_p]),
+})
+
+
 class DebugDdimArgs(ctypes.Structure):
     """dr_debug_ddim_args (include/diffreg_hip_debug.h): the DDIM kernel's launch argument, field for field"""
     _fields_ = [(n, c_void_p) for n in ("x", "x0", "shift", "noise", "src_mask", "tgt_mask")] + \
@@ -2101,10 +2110,11 @@ def rows_normalize_chw_backward(feats, grad_out, rows=None):
 # ------------------------------------------------------------------------------------------------
 # collate-time ops: stacked clouds [n,3] float32 + lengths int32 [nb], all on the device
 # ------------------------------------------------------------------------------------------------
-def grid_subsample(points, lengths, dl, vision3d=False):
+def grid_subsample(points, lengths, dl, vision3d=False, open3d=False):
     """-> (sub_points [n,3] buffer, sub_lengths [nb] int32, total [1] int32, status [1] int32), asynchronous; the first
     total[0] rows of the buffer are valid (cpp_subsampling.subsample_batch, grid_subsampling.cpp:4-211; vision3d = True: the
-    2D-3D loader's vision3d/csrc/cpu/grid_subsampling/grid_subsampling.cpp, whose grid origin is floor(min / dl) * dl)"""
+    2D-3D loader's vision3d/csrc/cpu/grid_subsampling/grid_subsampling.cpp, whose grid origin is floor(min / dl) * dl; open3d = True:
+    the origin of Open3D's voxel_down_sample, min - 0.5 * dl)"""
     points = points.to(torch.float32).contiguous()
     lengths = lengths.to(device=points.device, dtype=torch.int32).contiguous()
     n, nb = points.shape[0], lengths.shape[0]
@@ -2115,7 +2125,7 @@ def grid_subsample(points, lengths, dl, vision3d=False):
     status = torch.empty(1, dtype=torch.int32, device=dev)
     wsb = _lib.dr_grid_subsample_workspace_bytes(n, nb)
     ws = torch.empty(max(wsb, 16), dtype=torch.uint8, device=dev)
-    entry = _lib.dr_grid_subsample_vision3d_f32 if vision3d else _lib.dr_grid_subsample_f32
+    entry = _lib.dr_grid_subsample_open3d_f32 if open3d else _lib.dr_grid_subsample_vision3d_f32 if vision3d else _lib.dr_grid_subsample_f32
     check(entry(n, nb, ptr(points), ptr(lengths), float(dl), ptr(out), ptr(ol), ptr(tot), ptr(status), ptr(ws), wsb, stream_of(points)))
     return out, ol, tot, status
 

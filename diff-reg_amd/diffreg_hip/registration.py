@@ -6,6 +6,8 @@
     spatial_consistency, cross_spatial_consistency         vision3d/ops/spatial_consistency.py
     spatial_consistency_counts, SpatialConsistencyFiltering  vision3d/models/geotransformer/spatial_consistency_filtering.py
     leading_eigenvector                                    vision3d/ops/eigenvector.py
+    multi_scale_icp, icp, icp_pairs, voxel_down_sample,    vision3d/utils/open3d.py:378-396 (twenty-first set; csrc/icp.hip): the published
+    IterativeClosestPoint                                  loop of Open3D's point-to-point registration_icp, stated in the header
 
 Tensors on a ROCm device go through the library; CPU tensors take a plain-torch statement of the same rules (double sums, float32 residual
 and consistency rules), as elsewhere in the package.  Nothing here reads the device back except where a docstring says so."""
@@ -400,6 +402,244 @@ def leading_eigenvector(mat_or_points, method="power", num_iterations=10, tgt_po
     return (vec, its[:B].reshape(lead)) if return_iterations else vec
 
 
+# ---------------------------------------------------------------------------------------------- point-to-point ICP (twenty-first set)
+# vision3d/utils/open3d.py:378-396 (multi_scale_icp) runs Open3D's registration_icp per scale.  Open3D is not part of this project's
+# environment: the loop is STATED in include/diffreg_hip.h (dr_icp_p2p_f32) and both paths below are held to that statement; parity with
+# Open3D itself is not claimed.
+ICP_RANK_TOL = 1e-12
+
+
+def _cpu_icp_evaluate(T, src, tgt, r2):
+    """the float32 Evaluate(T) of the rule on CPU tensors -> (moved (n, 3), partner (n,) int64 or -1, d2 (n,))"""
+    a = [((T[i, 0] * src[:, 0] + T[i, 1] * src[:, 1]) + T[i, 2] * src[:, 2]) + T[i, 3] for i in range(3)]
+    moved = torch.stack(a, 1)
+    n = src.shape[0]
+    partner, best = torch.full((n,), -1, dtype=torch.int64), torch.zeros(n)
+    if n == 0 or tgt.shape[0] == 0:
+        return moved, partner, best
+    for lo in range(0, n, 2048):
+        m = moved[lo:lo + 2048]
+        dx, dy, dz = m[:, None, 0] - tgt[None, :, 0], m[:, None, 1] - tgt[None, :, 1], m[:, None, 2] - tgt[None, :, 2]
+        d2 = (dx * dx + dy * dy) + dz * dz
+        d2 = torch.where(d2 < r2, d2, torch.full_like(d2, float("inf")))
+        v = d2.min(1).values
+        j = (d2 == v[:, None]).to(torch.uint8).argmax(1)          # the lowest index among equal distances
+        ok = torch.isfinite(v)
+        partner[lo:lo + 2048] = torch.where(ok, j, torch.full_like(j, -1))
+        best[lo:lo + 2048] = torch.where(ok, v, torch.zeros_like(v))
+    return moved, partner, best
+
+
+def _cpu_icp_update(p, q):
+    """rule 1 with unit weights and eps = 0 in double -> (4 x 4 double update, status bits)"""
+    p, q = p.double(), q.double()
+    pc, qc = p.mean(0), q.mean(0)
+    H = (p - pc).T @ (q - qc) / p.shape[0]
+    U4, flags = torch.eye(4, dtype=torch.float64), 0
+    if bool(H.abs().sum() == 0):
+        flags = 16
+    else:
+        U, S, Vh = torch.linalg.svd(H)
+        if float(S[1]) <= ICP_RANK_TOL * float(S[0]):
+            flags = 16
+        V = Vh.T
+        D = torch.diag(torch.tensor([1.0, 1.0, float(torch.sign(torch.det(V @ U.T)))], dtype=torch.float64))
+        U4[:3, :3] = V @ D @ U.T
+    U4[:3, 3] = qc - U4[:3, :3] @ pc
+    return U4, flags
+
+
+def _cpu_icp(src, tgt, init, r, max_iteration, rel_fitness, rel_rmse):
+    f32 = lambda v: torch.tensor(v, dtype=torch.float32)
+    T = torch.eye(4) if init is None else init.float().clone()
+    T[3] = torch.tensor([0.0, 0.0, 0.0, 1.0])
+    r2 = f32(r) * f32(r)
+
+    def evaluate():
+        moved, partner, d2 = _cpu_icp_evaluate(T, src, tgt, r2)
+        n = int((partner >= 0).sum())
+        fit = f32(n / src.shape[0]) if src.shape[0] else f32(0.0)
+        rmse = f32(float(torch.sqrt(d2.double().sum() / n))) if n else f32(0.0)
+        return moved, partner, n, fit, rmse
+    moved, partner, n, fit, rmse = evaluate()
+    its, status = 0, 0
+    while True:
+        if n == 0:
+            status |= 32
+            break
+        if its >= max_iteration:
+            break
+        keep = partner >= 0
+        U4, flags = _cpu_icp_update(moved[keep], tgt[partner[keep]])
+        status |= flags
+        T = (U4 @ T.double()).float()
+        T[3] = torch.tensor([0.0, 0.0, 0.0, 1.0])
+        its += 1
+        last_fit, last_rmse = fit, rmse
+        moved, partner, n, fit, rmse = evaluate()
+        if bool((last_fit - fit).abs() < f32(rel_fitness)) and bool((last_rmse - rmse).abs() < f32(rel_rmse)):
+            if n == 0:
+                status |= 32
+            break
+    return T, fit, rmse, its, status, partner
+
+
+def icp_pairs(src_points, tgt_points, s_offsets, t_offsets, init_transforms=None, distance_threshold=0.05, max_iteration=30,
+              relative_fitness=1e-6, relative_rmse=1e-6, return_correspondence=False, host_s_offsets=None, host_t_offsets=None):
+    """Point-to-point ICP (the loop of Open3D's registration_icp with TransformationEstimationPointToPoint(False), as stated for
+    dr_icp_p2p_f32) for P pairs in one call: src_points (ns, 3), tgt_points (nt, 3) stacked, s_offsets / t_offsets (P + 1,) int32 on the
+    device, init_transforms (P, 4, 4) or None (identity).  -> dict(transforms (P, 4, 4), fitness (P,), inlier_rmse (P,), iterations (P,)
+    int32, status (P,) int32; with return_correspondence also correspondence (ns,) int32: the pair-local partner of every source row or -1).
+    Nothing is read back.  A pair with status bit 4 or 8 is skipped: its rows keep what this wrapper put there (the initial transform, zeros,
+    -1).  Bit 16: a fit met a rank-deficient H; bit 32: an evaluation found no correspondence."""
+    src, tgt = _f32(src_points), _f32(tgt_points)
+    so, to = s_offsets.to(torch.int32).contiguous(), t_offsets.to(torch.int32).contiguous()
+    P, ns, nt, dev = so.numel() - 1, src.shape[0], tgt.shape[0], src.device
+    init = None if init_transforms is None else _f32(init_transforms).reshape(P, 16)
+    if not src.is_cuda:
+        a, b = so.tolist(), to.tolist()
+        res = [_cpu_icp(src[a[p]:a[p + 1]], tgt[b[p]:b[p + 1]], None if init is None else init[p].view(4, 4), distance_threshold,
+                        max_iteration, relative_fitness, relative_rmse) for p in range(P)]
+        out = dict(transforms=torch.stack([r[0] for r in res]) if P else torch.zeros(0, 4, 4),
+                   fitness=torch.tensor([float(r[1]) for r in res]), inlier_rmse=torch.tensor([float(r[2]) for r in res]),
+                   iterations=torch.tensor([r[3] for r in res], dtype=torch.int32), status=torch.tensor([r[4] for r in res], dtype=torch.int32))
+        if return_correspondence:
+            out["correspondence"] = torch.cat([r[5] for r in res]).to(torch.int32) if P else torch.zeros(0, dtype=torch.int32)
+        return out
+    lib.ensure_init()
+    n = max(P, 1)
+    T = torch.eye(4, device=dev).reshape(1, 16).repeat(n, 1) if init is None else init.clone()
+    fit, rmse = torch.zeros(n, device=dev), torch.zeros(n, device=dev)
+    its, st = _i32(dev, n, 0), _i32(dev, n, 0)
+    corr = _i32(dev, max(ns, 1), -1) if return_correspondence else None
+    wsb = _raw.dr_icp_p2p_workspace_bytes(P, ns, nt)
+    ws = _ws(wsb, dev)
+    hp = lambda h: None if h is None else h.ctypes.data
+    check(_raw.dr_icp_p2p_f32(P, ns, ptr(src), ptr(so), nt, ptr(tgt), ptr(to), hp(host_s_offsets), hp(host_t_offsets), ptr(init),
+                              float(distance_threshold), int(max_iteration), float(relative_fitness), float(relative_rmse), ptr(T), ptr(fit),
+                              ptr(rmse), ptr(its), ptr(corr), ptr(st), ptr(ws), wsb, stream_of(src)))
+    out = dict(transforms=T[:P].view(P, 4, 4), fitness=fit[:P], inlier_rmse=rmse[:P], iterations=its[:P], status=st[:P])
+    if return_correspondence:
+        out["correspondence"] = corr[:ns]
+    return out
+
+
+def icp(src_points, tgt_points, init_transform=None, distance_threshold=0.05, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6,
+        return_correspondence=False):
+    """icp_pairs for one pair: (N, 3), (M, 3), init_transform (4, 4) or None -> dict(transform (4, 4), fitness, inlier_rmse, iterations,
+    status: 0-d tensors[, correspondence (N,)])"""
+    dev = src_points.device
+    so = torch.tensor([0, src_points.shape[0]], dtype=torch.int32, device=dev)
+    to = torch.tensor([0, tgt_points.shape[0]], dtype=torch.int32, device=dev)
+    r = icp_pairs(src_points, tgt_points, so, to, None if init_transform is None else init_transform[None], distance_threshold, max_iteration,
+                  relative_fitness, relative_rmse, return_correspondence)
+    out = dict(transform=r["transforms"][0], fitness=r["fitness"][0], inlier_rmse=r["inlier_rmse"][0], iterations=r["iterations"][0],
+               status=r["status"][0])
+    if return_correspondence:
+        out["correspondence"] = r["correspondence"]
+    return out
+
+
+def _cpu_voxel_down_sample(points, voxel_size):
+    p = points.float()
+    if p.shape[0] == 0:
+        return p
+    v = torch.tensor(voxel_size, dtype=torch.float32)
+    origin = p.min(0).values - torch.tensor(0.5, dtype=torch.float32) * v
+    idx = torch.floor((p - origin) / v).to(torch.int64)
+    key = (idx[:, 2] << 42) | (idx[:, 1] << 21) | idx[:, 0]
+    uniq, inv = torch.unique(key, return_inverse=True)                   # ascending (iz, iy, ix)
+    out = torch.zeros(uniq.shape[0], 3)
+    cnt = torch.zeros(uniq.shape[0], dtype=torch.int64)
+    for i in range(p.shape[0]):                                          # the float32 sum in input order
+        out[inv[i]] = out[inv[i]] + p[i]
+        cnt[inv[i]] += 1
+    return out * (1.0 / cnt.double()).float()[:, None]
+
+
+def voxel_down_sample(points, voxel_size, lengths=None, return_status=False):
+    """Open3D's PointCloud.voxel_down_sample (the barycentre of every voxel of the grid that starts at min - 0.5 * voxel_size), on
+    dr_grid_subsample_open3d_f32.  The rows come in this library's voxel-key order (ascending (iz, iy, ix)); Open3D's order is a hash map's
+    and unspecified.  lengths None: points (N, 3) is one cloud -> (M, 3); ONE word is read back, the number of voxels, to size the result.
+    lengths (nb,) int32: stacked clouds -> (buffer (N, 3), out_lengths (nb,) int32) with nothing read back; the rows of the buffer behind
+    out_lengths.sum() are unspecified.  return_status appends the grid subsample's status word, a (1,) int32 tensor on the points' device
+    that is not read here: non-zero when a cloud spans more voxels per axis than the 16 key bits hold (the output is then unspecified)."""
+    pts = _f32(points)
+    if not pts.is_cuda:
+        ok = torch.zeros(1, dtype=torch.int32)
+        if lengths is None:
+            out = _cpu_voxel_down_sample(pts, voxel_size)
+            return (out, ok) if return_status else out
+        cut = [0] + torch.cumsum(lengths.to(torch.int64), 0).tolist()
+        parts = [_cpu_voxel_down_sample(pts[a:b], voxel_size) for a, b in zip(cut[:-1], cut[1:])]
+        buf = torch.zeros(max(pts.shape[0], 1), 3)
+        got = torch.cat(parts) if parts else pts[:0]
+        buf[:got.shape[0]] = got
+        ol = torch.tensor([q.shape[0] for q in parts], dtype=torch.int32)
+        return (buf, ol, ok) if return_status else (buf, ol)
+    lib.ensure_init()
+    one = lengths is None
+    ln = torch.tensor([pts.shape[0]], dtype=torch.int32, device=pts.device) if one else lengths
+    out, ol, tot, st = lib.grid_subsample(pts, ln, voxel_size, open3d=True)
+    if one:
+        out = out[:int(tot.item())]                                      # the one word read back
+        return (out, st) if return_status else out
+    return (out, ol, st) if return_status else (out, ol)
+
+
+def _offsets_of(lengths):
+    z = torch.zeros(1, dtype=torch.int64, device=lengths.device)
+    return torch.cat([z, torch.cumsum(lengths.to(torch.int64), 0)]).to(torch.int32)
+
+
+def multi_scale_icp(src_points, tgt_points, init_transform, multi_scale_icp_cfgs, distance_threshold, src_lengths=None, tgt_lengths=None,
+                    relative_fitness=1e-6, relative_rmse=1e-6, return_status=False):
+    """vision3d.utils.open3d.multi_scale_icp: for each cfg (a dict with "max_iteration" and "voxel_size") both clouds are voxel-down-sampled
+    and refined by point-to-point ICP from the previous transform.  One pair: (N, 3), (M, 3), init_transform (4, 4) -> (4, 4).  A batch:
+    stacked clouds with src_lengths / tgt_lengths (P,) int32 and init_transform (P, 4, 4) -> (P, 4, 4), ragged in one call per scale.  The
+    offsets of every scale come from the device lengths of the down-sample, and the ICP takes the down-sample's buffers at their capacity:
+    no host read per scale was needed, and none is made.  A pair that a scale skips (status bit 4 or 8) or finds without correspondence
+    (bit 32) goes on with the transform it had; return_status=True returns (transforms, status) with status (P,) int32 -- () for one pair --
+    the OR over the scales of icp_pairs' status words, plus bit 1 where a down-sample reported a voxel range beyond its key bits (that
+    word is per call, so every pair of the batch gets it).  The status stays on the device."""
+    one = src_lengths is None
+    dev = src_points.device
+    sl = torch.tensor([src_points.shape[0]], dtype=torch.int32, device=dev) if one else src_lengths.to(device=dev, dtype=torch.int32)
+    tl = torch.tensor([tgt_points.shape[0]], dtype=torch.int32, device=dev) if one else tgt_lengths.to(device=dev, dtype=torch.int32)
+    T = _f32(init_transform)[None] if one else _f32(init_transform)
+    status = torch.zeros(T.shape[0], dtype=torch.int32, device=dev)
+    for cfg in multi_scale_icp_cfgs:
+        s, s_len, s_st = voxel_down_sample(src_points, cfg["voxel_size"], sl, True)
+        t, t_len, t_st = voxel_down_sample(tgt_points, cfg["voxel_size"], tl, True)
+        r = icp_pairs(s, t, _offsets_of(s_len), _offsets_of(t_len), T, distance_threshold, cfg["max_iteration"], relative_fitness,
+                      relative_rmse)
+        T = r["transforms"]
+        status = status | r["status"] | ((s_st | t_st) != 0).to(torch.int32)
+    if return_status:
+        return (T[0], status[0]) if one else (T, status)
+    return T[0] if one else T
+
+
+class IterativeClosestPoint(nn.Module):
+    """point-to-point ICP with fixed settings; forward(src_points, tgt_points, init_transform=None) is icp(...)"""
+
+    def __init__(self, distance_threshold, max_iteration=30, relative_fitness=1e-6, relative_rmse=1e-6):
+        super().__init__()
+        self.distance_threshold = distance_threshold
+        self.max_iteration = max_iteration
+        self.relative_fitness = relative_fitness
+        self.relative_rmse = relative_rmse
+
+    def forward(self, src_points, tgt_points, init_transform=None):
+        return icp(src_points, tgt_points, init_transform, self.distance_threshold, self.max_iteration, self.relative_fitness,
+                   self.relative_rmse)
+
+    def extra_repr(self):
+        return "distance_threshold=%g, max_iteration=%d, relative_fitness=%g, relative_rmse=%g" % (
+            self.distance_threshold, self.max_iteration, self.relative_fitness, self.relative_rmse)
+
+
 __all__ = ["weighted_procrustes", "weighted_procrustes_groups", "WeightedProcrustes", "LocalGlobalRegistration",
            "local_to_global_registration_pairs", "spatial_consistency", "cross_spatial_consistency", "spatial_consistency_counts",
-           "SpatialConsistencyFiltering", "leading_eigenvector"]
+           "SpatialConsistencyFiltering", "leading_eigenvector", "icp_pairs", "icp", "voxel_down_sample", "multi_scale_icp",
+           "IterativeClosestPoint"]

@@ -86,7 +86,9 @@ extern "C" {
  *          with dr_nn_stats_workspace_bytes, dr_flow_metrics_f32 with dr_flow_metrics_workspace_bytes (new entries only; nothing older changed).
  *   0.7.0, twentieth set (same rule)  the RANSAC-free rigid estimators: dr_weighted_procrustes_f32 with dr_lgr_wave_limit, dr_lgr_f32 with
  *          dr_lgr_workspace_bytes, dr_spatial_consistency_f32, dr_sc_row_sums_f32 with dr_sc_block / dr_sc_tile, dr_sc_leading_eigenvector_f32
- *          with dr_sc_leading_eigenvector_workspace_bytes (new entries only; nothing older changed). */
+ *          with dr_sc_leading_eigenvector_workspace_bytes (new entries only; nothing older changed).
+ *   0.7.0, twenty-first set (same rule)  point-to-point ICP on the dense clouds: dr_icp_p2p_f32 with dr_icp_p2p_workspace_bytes,
+ *          dr_grid_subsample_open3d_f32 (new entries only; nothing older changed). */
 #define DR_ABI_VERSION 700
 int dr_version(void);                 /* major*10000 + minor*100 + patch */
 const char* dr_strerror(int code);
@@ -2055,6 +2057,68 @@ size_t dr_sc_leading_eigenvector_workspace_bytes(int P, int n);
 int dr_sc_leading_eigenvector_f32(int P, int n, const float* src_points, const float* tgt_points, const int32_t* offsets,
                                   const int32_t* host_offsets, float sigma, const float* mat, const int64_t* mat_offsets, int num_iterations,
                                   float* out, int32_t* iterations, int32_t* status, void* workspace, size_t workspace_bytes, void* stream);
+
+/* ---------------------------------------------------------------------------------------------
+ * Added after ABI 0.7.0, twenty-first set (detected by symbol like the fourth to twentieth sets): the refinement every registration user
+ * runs after the coarse pose, multi_scale_icp of 2D-3D vision3d/utils/open3d.py:378-396 -- per scale a voxel down-sample of both clouds and
+ * Open3D's registration_icp with TransformationEstimationPointToPoint(False).  csrc/icp.hip, indices in csrc/icp_index.h; the down-sample
+ * in csrc/collate.hip; DESIGN 5ze.  Open3D is not part of this project's environment: PARITY WITH OPEN3D ITSELF IS NOT CLAIMED.  The
+ * published loop is stated below and the kernels are held to that statement (tests/icp_ref.py).
+ *
+ * Conventions of the fourteenth and twentieth sets: ragged over P pairs through int32 DEVICE arrays of P + 1 offsets with optional HOST
+ * mirrors (a mirror that does not start at >= 0, ascend and end at <= the row count is DR_EINVAL), asynchronous on `stream`, nothing
+ * allocated, nothing read back, no floating-point atomic: two runs are bit-equal and the call can be captured on one stream.  status [P]:
+ * bit 4 = the pair's source or target offsets do not ascend from entry 0 inside [0, rows]; bit 8 = a NaN / Inf coordinate of the pair, or
+ * a NaN / Inf in the first three rows of its initial transform.  A pair with bit 4 or 8 is SKIPPED: none of its outputs but the status word
+ * is written.  P = 0 is a no-op; a negative size, a NULL pointer that a non-empty array needs, max_correspondence_distance that is not
+ * positive and finite, max_iteration outside [0, 4096] or a negative / NaN relative_* is DR_EINVAL; more than 65 535 pairs or 2^31 / 3
+ * stacked rows DR_ENOSUP (P is meant to be a BATCH size: the kernels map rows and workgroups to pairs by walking the offsets, O(P)
+ * reads per target row, per workgroup of the sweep and per pair of the set-up; the limit is what the 16 pair bits of the grid key hold, not a
+ * size at which the call is fast); a missing or short workspace DR_EWORKSPACE (16-byte aligned, else DR_EINVAL; transforms and init_transforms are
+ * 16-byte aligned as well): all reported before the first launch.
+ *
+ * dr_icp_p2p_f32, THE RULE.  With r = max_correspondence_distance and T a float32 [R | t]:
+ *   Evaluate(T): every source row of the pair is moved by THE RESIDUAL RULE of dr_lgr_f32, x' = ((R00 x + R01 y) + R02 z) + t0 and
+ *     likewise y', z', float32, never contracted; d2 = (dx dx + dy dy) + dz dz of (x' - target).  The partner of a row is the target of its
+ *     OWN pair with the smallest (d2, pair-local target index) among those with d2 < r * r (float32 compares; r * r rounded once); none: -1.
+ *     n_corr = rows with a partner; fitness = float32(n_corr / n_src) (0 for an empty source); inlier_rmse = float32(sqrt(sum d2 /
+ *     n_corr)), the sum of the float32 d2 in double; 0 when n_corr = 0.
+ *   Loop: res = Evaluate(init) (init_transforms NULL: identity; only the first three rows are read, the fourth is written as 0 0 0 1).
+ *     Then at most max_iteration times: (1) update = the fit of RULE 1 with unit weights and eps = 0 on (moved source, partner) over the
+ *     current correspondences -- pc, qc the means, H = (sum p q^T - (sum p)(sum q)^T / n) / n from the moments in double, taken about
+ *     the min corner of the pair's targets (a target coordinate that equals the min corner's over all partners then gives an exactly
+ *     zero column of H; any other rank-deficient set of partners gives an H that is rank-deficient only up to rounding of the moments, about
+ *     1e-16 relative, and is detected only when its second singular value still falls under the 1e-12 below), svd3_jacobi,
+ *     R = V diag(1, 1, sign det(V U^T)) U^T, t = qc - R pc; (2) T = update * T, in double on the float32 T, rounded once to float32;
+ *     (3) new = Evaluate(T); (4) new becomes the result, and the pair stops when both |res.fitness - new.fitness| < relative_fitness and
+ *     |res.rmse - new.rmse| < relative_rmse hold (float32 subtractions and compares).  iterations [P] = the fits that ran.
+ *     max_iteration = 0 is evaluation only.  A pair whose evaluation has no correspondence stops there with status bit 32 and keeps its
+ *     transform.  A fit whose H has rank <= 1 (second singular value <= 1e-12 of the first: one or two correspondences, collinear
+ *     targets) follows rule 1 -- R is the proper rotation with the Jacobi SVD's completion of the basis, not LAPACK's -- and sets status
+ *     bit 16; an all-zero H (one correspondence) gives R = identity, t = qc - pc, and bit 16 as well.  The loop goes on after bit 16.
+ *   The sums: a workgroup of the sweep owns 64 consecutive source rows of one pair; wave w adds rows w, w + 4, ... of them ascending; the
+ *     four waves are added ascending into the workgroup's partial; the finish adds a pair's partials ascending.  The order depends on the
+ *     shapes alone.
+ *   Outputs: transforms [P, 16] row-major 4 x 4; fitness, inlier_rmse [P] of the last evaluation; iterations [P]; correspondence [ns] or
+ *     NULL: per stacked source row the pair-local partner (or -1) of the last evaluation; status [P]: 0 or bits 4, 8, 16, 32.
+ *   Launches: 1 (status) + the target grid (origin, key, bitonic sort, gather: cells of edge r (1 + 2^-7), the grid of
+ *     dr_radius_pairs_ragged_f32, built once because targets never move) + 2 for the evaluation of init, then 2 per iteration (the sweep and
+ *     the finish), whatever P.  A pair that has stopped sets a DEVICE flag: later launches leave it untouched.  No scratch; LDS: 544 bytes
+ *     (4 waves x 17 doubles) in the sweep, 136 bytes in the finish.  Workspace: dr_icp_p2p_workspace_bytes(P, ns, nt).
+ * dr_grid_subsample_open3d_f32: dr_grid_subsample_vision3d_f32 with the origin of Open3D's PointCloud::VoxelDownSample, origin = min_corner -
+ *   0.5 * voxel_size in float32; voxel = floor((p - origin) / voxel_size) per axis; the barycentre as in the other two entries (float32 sum
+ *   in input order, times the float reciprocal of the count; Open3D sums in double).  Same arguments, same workspace
+ *   (dr_grid_subsample_workspace_bytes).  The output order is this library's voxel-key order, per cloud ascending (iz, iy, ix): Open3D emits
+ *   the order of a std::unordered_map, which is unspecified. */
+size_t dr_icp_p2p_workspace_bytes(int P, int ns, int nt);
+int dr_icp_p2p_f32(int P, int ns, const float* src, const int32_t* s_offsets, int nt, const float* tgt, const int32_t* t_offsets,
+                   const int32_t* host_s_offsets, const int32_t* host_t_offsets, const float* init_transforms,
+                   float max_correspondence_distance, int max_iteration, float relative_fitness, float relative_rmse, float* transforms,
+                   float* fitness, float* inlier_rmse, int32_t* iterations, int32_t* correspondence, int32_t* status, void* workspace,
+                   size_t workspace_bytes, void* stream);
+int dr_grid_subsample_open3d_f32(int n, int nb, const float* points, const int32_t* lengths, float voxel_size, float* out_points,
+                                 int32_t* out_lengths, int32_t* out_total, int32_t* status, void* workspace, size_t workspace_bytes,
+                                 void* stream);
 
 #ifdef __cplusplus
 }
